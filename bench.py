@@ -9,8 +9,8 @@
 workload `tiles` (BASELINE configs[1]): one "step" = one pass of the hot path over one batch of synthetic EM tiles
 already resident in HBM as uint8: fused normalisation + Panoptic-DeepLab/PointRend forward (fp16 MFMA, fp32
 accumulate) + sigmoid + centre NMS/voting + panoptic merge -> int64 label maps on the device, 32 distinct 1024x1024
-tiles per GPU.  Tiles are independent: N GPUs shard tiles with no data-path collective ("weak" scaling).  The same
-JSON line also carries the Engine2d-level rate (host uint8 tile -> int32 numpy label map incl. force_connected and
+tiles per GPU.  Tiles are independent: N GPUs shard tiles with no data-path collective ("weak" scaling).  With --full
+the same JSON line also carries the Engine2d-level rate (host uint8 tile -> int32 numpy label map incl. force_connected and
 both PCIe copies, pipelined), the batch-1 latency, and -- N = 1 only, outside the timed region -- the CPU port beside
 it and the 512^3 ortho-plane job (configs[2]).
 
@@ -18,9 +18,14 @@ workload `stack3d` (configs[3] in small): a procedural (hash-seeded, never store
 PER GPU of `--size`^2, xy stack inference with the recursive median through MultiGPUEngine3d's slab pipeline
 (RCCL neighbour halo + filtered carry) + matching / tracking on rank 0; value = voxels/s of the whole job.
 
-N > 1, workload `tiles`: after the tile measurement rank 0 runs the z-slab job (`--slab-depth` slices of `--slab-size`^2 per
+N > 1, workload `tiles`, --full: after the tile measurement rank 0 runs the z-slab job (`--slab-depth` slices of `--slab-size`^2 per
 rank) as a bounded CHILD job on the same GPUs (`slab_job_child`, internal workload `slabjob`) and reports it as the
 `stack3d` block -- the headline line never depends on the only part of the bench with neighbour traffic between ranks.
+
+A plain run sets up, warms up, times `--steps` steps and prints the headline; everything else the line can carry (the
+uninstrumented repeat, batch-1 latency, Engine2d rate, CPU baseline and parity, the fp32 / fp16x3 modes, fine boundaries,
+the 3-D job, the N > 1 z-slab child job) runs only with `--full`.  `--dump-outputs DIR` writes what the timed path
+computed in its last step as DIR/<name>.npy (float32 / float64, a fixed seeded sample of at most 60 MB).
 
 Prints ONE JSON line on rank 0.
 """
@@ -66,7 +71,39 @@ def parse_args():
     ap.add_argument('--slab-depth', type=int, default=16, help='tiles workload, N > 1: slices per rank of that job')
     ap.add_argument('--ks', type=int, default=3, help='stack3d workload: median kernel size')
     ap.add_argument('--slab-timeout', type=float, default=420.0, help='tiles workload, N > 1: bound (s) on the z-slab job, which runs as a child job of its own')
+    ap.add_argument('--full', action='store_true', help='also run every measurement beyond the headline (the options above that '
+                                                         'name one: latency, Engine2d, CPU baseline, parity, fp32 / fp16x3 modes, '
+                                                         'fine boundaries, 3-D job, z-slab child job, uninstrumented repeat)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64; a fixed seeded sample)")
     return ap.parse_args()
+
+
+DUMP_BYTES = 60_000_000      # --dump-outputs: at most this many bytes in all
+
+
+def dump_outputs(dirname, arrays):
+    """arrays: name -> array with a leading item axis (tiles, slices).  Writes DIR/<name>.npy for each, float32 when that
+    holds the values exactly, else float64; when the whole does not fit DUMP_BYTES, the same seeded choice of items
+    (sorted, seed 0) is kept from every array and its indices go to DIR/<name>_index.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    n = min(len(v) for v in arrays.values())
+
+    def float_type(v):
+        if v.dtype.kind == 'f':
+            return np.float32 if v.dtype.itemsize <= 4 else np.float64
+        return np.float32 if v.size == 0 or int(np.abs(v).max()) < 2 ** 24 else np.float64
+
+    types = {name: float_type(v) for name, v in arrays.items()}
+    per_item = sum(v[0].size * np.dtype(types[name]).itemsize for name, v in arrays.items())
+    k = max(1, min(n, DUMP_BYTES // max(1, per_item)))
+    idx = np.arange(n) if k == n else np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+    for name, v in arrays.items():
+        np.save(os.path.join(dirname, name + '.npy'), v[idx].astype(types[name]))
+        if k < n:
+            np.save(os.path.join(dirname, name + '_index.npy'), idx.astype(np.float64))
 
 
 def launch_ranks(args):
@@ -501,9 +538,13 @@ def run_tiles(args, rank, local_rank, world, dist_on, dev):
     if dist_on:
         dist.barrier()
     torch.cuda.synchronize()
+    last_outs = None
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step(True)
+    for i in range(args.steps):
+        if i + 1 < args.steps:
+            step(True)
+        else:
+            last_outs = step(True)      # the last step's label maps: what --dump-outputs writes
     torch.cuda.synchronize()
     if dist_on:
         dist.barrier()
@@ -517,16 +558,21 @@ def run_tiles(args, rank, local_rank, world, dist_on, dev):
     dom_ms, dom_flops, dom_launches = model.profile_read()
     model.profile(False)
     flops_fwd = model.last_flops() * (B / mb)  # per step (last_flops is per forward call of mb tiles)
-    # the same K steps once more WITHOUT the HIP-event pairs around the dominant kernel's launches: what the
-    # instrumentation inside the timed region costs (reported, not the headline)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        step(False)
-    torch.cuda.synchronize()
-    ms_plain = (time.perf_counter() - t1) * 1e3 / args.steps
+    if rank == 0 and args.dump_outputs and last_outs is not None:
+        dump_outputs(args.dump_outputs, {'panoptic_labels': torch.cat(last_outs).cpu().numpy()})
+    del last_outs
+    ms_plain = None
+    if args.full:
+        # the same K steps once more WITHOUT the HIP-event pairs around the dominant kernel's launches: what the
+        # instrumentation inside the timed region costs (reported, not the headline)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            step(False)
+        torch.cuda.synchronize()
+        ms_plain = (time.perf_counter() - t1) * 1e3 / args.steps
     slab_block = None
-    if dist_on and args.stack3d > 0:        # outside the timed region of `value`, and outside this job altogether
+    if args.full and dist_on and args.stack3d > 0:        # outside the timed region of `value`, and outside this job altogether
         slab_block = slab_job_child(args, rank, world)
     fwd_total_ms = sum(a.elapsed_time(b) for a, b in fwd_ms)
     ms_per_step = dt * 1e3 / args.steps
@@ -553,7 +599,7 @@ def run_tiles(args, rank, local_rank, world, dist_on, dev):
                                f"post-processing to int64 label maps on the device; `value` is the fp16 ENGINE (precision='fp16', "
                                f"the explicit throughput opt-in: BASELINE's metric is quoted in fp16); the product's default "
                                f"precision 'fp16x3' -- the one within 1e-3 (max norm) of the reference's fp32 forward -- is timed on "
-                               f"the same tiles under `fp16x3_mode`",
+                               f"the same tiles under `fp16x3_mode` (--full)",
                    'precision': args.precision, 'default_precision_of_the_product': 'fp16x3',
                    'tile': S, 'batch_per_gpu': B, 'micro_batch': mb, 'weights': 'seeded random init (seed 0)',
                    'parallelism': f'tile-sharded x{world}, no data-path collective; RCCL ranks: '
@@ -574,11 +620,17 @@ def run_tiles(args, rank, local_rank, world, dist_on, dev):
                      'forward_tflops': round(fwd_tflops, 2), 'forward_frac': round(fwd_tflops / PEAK_F16_TFLOPS, 4),
                      'flops_per_tile': round(flops_fwd / B / 1e9, 2), 'forward_ms_per_step': round(fwd_ms_per_step, 3)},
         'arena_gib': round(model.arena_bytes() / 2 ** 30, 2),
-        'ms_per_step_uninstrumented': round(ms_plain, 3),
-        'uninstrumented_note': 'the same steps on this rank without the HIP-event pairs around the dominant kernel (untimed extra pass)',
+        'full': args.full,
     }
+    if not args.full:      # a plain run: the headline and its roofline block only
+        res['forward_steps_bench_loop'] = args.warmup + args.steps
+        res['forward_calls_total'] = model.forward_calls
+        res['stack3d'] = None
+        return res
+    res['ms_per_step_uninstrumented'] = round(ms_plain, 3)
+    res['uninstrumented_note'] = 'the same steps on this rank without the HIP-event pairs around the dominant kernel (untimed extra pass)'
     res['forward_steps_bench_loop'] = args.warmup + 2 * args.steps
-    res['forward_steps_note'] = ('forward calls of the step loop: warm-up + timed + the uninstrumented repeat; with --engine2d 0 '
+    res['forward_steps_note'] = ('forward calls of the step loop: warm-up + timed + the uninstrumented repeat (--full); with --engine2d 0 '
                                  '--latency 0 --fp32-mode 0 --no-cpu-baseline --stack3d 0 that is every forward of the process = the '
                                  'stem_pool_kernel launches of its rocprofv3 trace (tools/step_breakdown.py, tools/hbm_traffic.py '
                                  'count them there); `forward_calls_total` = every forward call of this model object in the process')
@@ -928,6 +980,10 @@ def run_stack3d(args, rank, local_rank, world, dist_on, dev):
 
 def main():
     args = parse_args()
+    if args.dump_outputs and args.workload != 'tiles':
+        print('bench.py: --dump-outputs writes the label maps of the tiles workload; other workloads have no array output',
+              file=sys.stderr)
+        sys.exit(2)
     if 'RANK' not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args))
     import torch

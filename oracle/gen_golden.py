@@ -1,6 +1,7 @@
 """Generate tests/golden/*.npz by importing the REFERENCE (build container only).
 
     python oracle/gen_golden.py            # needs /root/reference, CPU only
+    python oracle/gen_golden.py exports    # the TorchScript export fixtures of tests/test_load_export.py
 
 The reference cannot travel to the GPU box, so its outputs on seeded inputs are
 committed as small fixtures; the inputs are either stored next to them or are
@@ -116,7 +117,8 @@ def gen_bifpn():
             B = weights.fold_state_dict({k: v.numpy() for k, v in m.state_dict().items()}, cfg)
             for n in A:
                 assert np.allclose(A[n][0], B[n][0], atol=1e-6, rtol=1e-5) and np.allclose(A[n][1], B[n][1], atol=1e-5, rtol=1e-4), n
-    save('bifpn_forward', **out)
+    for part in ('m1', 'm4a', 'm4b'):      # each file under 1 MiB (tests/golden_files.py reads the parts back as one)
+        save(f'bifpn_forward.{part}', **{k: v for k, v in out.items() if k.startswith(part)})
 
 
 def gen_regnet():
@@ -164,7 +166,8 @@ def gen_regnet():
             # the export's key layout with the shapes behind it: weights.infer_cfg reads the architecture from exactly this
             out[f'{tag}_fused_keys'] = np.array(sorted(fsd.keys()))
             out[f'{tag}_fused_shapes'] = np.array([','.join(str(d) for d in fsd[k].shape) for k in sorted(fsd.keys())])
-    save('regnet_forward', **out)
+    for part in ('x', 'y'):      # each file under 1 MiB (tests/golden_files.py reads the parts back as one)
+        save(f'regnet_forward.{part}', **{k: v for k, v in out.items() if k.startswith(part)})
 
 
 # ----------------------------------------------------------------------------
@@ -530,3 +533,55 @@ if __name__ == '__main__' and 'regnet' in (sys.argv[1:] or ['regnet']):
     gen_regnet()
 if __name__ == '__main__' and 'tiles' in (sys.argv[1:] or ['tiles']):
     gen_tiles()
+
+
+# ----------------------------------------------------------------------------
+# E. TorchScript exports of the reference's fused models (tests/test_load_export.py)
+# ----------------------------------------------------------------------------
+EXPORT_PDL_KW = dict(encoder='resnet50', num_classes=1, stage4_stride=16, decoder_channels=256, low_level_stages=[1],
+                     low_level_channels_project=[32], atrous_rates=[2, 4, 6], aspp_channels=None, aspp_dropout=0.5,
+                     ins_decoder=True, ins_ratio=0.5, num_fc=3, train_num_points=1024, oversample_ratio=3,
+                     importance_sample_ratio=0.75, subdivision_steps=2, subdivision_num_points=8192)
+EXPORT_BIFPN_KW = dict(encoder='resnet50', num_classes=4, fpn_dim=128, fpn_layers=2, ins_decoder=True, depthwise=True, num_fc=3,
+                       train_num_points=1024, oversample_ratio=3, importance_sample_ratio=0.75, subdivision_steps=2,
+                       subdivision_num_points=2048)
+
+
+def export_cases():
+    """case name -> (arch, constructor kwargs, input side): the exports tests/test_load_export.py loads"""
+    pdl = dict(EXPORT_PDL_KW)
+    return {
+        'pdl_default': ('PanopticDeepLabPR', pdl, 64),
+        'pdl_odd': ('PanopticDeepLabPR', dict(pdl, num_classes=3, decoder_channels=128, aspp_channels=192, low_level_stages=[2, 1],
+                                              low_level_channels_project=[64, 32], atrous_rates=[3, 6, 9], stage4_stride=32,
+                                              num_fc=2, subdivision_num_points=4096), 64),
+        'pdl_ratio': ('PanopticDeepLabPR', dict(pdl, low_level_channels_project=[22], ins_ratio=0.7), 64),
+        'bifpn': ('PanopticBiFPNPR', dict(EXPORT_BIFPN_KW), 128),
+        'regnet_bifpn_y': ('PanopticBiFPNPR', dict(EXPORT_BIFPN_KW, encoder='regnety_6p4gf', num_classes=3), 128),
+        'regnet_pdl_x': ('PanopticDeepLabPR', dict(pdl, encoder='regnetx_6p4gf'), 64),
+        'regnet_pdl_y': ('PanopticDeepLabPR', dict(pdl, encoder='regnety_6p4gf'), 64),
+    }
+
+
+def gen_exports():
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import export_case
+    from empanada.models import quantization as quant_models
+    for i, (case, (arch, kw, size)) in enumerate(export_cases().items()):
+        torch.manual_seed(0)
+        model = quant_models.__dict__['Quantizable' + arch](**kw, quantize=False)
+        model.eval()
+        model.fuse_model()
+        sd = model.state_dict()
+        seed = 100 + i
+        keys = list(sd.keys())
+        model.load_state_dict(export_case.fused_values(keys, [tuple(sd[k].shape) for k in keys],
+                                                       [str(sd[k].numpy().dtype) for k in keys], seed, export_case.ties(sd)),
+                              strict=True)
+        torch.manual_seed(1)
+        x = torch.randn(1, 1, size, size)
+        save(f'export_{case}', **export_case.record(torch.jit.script(model), x, seed))
+
+
+if __name__ == '__main__' and 'exports' in sys.argv[1:]:
+    gen_exports()

@@ -27,7 +27,7 @@ def _bench(args, env=None, timeout=900):
 
 
 def test_one_gpu_line_carries_roofline_cpu_baseline_and_parity():
-    j = _bench(['--steps', '2', '--warmup', '1', '--batch', '4', '--size', '512', '--cpu-tiles', '1', '--stack3d', '0',
+    j = _bench(['--full', '--steps', '2', '--warmup', '1', '--batch', '4', '--size', '512', '--cpu-tiles', '1', '--stack3d', '0',
                 '--engine2d', '0', '--latency', '0', '--fp32-mode', '2'])
     assert j['n_gpus'] == 1 and j['unit'] == 'tiles/s' and j['value'] > 0 and j['dtype'] == 'f16'
     f = j['fp32_mode']       # the rate of the tolerance-compliant mode rides on the same line
@@ -47,7 +47,7 @@ def test_one_gpu_line_carries_roofline_cpu_baseline_and_parity():
 
 
 def test_two_ranks_sharing_the_gpu_emit_the_stack3d_block():
-    j = _bench(['--gpus', '2', '--steps', '1', '--warmup', '1', '--batch', '2', '--size', '256', '--slab-size', '512',
+    j = _bench(['--full', '--gpus', '2', '--steps', '1', '--warmup', '1', '--batch', '2', '--size', '256', '--slab-size', '512',
                 '--slab-depth', '6', '--engine2d', '0', '--latency', '0', '--no-cpu-baseline'],
                env={'EMP_BENCH_SHARE_GPU': '1'})
     assert j['n_gpus'] == 2 and j['config']['ranks_sharing_one_gpu'] == 2
@@ -61,7 +61,7 @@ def test_two_ranks_sharing_the_gpu_emit_the_stack3d_block():
 def test_a_stuck_slab_job_costs_the_block_not_the_headline():
     """the z-slab job runs as a child job with a bound (bench.slab_job_child): one that does not finish is killed and
     leaves an `error` entry; the headline line of the N ranks is printed all the same"""
-    j = _bench(['--gpus', '2', '--steps', '1', '--warmup', '1', '--batch', '2', '--size', '256', '--slab-size', '512',
+    j = _bench(['--full', '--gpus', '2', '--steps', '1', '--warmup', '1', '--batch', '2', '--size', '256', '--slab-size', '512',
                 '--slab-depth', '6', '--engine2d', '0', '--latency', '0', '--no-cpu-baseline', '--slab-timeout', '1.5'],      # (a warm box finishes the job in under 4 s)
                env={'EMP_BENCH_SHARE_GPU': '1'})
     assert j['n_gpus'] == 2 and j['value'] > 0
@@ -83,7 +83,7 @@ def test_profile_tools_read_the_step_count_off_the_trace(tmp_path):
         e.pop(k, None)
     d = str(tmp_path / 'ks')
     r = subprocess.run(['rocprofv3', '--kernel-trace', '--output-format', 'csv', '-d', d, '-o', 'ks', '--', sys.executable,
-                        os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--stack3d', '0',
+                        os.path.join(ROOT, 'bench.py'), '--full', '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--stack3d', '0',
                         '--engine2d', '0', '--latency', '0', '--fine-boundaries', '0', '--fp32-mode', '0'],
                        capture_output=True, text=True, env=e, cwd=str(tmp_path), timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -133,3 +133,21 @@ def test_dominant_kernel_asks_l2_for_whole_lines(tmp_path):
     print(f'bytes per L2 read request: whole-line kernel + packed weights {whole:.1f}, rounds 2-4 kernel {half:.1f}')
     assert whole >= 120.0, whole
     assert half <= 72.0, half
+
+
+def test_plain_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """without --full the line carries the headline and its roofline block only; --dump-outputs writes the label maps of
+    the last timed step, and two runs with the same arguments write the same arrays"""
+    import numpy as np
+    args = ['--steps', '2', '--warmup', '1', '--batch', '4', '--size', '256']
+    j = _bench(args + ['--dump-outputs', str(tmp_path / 'a')])
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert k in j, k
+    assert j['unit'] == 'tiles/s' and j['value'] > 0 and j['ms_per_step'] > 0 and j['full'] is False
+    assert j['forward_steps_bench_loop'] == j['forward_calls_total'] == 1 + 2
+    for k in ('cpu_baseline', 'parity', 'fp32_mode', 'fp16x3_mode', 'latency_ms_batch1', 'ms_per_step_uninstrumented'):
+        assert k not in j, k
+    a = np.load(tmp_path / 'a' / 'panoptic_labels.npy')
+    assert a.shape == (4, 256, 256) and a.dtype == np.float32 and (a > 0).any()
+    _bench(args + ['--dump-outputs', str(tmp_path / 'b')])
+    assert np.array_equal(a, np.load(tmp_path / 'b' / 'panoptic_labels.npy'))

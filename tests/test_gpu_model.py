@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 import torch
 
+import golden_files
+
 pytestmark = pytest.mark.gpu
 
 
@@ -156,7 +158,7 @@ def test_bifpn_heads_match_reference_golden(golden_dir, tag, ncls, case):
     """PanopticBiFPNPR (MitoNet_v1_mini-class; 4-class = BASELINE configs[4]) on the HIP engine."""
     from empanada_napari_amd import weights
     from empanada_napari_amd.engines import HipPanopticDeepLab
-    g = np.load(os.path.join(golden_dir, 'bifpn_forward.npz'))
+    g = golden_files.load('bifpn_forward', golden_dir)
     cfg = dict(weights.MITONET_MINI_CFG, num_classes=ncls)
     model = HipPanopticDeepLab(weights.seeded_state_dict(cfg, seed=3), cfg, precision='fp16')
     x = _norm(g[f'{tag}{case}_image']).cuda()

@@ -288,7 +288,7 @@ def test_end_to_end_label_flips_vs_fp32_pipeline(case):
 @pytest.mark.parametrize('ncls', [1, 4])
 def test_bifpn_512_tile_vs_fp32_forward(ncls):
     """PanopticBiFPNPR (MitoNet_v1_mini class; 4 outputs = BASELINE configs[4]) on one 512^2 tile against the fp32 oracle
-    forward (pinned by tests/golden/bifpn_forward.npz): the same statement as (B) for the second network family -- rms inside
+    forward (pinned by tests/golden/bifpn_forward.*.npz): the same statement as (B) for the second network family -- rms inside
     1e-3 of the head's scale ASSERTED (round 4), max bounded.  Its encoder and heads are the kernels that (A) checks layer by layer."""
     from empanada_napari_amd import synth, weights
     from empanada_napari_amd.engines import HipPanopticDeepLab

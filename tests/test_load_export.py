@@ -4,8 +4,10 @@ NO architecture hint (the reference's YAML descriptors carry none, empanada_napa
 ``inference.load_model_spec`` rebuilds the right layer spec from the export itself; a URL resolves to the torch-hub
 cache file the reference's loader would have written (empanada_napari/utils.py:80-106).
 
-Runs only where the reference is importable (this build container): a scripted reference model carries the reference's
-code and therefore cannot travel as a fixture."""
+A scripted reference model carries the reference's code and therefore cannot travel as a fixture: each export is rebuilt
+from ``tests/golden/export_<case>.npz`` (tests/export_case.py) -- the fused model's parameter names, shapes and dtypes, the
+scalar attributes of its scripted submodules, seeded parameter values, and the scripted reference model's outputs on a
+stored input with exactly those values (oracle/gen_golden.py ``exports``)."""
 import os
 import sys
 
@@ -13,23 +15,14 @@ import numpy as np
 import pytest
 import torch
 
-REF = '/root/reference'
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'empanada')), reason='reference tree not present')
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import export_case  # noqa: E402
 
 
-def _export(arch, tmp_path, **model_kwargs):
-    sys.path.insert(0, REF)
-    try:
-        from empanada.models import quantization as quant_models
-    finally:
-        sys.path.remove(REF)
-    torch.manual_seed(0)
-    model = quant_models.__dict__['Quantizable' + arch](**model_kwargs, quantize=False)
-    model.eval()
-    model.fuse_model()
-    path = str(tmp_path / f'{arch}.pth')
-    torch.jit.save(torch.jit.script(model), path)
-    return model, path
+def _export(case, tmp_path):
+    """-> (path of the rebuilt TorchScript export, its input, the scripted reference model's outputs on it)"""
+    values, attrs, x, want = export_case.load(case)
+    return export_case.build_export(values, attrs, str(tmp_path / f'{case}.pth')), x, want
 
 
 PDL_KW = dict(encoder='resnet50', num_classes=1, stage4_stride=16, decoder_channels=256, low_level_stages=[1],
@@ -48,7 +41,7 @@ def test_panoptic_deeplab_export_is_loaded_without_arch(tmp_path, variant):
         kw.update(num_classes=3, decoder_channels=128, aspp_channels=192, low_level_stages=[2, 1],
                   low_level_channels_project=[64, 32], atrous_rates=[3, 6, 9], stage4_stride=32, num_fc=2,
                   subdivision_num_points=4096)
-    model, path = _export('PanopticDeepLabPR', tmp_path, **kw)
+    path, x, want = _export(f'pdl_{variant}', tmp_path)
     sd, cfg = inference.load_model_spec({'model': path})
     assert cfg['arch'] == 'PanopticDeepLabPR' and cfg['encoder'] == 'resnet50'
     for k in ('num_classes', 'decoder_channels', 'low_level_stages', 'low_level_channels_project', 'atrous_rates',
@@ -61,9 +54,6 @@ def test_panoptic_deeplab_export_is_loaded_without_arch(tmp_path, variant):
     assert len(P) == len(weights.model_spec(cfg))
     # and the folded parameters reproduce the export: oracle forward (pinned by tests/golden) == the scripted model
     from oracle import pdl_model
-    x = torch.randn(1, 1, 64, 64)
-    with torch.no_grad():
-        want = torch.jit.load(path)(x, 2, False)
     got = pdl_model.model_forward(P, x, cfg, 2, False)
     for k in ('sem_logits', 'ctr_hmp', 'offsets'):
         assert torch.allclose(got[k], want[k], rtol=1e-4, atol=1e-5), k
@@ -74,7 +64,7 @@ def test_panoptic_bifpn_export_is_loaded_without_arch(tmp_path):
     kw = dict(encoder='resnet50', num_classes=4, fpn_dim=128, fpn_layers=2, ins_decoder=True, depthwise=True, num_fc=3,
               train_num_points=1024, oversample_ratio=3, importance_sample_ratio=0.75, subdivision_steps=2,
               subdivision_num_points=2048)
-    model, path = _export('PanopticBiFPNPR', tmp_path, **kw)
+    path, x, want = _export('bifpn', tmp_path)
     sd, cfg = inference.load_model_spec({'model': path})
     assert cfg['arch'] == 'PanopticBiFPNPR'
     for k in ('num_classes', 'fpn_dim', 'fpn_layers', 'ins_decoder', 'num_fc', 'subdivision_num_points'):
@@ -82,9 +72,6 @@ def test_panoptic_bifpn_export_is_loaded_without_arch(tmp_path):
     P = weights.fold_state_dict(sd, cfg)
     assert len(P) == len(weights.model_spec(cfg))
     from oracle import pdl_model
-    x = torch.randn(1, 1, 128, 128)
-    with torch.no_grad():
-        want = torch.jit.load(path)(x, 2, False)
     got = pdl_model.model_forward(P, x, cfg, 2, False)
     for k in ('sem_logits', 'ctr_hmp', 'offsets'):
         assert torch.allclose(got[k], want[k], rtol=1e-4, atol=1e-5), k
@@ -123,11 +110,9 @@ def test_regnet_export_is_loaded_without_arch(tmp_path, arch, encoder):
         kw = dict(encoder=encoder, num_classes=3, fpn_dim=128, fpn_layers=2, ins_decoder=True, depthwise=True, num_fc=3,
                   train_num_points=1024, oversample_ratio=3, importance_sample_ratio=0.75, subdivision_steps=2,
                   subdivision_num_points=2048)
-        size = 128
     else:
         kw = dict(PDL_KW, encoder=encoder)
-        size = 64
-    model, path = _export(arch, tmp_path, **kw)
+    path, x, want = _export(('regnet_bifpn_' if arch == 'PanopticBiFPNPR' else 'regnet_pdl_') + encoder[len('regnet')], tmp_path)
     sd, cfg = inference.load_model_spec({'model': path})
     assert cfg['arch'] == arch and cfg['encoder'] == encoder
     assert cfg['regnet'] == weights.regnet_layout(*weights.REGNET_PARAMS[encoder])
@@ -135,10 +120,6 @@ def test_regnet_export_is_loaded_without_arch(tmp_path, arch, encoder):
     P = weights.fold_state_dict(sd, cfg)
     assert len(P) == len(weights.model_spec(cfg))
     from oracle import pdl_model
-    torch.manual_seed(1)
-    x = torch.randn(1, 1, size, size)
-    with torch.no_grad():
-        want = torch.jit.load(path)(x, 2, False)
     got = pdl_model.model_forward(P, x, cfg, 2, False)
     for k in ('sem_logits', 'ctr_hmp', 'offsets'):
         assert torch.allclose(got[k], want[k], rtol=1e-4, atol=1e-5), k

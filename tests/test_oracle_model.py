@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import golden_files
 from empanada_napari_amd import weights
 from empanada_napari_amd.preprocess import normalize
 from oracle import pdl_model
@@ -72,7 +73,7 @@ def test_fold_accepts_fused_layout(golden_dir, folded):
 @pytest.mark.parametrize('case', ['a', 'b'])
 def test_bifpn_forward_matches_reference(golden_dir, tag, ncls, case):
     """PanopticBiFPNPR (MitoNet_v1_mini-class, and the 4-class variant of BASELINE configs[4])."""
-    g = np.load(os.path.join(golden_dir, 'bifpn_forward.npz'))
+    g = golden_files.load('bifpn_forward', golden_dir)
     cfg = dict(weights.MITONET_MINI_CFG, num_classes=ncls)
     P = weights.fold_state_dict(weights.seeded_state_dict(cfg, seed=3), cfg)
     x = torch.from_numpy(normalize(g[f'{tag}{case}_image'], 0.57571, 0.12765))[:, None]

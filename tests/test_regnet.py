@@ -1,15 +1,14 @@
 """RegNet encoders (reference: empanada/models/encoders/regnet.py:38-316, the two the reference can
 export: quantization/encoders/__init__.py) -- host side: the layout derived from the generating parameters, the layer
 spec in the reference's key layout, the architecture read back from an export's keys + shapes, and the oracle's restated
-forward against outputs of the imported reference (tests/golden/regnet_forward.npz, oracle/gen_golden.py::gen_regnet):
+forward against outputs of the imported reference (tests/golden/regnet_forward.*.npz, oracle/gen_golden.py::gen_regnet):
 PanopticBiFPNPR on regnety_6p4gf (grouped 3x3 + the reference's per-pixel squeeze-excite gate) and PanopticDeepLabPR on
 regnetx_6p4gf (whose stage 4 stays at stride 2 whatever ``stage4_stride`` says)."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
+import golden_files
 from empanada_napari_amd import weights
 from empanada_napari_amd.preprocess import normalize
 from oracle import pdl_model
@@ -43,7 +42,7 @@ def test_layouts_of_the_exportable_regnets():
 def test_architecture_is_read_back_from_the_exports_keys(golden_dir, tag):
     """an export carries no architecture (empanada_napari/configs/*.yaml): widths, depths, group width and the gate come
     from the fused state dict's shapes -- here the reference's own fused key layout with the shapes behind it"""
-    g = np.load(os.path.join(golden_dir, 'regnet_forward.npz'))
+    g = golden_files.load('regnet_forward', golden_dir)
     sd = {str(k): np.empty(tuple(int(d) for d in str(s).split(',')) if str(s) else (), np.float32)
           for k, s in zip(g[f'{tag}_fused_keys'], g[f'{tag}_fused_shapes'])}
     cfg = weights.infer_cfg(sd)
@@ -65,7 +64,7 @@ def test_architecture_is_read_back_from_the_exports_keys(golden_dir, tag):
 
 @pytest.mark.parametrize('tag,case', [('y', 'a'), ('y', 'b'), ('x', 'a'), ('x', 'b')])
 def test_oracle_forward_matches_the_reference(golden_dir, tag, case):
-    g = np.load(os.path.join(golden_dir, 'regnet_forward.npz'))
+    g = golden_files.load('regnet_forward', golden_dir)
     cfg, P = regnet_model(tag)
     x = torch.from_numpy(normalize(g[f'{tag}{case}_image'], 0.57571, 0.12765))[:, None]
     out = pdl_model.model_forward(P, x, cfg, int(g[f'{tag}{case}_render_steps']), bool(g[f'{tag}{case}_interpolate_ins']))
@@ -80,7 +79,7 @@ def test_oracle_forward_matches_the_reference(golden_dir, tag, case):
 def test_oracle_pyramid_matches_the_reference(golden_dir, tag):
     """the encoder alone: stem + four stages, sampled -- pins the grouped convolutions, the gate and the strides level by
     level (a decoder could hide a wrong level behind its own normalisation)"""
-    g = np.load(os.path.join(golden_dir, 'regnet_forward.npz'))
+    g = golden_files.load('regnet_forward', golden_dir)
     cfg, P = regnet_model(tag)
     x = torch.from_numpy(normalize(g[f'{tag}a_image'], 0.57571, 0.12765))[:, None]
     pyr = pdl_model.regnet_forward(P, x, cfg['regnet'])

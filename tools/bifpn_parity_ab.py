@@ -15,6 +15,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import golden_files  # noqa: E402
 import __graft_entry__ as ge  # noqa: E402
 
 ge.load_package()
@@ -37,7 +39,7 @@ def main():
     ap.add_argument('--out', default=os.path.join(ROOT, 'gpurun_out', 'bifpn_parity_ab.json'))
     a = ap.parse_args()
     torch.set_num_threads(min(os.cpu_count() or 1, 32))
-    g = np.load(os.path.join(ROOT, 'tests', 'golden', 'bifpn_forward.npz'))
+    g = golden_files.load('bifpn_forward')
     res = {}
     refs = {}
     for ncls in (1, 4):

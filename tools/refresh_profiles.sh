@@ -23,7 +23,7 @@ d=json.load(open('$OUT/hbm_traffic.json')); d['commit']='${EMP_COMMIT:-unknown}'
 json.dump(d, open('$OUT/hbm_traffic.json','w'), indent=1)
 PY
 cp $OUT/hbm_traffic.json $REPO/profiles/${EMP_ROUND:-r05}_hbm_traffic.json
-python3 $REPO/bench.py --steps 10 --warmup 3 2>/dev/null | tail -1 > $OUT/bench.json
+python3 $REPO/bench.py --full --steps 10 --warmup 3 2>/dev/null | tail -1 > $OUT/bench.json
 ls -la $OUT
 tail -3 $OUT/hbm_traffic.txt
 python3 -c "
