@@ -143,6 +143,13 @@ PROTOTYPES = {
     'emp_gather_segments_i64': (c_int, [vp, vp, vp, vp, vp, vp, c_i64, vp, vp]),
     'emp_panoptic_merge': (c_int, [vp, vp, c_int, c_int, c_int, c_int, c_f32, C.POINTER(c_i32), c_int, c_i64, c_i64,
                                    c_i64, c_int, vp, vp, vp]),
+    'emp_label_overlap_work_bytes': (sz, [c_i64]),
+    'emp_label_overlap_reset': (c_int, [vp, c_i64, vp]),
+    'emp_label_overlap_accumulate': (c_int, [vp, c_int, vp, c_int, c_i64, vp, c_i64, vp, C.POINTER(c_int)]),
+    'emp_label_overlap_grow': (c_int, [vp, c_i64, vp, c_i64, vp, C.POINTER(c_int)]),
+    'emp_label_overlap_finalize': (c_int, [vp, c_i64, vp, vp, c_i64, C.POINTER(c_i64), vp]),
+    'emp_overlap_match': (c_int, [c_i64, vp, vp, vp, c_int, vp, vp, C.POINTER(c_i64), vp, vp, C.POINTER(c_i64), vp, vp, vp, vp,
+                                  C.POINTER(c_i64)]),
 }
 
 

@@ -623,6 +623,51 @@ EMP_API int emp_sm_slice_object_info(const emp_stack_matcher_t* h, int64_t idx, 
                              int64_t* n_runs);
 EMP_API int emp_sm_slice_object_runs(const emp_stack_matcher_t* h, int64_t idx, int64_t k, int64_t* starts, int64_t* runs);
 
+/* ------------------------------------------------------------------------
+ * 6. Scoring of label volumes (csrc/overlap.hip): the sparse contingency table
+ *    of two label arrays on the device, and the matching derived from it.
+ *    replaces the dense np.histogram2d over label VALUES + np.bincount of the
+ *    plugin's model-performance tool (empanada_napari/_accuracy_metrics.py:
+ *    121-131) and the per-pair rle_iou loop of the offline evaluator
+ *    (empanada/inference/matcher.py:194-204 as called from
+ *    empanada/evaluation/evaluator.py:88-89).
+ *
+ *    The table is a device buffer of emp_label_overlap_work_bytes(capacity)
+ *    bytes (capacity: slots, a power of two in [64, 2^32]) that the caller
+ *    resets once and then feeds slab by slab; it survives between calls.
+ *    Labels must lie in [0, 2^32).  The counts are exact uint64 integers.
+ * ---------------------------------------------------------------------- */
+/* 0 if the capacity is not a power of two in [64, 2^32] */
+EMP_API size_t emp_label_overlap_work_bytes(int64_t capacity);
+EMP_API int emp_label_overlap_reset(void* d_table, int64_t capacity, void* stream);
+/* Adds the n voxel pairs (d_a[i], d_b[i]) to the table: conf_matrix of _accuracy_metrics.py:125 restricted to its non-zero
+ * cells, accumulated.  a_bytes / b_bytes: element size 1, 2, 4 or 8, NEGATIVE for a signed type (int32: -4), as
+ * emp_ccl_range takes in_bytes.  A value outside [0, 2^32) -- negative, or 2^32 and above -- is an error (EMP_ERR_INVALID,
+ * the table's content is then undefined), never wrapped.  Synchronises the stream.  *h_overflow = 1: the table is too small for
+ * this slab; the call has removed what it had added (the table is as before): move the table to a larger one with
+ * emp_label_overlap_grow and call again. */
+EMP_API int emp_label_overlap_accumulate(const void* d_a, int a_bytes, const void* d_b, int b_bytes, int64_t n, void* d_table,
+                                 int64_t capacity, void* stream, int* h_overflow);
+/* Re-inserts the cells of d_from into the reset, larger table d_to.  Synchronises.  *h_overflow = 1: d_to is too small too. */
+EMP_API int emp_label_overlap_grow(const void* d_from, int64_t from_capacity, void* d_to, int64_t to_capacity, void* stream,
+                                 int* h_overflow);
+/* The occupied cells as d_keys[i] = a << 32 | b and d_counts[i], in no particular order (sort the keys: the result is then
+ * np.unique(a << 32 | b, return_counts=True)); *h_num = their number, of which min(*h_num, max_out) are written.
+ * Synchronises.  The table stays valid and can be fed further. */
+EMP_API int emp_label_overlap_finalize(void* d_table, int64_t capacity, uint64_t* d_keys, uint64_t* d_counts, int64_t max_out,
+                                 int64_t* h_num, void* stream);
+/* HOST: from the k cells (h_a[i], h_b[i]) -> h_count[i], sorted by (a, b): the non-zero labels of each side in ascending order
+ * with their areas (gt_ids / gt_area / pred_ids / pred_area of _accuracy_metrics.py:96-99,130-131; target_labels /
+ * match_labels of matcher.py:179-183), IoU = inter / (area_a + area_b - inter) in float64 (_accuracy_metrics.py:134-136,
+ * array_utils.py:427-433) and the assignment linear_sum_assignment(-iou) == linear_sum_assignment(iou, maximize=True)
+ * (_accuracy_metrics.py:145-146, matcher.py:213) through emp_lsa_maximize_sparse.  index_space 0: one row / column per label
+ * that occurs (the evaluator); 1: one per integer 1..max label, the absent ones empty (the tool's histogram bins), labels up
+ * to 2^26.  Out: the assigned pairs that overlap, rows ascending, as indices into the label lists, with their IoU and
+ * intersection; pairs without overlap (IoU 0) are not returned.  Every output array holds k entries. */
+EMP_API int emp_overlap_match(int64_t k, const int64_t* h_a, const int64_t* h_b, const int64_t* h_count, int index_space,
+                      int64_t* h_a_labels, int64_t* h_a_areas, int64_t* n_a, int64_t* h_b_labels, int64_t* h_b_areas, int64_t* n_b,
+                      int64_t* h_rows, int64_t* h_cols, double* h_iou, int64_t* h_inter, int64_t* n_match);
+
 #ifdef __cplusplus
 }
 #endif
