@@ -11,5 +11,7 @@ Sub-modules
   build     -- hipcc build recipe for csrc/ (gfx950 only)
   engines   -- PanopticDeepLabRenderEngine[3d] mirror (empanada/inference/engines.py)
   inference -- Engine2d / Engine3d mirror (empanada_napari/inference.py)
+  metrics   -- scoring of label volumes on the device (empanada_napari/_accuracy_metrics.py, empanada/evaluation)
+  labels    -- label clean-up on the device: per-label table, filters, delete / merge (the plugin's label widgets)
 """
 __version__ = '0.1.0'

@@ -150,6 +150,13 @@ PROTOTYPES = {
     'emp_label_overlap_finalize': (c_int, [vp, c_i64, vp, vp, c_i64, C.POINTER(c_i64), vp]),
     'emp_overlap_match': (c_int, [c_i64, vp, vp, vp, c_int, vp, vp, C.POINTER(c_i64), vp, vp, C.POINTER(c_i64), vp, vp, vp, vp,
                                   C.POINTER(c_i64)]),
+    'emp_label_table_work_bytes': (sz, [c_i64]),
+    'emp_label_table_reset': (c_int, [vp, c_i64, vp]),
+    'emp_label_table_accumulate': (c_int, [vp, c_int, c_i64, c_int, c_int, c_int, c_int, vp, c_i64, vp, C.POINTER(c_int)]),
+    'emp_label_table_grow': (c_int, [vp, c_i64, vp, c_i64, vp, C.POINTER(c_int)]),
+    'emp_label_table_finalize': (c_int, [vp, c_i64, vp, vp, vp, c_i64, C.POINTER(c_i64), vp]),
+    'emp_label_map_build': (c_int, [vp, vp, c_i64, vp, vp, c_i64, vp]),
+    'emp_label_apply_map': (c_int, [vp, c_int, vp, c_int, vp, c_i64, c_int, c_int, c_int, c_int, vp, vp, c_i64, vp]),
 }
 
 

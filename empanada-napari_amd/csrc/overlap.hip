@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "common.h"
+#include "label_stream.h"
 
 namespace emp {
 namespace {
@@ -64,15 +65,6 @@ inline OvTable ov_table(void* d_table, int64_t capacity) {
   t.counts = t.keys + capacity;
   t.mask = (uint64_t)capacity - 1;
   return t;
-}
-
-__device__ __forceinline__ uint64_t ov_hash(uint64_t k) {      // the 64-bit finaliser of MurmurHash3 (public domain)
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdull;
-  k ^= k >> 33;
-  k *= 0xc4ceb9fe1a85ec53ull;
-  k ^= k >> 33;
-  return k;
 }
 
 __device__ __forceinline__ void ov_global_add(const OvTable& t, uint64_t key, uint64_t w) {
@@ -113,36 +105,6 @@ __device__ __forceinline__ void ov_lds_add(uint64_t* lkeys, uint64_t* lcnt, cons
     }
   }
   ov_global_add(t, key, negate ? 0ull - w : w);
-}
-
-template <int BYTES> struct OvVec;
-template <> struct OvVec<16> { typedef uint4 type; };
-template <> struct OvVec<8> { typedef uint2 type; };
-template <> struct OvVec<4> { typedef uint32_t type; };
-template <> struct OvVec<2> { typedef uint16_t type; };
-template <int S> struct OvElem;
-template <> struct OvElem<1> { typedef uint8_t type; };
-template <> struct OvElem<2> { typedef uint16_t type; };
-template <> struct OvElem<4> { typedef uint32_t type; };
-template <> struct OvElem<8> { typedef uint64_t type; };
-
-// E elements of S bytes from element i0 on as raw unsigned values; nv of them exist (the rest read as 0).  One vector
-// load where the base is aligned for it and the lane is full, element loads otherwise (the tail, a misaligned view).
-template <int S, int E>
-__device__ __forceinline__ void ov_load(const void* base, int64_t i0, int nv, int vec_ok, uint64_t* v) {
-  typedef typename OvElem<S>::type T;
-  typedef typename OvVec<S * E>::type V;
-  const T* p = (const T*)base + i0;
-  if (vec_ok && nv == E) {
-    const V vec = *(const V*)p;
-    T e[E];
-    __builtin_memcpy(e, &vec, sizeof(V));
-#pragma unroll
-    for (int j = 0; j < E; ++j) v[j] = (uint64_t)e[j];
-  } else {
-#pragma unroll
-    for (int j = 0; j < E; ++j) v[j] = j < nv ? (uint64_t)p[j] : 0ull;
-  }
 }
 
 // values outside [0, 2^32): an 8-byte value with a high word (a negative int64 included), a signed narrower value with its sign bit

@@ -1,0 +1,574 @@
+"""Clean-up of label volumes on the device: the plugin's label tools without the trip to the host.
+
+Two device primitives (csrc/labels.hip) carry everything:
+
+* ``label_table``: for every label that occurs its voxel count and its bounding box, in one pass -- what
+  ``regionprops_table(img, properties=('label', 'area'))`` (empanada_napari/_filter_small_labels.py:16), ``regionprops(...).bbox``
+  (_merge_split_widget.py:653-655) and ``np.unique`` (_label_counter_widget.py:243, _merge_split_widget.py:730) give;
+* the edit: one pass that rewrites a volume through a ``from -> to`` map, instead of one ``labels[labels == l] = v`` pass per label
+  (_filter_small_labels.py:10-12, _merge_split_widget.py:249-250, :385-387).
+
+On top of them, as pure numpy on a ``LabelTable`` (no device needed): ``small_labels``, ``boundary_labels``, ``count_labels``,
+``class_label_lists``, ``next_available_labels``, ``next_available_label``, ``label_bbox``; and the edits ``delete_labels``,
+``merge_labels``, ``filter_out_small_label_areas``, ``remove_boundary_labels``.
+
+Inputs are those of ``metrics.label_overlap``: device tensors (read in place), numpy arrays and chunked stores
+(``zstore.DirArray``, zarr arrays) streamed in leading-axis slabs through pinned staging buffers.  An edit returns the kind of
+object it was given: a device tensor for a device tensor, a new numpy array for a numpy array (the caller's array is only written
+with ``inplace=True``), and for a store the store given as ``out=``, written slab by slab.
+
+skimage is not available where this package is built and tested: what ``regionprops_table`` and ``clear_border`` compute is
+restated from their documented behaviour (area = voxel count; bbox = minimum and exclusive maximum per axis; clear_border =
+every connected component, full connectivity and equal value, that touches a face of the array is cleared) and is not pinned
+against them.  ``count_labels`` is pure numpy in the reference and is pinned (tests/golden/labels.npz).
+
+The one deliberate difference: on an image without labels the reference's ``filter_out_small_label_areas`` dies with an
+``IndexError`` (``.iloc[0]`` of an empty frame, _filter_small_labels.py:20); here that case returns the image unchanged and 0.
+
+There is no numpy fallback: without the HIP library or a device the device entries raise like every other entry of the package.
+"""
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _abi
+from .metrics import SLAB_BYTES, _DeviceSource, _HostSource, _ebytes, _hp, _source, initial_capacity
+
+__all__ = ['LabelTable', 'label_table', 'table_from_arrays', 'small_labels', 'boundary_labels', 'count_labels', 'class_label_lists',
+           'next_available_labels', 'next_available_label', 'label_bbox', 'delete_labels', 'merge_labels',
+           'filter_out_small_label_areas', 'remove_boundary_labels']
+
+CCL_MAX_VOXELS = 1 << 30      # emp_ccl_range: D * H * W < 2^30
+CCL_MAX_LABEL = (1 << 31) - 2      # ... and labels below 2^31 - 1
+
+
+@dataclass
+class LabelTable:
+    """The labels of an array with their sizes and boxes.
+
+    Whole mode: ``labels`` ascending (``np.unique``, background 0 included where it occurs), ``areas`` their voxel counts,
+    ``boxes`` (k, 2 * ndim) ``(min_0, .., min_n, max_0, .., max_n)`` with exclusive upper ends, as ``regionprops.bbox``;
+    ``slices`` is None.  Per-slice mode (a 3-D array as a stack of images): one row per (slice, label) that occurs, sorted by
+    slice, then label; ``slices`` holds the leading-axis index and ``boxes`` (k, 4) the box within the image.  ``shape``: the
+    array's shape; ``doublings``: how often the device table had to grow."""
+    labels: np.ndarray
+    areas: np.ndarray
+    boxes: np.ndarray
+    slices: object = None
+    shape: tuple = ()
+    doublings: int = 0
+
+    @property
+    def per_slice(self):
+        return self.slices is not None
+
+
+def table_from_arrays(labels, areas, boxes, shape, slices=None, doublings=0):
+    """LabelTable from host arrays (rows in any order, each key once)."""
+    labels = np.asarray(labels, dtype=np.int64).reshape(-1)
+    areas = np.asarray(areas, dtype=np.int64).reshape(-1)
+    shape = tuple(int(s) for s in shape)
+    nd = 2 if slices is not None else len(shape)
+    boxes = np.asarray(boxes, dtype=np.int64).reshape(-1, 2 * nd)
+    if not (len(labels) == len(areas) == len(boxes)):
+        raise ValueError('table_from_arrays: labels, areas and boxes differ in length')
+    if slices is not None:
+        if len(shape) != 3:
+            raise ValueError('table_from_arrays: a per-slice table belongs to a 3-D array')
+        slices = np.asarray(slices, dtype=np.int64).reshape(-1)
+        order = np.lexsort((labels, slices))
+        slices = slices[order]
+    else:
+        order = np.argsort(labels, kind='stable')
+    return LabelTable(labels[order], areas[order], boxes[order], slices, shape, int(doublings))
+
+
+# ----------------------------------------------------------------------------
+# device: the table
+# ----------------------------------------------------------------------------
+def _need_device():
+    if not torch.cuda.is_available():
+        raise RuntimeError('empanada_napari_amd needs a HIP device (MI355X); there is no CPU fallback')
+    _abi.load()
+
+
+def _pick_device(device, *arrays):
+    if device is None:
+        dev_in = [x.device for x in arrays if isinstance(x, torch.Tensor) and x.is_cuda]
+        device = dev_in[0] if dev_in else torch.device('cuda', torch.cuda.current_device())
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    return device
+
+
+def _geometry(shape, per_slice, what):
+    """(rows, H, W) as the kernels see a slab of `rows` leading-axis entries.  A 2-D image (R, W) is R slabs of one row each:
+    the kernels' z is the image's y, so that a host image is streamed by rows like a volume by slices."""
+    if len(shape) == 3:
+        return shape[0], shape[1], shape[2]
+    if len(shape) == 2:
+        if per_slice:
+            raise ValueError(f'{what}: per_slice needs a 3-D array (a stack of images)')
+        return shape[0], 1, shape[1]
+    raise ValueError(f'{what}: 2-D or 3-D label arrays, got shape {shape}')
+
+
+class _Table:
+    def __init__(self, capacity, device):
+        self.lib = _abi.load()
+        self.device = device
+        self.doublings = 0
+        self.capacity = int(capacity)
+        self.buf = self._new(self.capacity)
+
+    def _new(self, capacity):
+        nbytes = self.lib.emp_label_table_work_bytes(capacity)
+        if nbytes == 0:
+            raise ValueError(f'label_table: capacity {capacity} is not a power of two in [64, 2^32]')
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        _abi.check(self.lib.emp_label_table_reset(_abi.ptr(buf), capacity, _abi.stream_ptr(self.device)), 'emp_label_table_reset')
+        return buf
+
+    def _grow(self):
+        cap = self.capacity
+        while True:
+            cap *= 2
+            new = self._new(cap)
+            ov = C.c_int(0)
+            _abi.check(self.lib.emp_label_table_grow(_abi.ptr(self.buf), self.capacity, _abi.ptr(new), cap, _abi.stream_ptr(self.device),
+                                                     C.byref(ov)), 'emp_label_table_grow')
+            self.doublings += 1
+            if not ov.value:
+                break
+        self.buf, self.capacity = new, cap
+
+    def add(self, address, ebytes, z0, depth, H, W, per_slice):
+        while True:
+            ov = C.c_int(0)
+            _abi.check(self.lib.emp_label_table_accumulate(C.c_void_p(address), ebytes, z0, depth, H, W, int(per_slice), _abi.ptr(self.buf),
+                                                           self.capacity, _abi.stream_ptr(self.device), C.byref(ov)),
+                       'emp_label_table_accumulate')
+            if not ov.value:
+                return
+            self._grow()      # the failed call has taken its counts out again: count the slab once more
+
+    def rows(self):
+        """(keys, counts, boxes (k, 6)) as numpy arrays, sorted by key"""
+        num = C.c_int64(0)
+        stream = _abi.stream_ptr(self.device)
+        _abi.check(self.lib.emp_label_table_finalize(_abi.ptr(self.buf), self.capacity, None, None, None, 0, C.byref(num), stream),
+                   'emp_label_table_finalize')
+        k = num.value
+        keys = torch.empty(max(k, 1), dtype=torch.int64, device=self.device)
+        cnt = torch.empty(max(k, 1), dtype=torch.int64, device=self.device)
+        box = torch.empty((max(k, 1), 6), dtype=torch.int32, device=self.device)
+        _abi.check(self.lib.emp_label_table_finalize(_abi.ptr(self.buf), self.capacity, _abi.ptr(keys), _abi.ptr(cnt), _abi.ptr(box), k,
+                                                     C.byref(num), stream), 'emp_label_table_finalize')
+        skeys, order = torch.sort(keys[:k])      # keys lie below 2^63: the signed order is theirs
+        return skeys.cpu().numpy(), cnt[:k][order].cpu().numpy(), box[:k][order].cpu().numpy().astype(np.int64)
+
+
+def _slabs(src, slab, rows):
+    host = isinstance(src, _HostSource)
+    if slab is None:
+        slab = rows if not host else max(1, SLAB_BYTES // max(1, src.row_bytes))
+    slab = max(1, min(int(slab), max(rows, 1)))
+    return slab, [(z, min(rows, z + slab)) for z in range(0, rows, slab)]
+
+
+def _table_of_source(src, shape, per_slice, device, slab, capacity):
+    rows, H, W = _geometry(shape, per_slice, 'label_table')
+    table = _Table(capacity or initial_capacity(rows * H * W), device)
+    slab, bounds = _slabs(src, slab, rows)
+    stream = torch.cuda.current_stream(device)
+    host = isinstance(src, _HostSource)
+    if host:
+        src.reserve(slab, torch.cuda.Stream(device=device))
+        if bounds:
+            src.stage(*bounds[0], 0)
+    for k, (z0, z1) in enumerate(bounds):
+        if host and k + 1 < len(bounds):
+            src.stage(*bounds[k + 1], (k + 1) & 1)      # that slot's last slab was counted, and waited for, at step k - 1
+        table.add(src.address(z0, z1, k & 1, stream), src.ebytes, z0, z1 - z0, H, W, per_slice)
+    keys, cnt, box = table.rows()
+    if len(shape) == 2:      # kernel (z, y, x) = image (y, 0, x)
+        box = box[:, [0, 2, 3, 5]]
+    box[:, box.shape[1] // 2:] += 1      # exclusive upper ends
+    if per_slice:
+        return LabelTable(keys & 0xffffffff, cnt, box[:, [1, 2, 4, 5]], keys >> 32, tuple(shape), table.doublings)
+    return LabelTable(keys, cnt, box, None, tuple(shape), table.doublings)
+
+
+@torch.no_grad()
+def label_table(labels, per_slice=False, device=None, slab=None, capacity=None):
+    """The ``LabelTable`` of a 2-D or 3-D label array (any integer dtype of 1, 2, 4 or 8 bytes; values in [0, 2^63), per slice in
+    [0, 2^32); anything else raises ``EmpError``).  ``labels``: a device tensor (read in place), a numpy array or a chunked
+    store; host data is streamed in slabs of ``slab`` leading-axis entries (default: about 64 MiB).  ``per_slice``: a 3-D array
+    as a stack of images, one row per (slice, label).  The result is exact, does not depend on ``slab`` and is
+    bit-reproducible.  ``capacity``: first size of the device table in slots (it doubles when it is too small)."""
+    _need_device()
+    device = _pick_device(device, labels)
+    with torch.cuda.device(device):
+        src = _source(labels, device)
+        return _table_of_source(src, src.shape, bool(per_slice), device, slab, capacity)
+
+
+# ----------------------------------------------------------------------------
+# policy: pure numpy on a LabelTable
+# ----------------------------------------------------------------------------
+def _ids(table, keep):
+    """the selected rows as ids (whole mode) or (slice, id) pairs (per-slice mode)"""
+    if table.per_slice:
+        return np.stack([table.slices[keep], table.labels[keep]], axis=1)
+    return table.labels[keep]
+
+
+def small_labels(table, minimum_area_allowed):
+    """ids with ``area <= minimum_area_allowed`` (the reference's ``<=``, _filter_small_labels.py:23), background excluded; per
+    slice: (slice, id) pairs"""
+    return _ids(table, (table.areas <= minimum_area_allowed) & (table.labels != 0))
+
+
+def boundary_labels(table):
+    """ids whose box touches a face of the array -- the four edges of a 2-D image, the six faces of a volume, and in per-slice
+    mode the four edges of each image -- background excluded"""
+    nd = table.boxes.shape[1] // 2
+    extent = np.asarray(table.shape[-nd:], dtype=np.int64)
+    touch = ((table.boxes[:, :nd] == 0) | (table.boxes[:, nd:] == extent)).any(axis=1)
+    return _ids(table, touch & (table.labels != 0))
+
+
+def count_labels(label_values, label_divisor):
+    """What _label_counter_widget.py:105-118 returns: ({class id: [label ids]}, [class ids]) of the label values given (the
+    widget passes the non-zero ones), classes ascending, class = value // divisor; a divisor of 0 puts all of them into class 1.
+    ``label_divisor`` is not negative."""
+    values = np.asarray(label_values).reshape(-1)
+    if label_divisor == 0:
+        return {1: values.tolist()}, [1]
+    # group the values by class in one stable sort: every class keeps its values in the order given
+    classes = np.floor_divide(values, label_divisor)
+    order = np.argsort(classes, kind='stable')
+    present, first = np.unique(classes[order], return_index=True)
+    groups = np.split(values[order], first[1:])
+    present = present.tolist()
+    return {c: g.tolist() for c, g in zip(present, groups)}, present
+
+
+def _per_slice_values(table):
+    """label values as the widgets collect them, np.unique(...)[1:]: the values that occur without the smallest one"""
+    if not table.per_slice:
+        return table.labels[1:]
+    return {z: table.labels[table.slices == z][1:] for z in range(table.shape[0])}
+
+
+def class_label_lists(table, label_divisor):
+    """the ids per class as Count Labels prints them (_label_counter_widget.py:243-246, :281-283): ``count_labels`` of
+    ``np.unique(labels)[1:]``; per slice a dict {slice: that}"""
+    v = _per_slice_values(table)
+    if table.per_slice:
+        return {z: count_labels(x, label_divisor)[0] for z, x in v.items()}
+    return count_labels(v, label_divisor)[0]
+
+
+def _queue(label_values, label_divisor):
+    """per class that occurs the free ids of its register: a mask over the register's offsets, of which offset 0 (the class's
+    own base id, which no instance gets) is never free"""
+    used = np.unique(np.asarray(label_values, dtype=np.int64))
+    d = int(label_divisor)
+    free = {}
+    for c in np.unique(used // d).tolist():
+        taken = np.zeros(d, dtype=bool)
+        taken[0] = True
+        lo, hi = np.searchsorted(used, [c * d, (c + 1) * d])
+        taken[used[lo:hi] - c * d] = True
+        free[c] = (c * d + np.flatnonzero(~taken)).tolist()
+    return free
+
+
+def next_available_labels(table, label_divisor):
+    """the widget's ``label_queue`` (_merge_split_widget.py:730-744): per class that occurs the unused ids of
+    (class * divisor, (class + 1) * divisor), ascending; per slice a dict {slice: that}"""
+    if not label_divisor > 0:
+        raise ValueError('Label divisor must be a positive integer!')
+    v = _per_slice_values(table)
+    if table.per_slice:
+        return {z: _queue(x, label_divisor) for z, x in v.items()}
+    return _queue(v, label_divisor)
+
+
+def next_available_label(queue, class_id, label_divisor):
+    """_merge_split_widget.py:751-759: pops the first free id of the class from ``queue`` (in place); a class that does not
+    occur gets its whole register, of which the first id is returned"""
+    free = queue.get(class_id)
+    if free is None:
+        base = class_id * label_divisor
+        free = queue[class_id] = list(range(base + 1, base + label_divisor))
+    return free.pop(0)
+
+
+def label_bbox(table, label_id, slice_index=None):
+    """``regionprops.bbox`` of one label for Jump to Label (_merge_split_widget.py:652-659); raises on an absent id as the widget
+    does.  Per-slice tables take the slice as well."""
+    hit = table.labels == int(label_id)
+    if table.per_slice:
+        if slice_index is None:
+            raise ValueError('label_bbox: a per-slice table needs slice_index')
+        hit &= table.slices == int(slice_index)
+    if int(label_id) == 0 or not hit.any():
+        raise Exception(f'No label {label_id} in the table')
+    return tuple(int(v) for v in table.boxes[np.flatnonzero(hit)[0]])
+
+
+# ----------------------------------------------------------------------------
+# device: the edit
+# ----------------------------------------------------------------------------
+class _Map:
+    """from -> to on the device (emp_label_map_build)"""
+
+    def __init__(self, keys, vals, device):
+        lib = _abi.load()
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        vals = np.ascontiguousarray(vals, dtype=np.uint64)
+        cap = 64
+        while cap < 2 * len(keys):
+            cap *= 2
+        self.capacity = cap
+        self.keys = torch.empty(cap, dtype=torch.int64, device=device)
+        self.vals = torch.empty(cap, dtype=torch.int64, device=device)
+        _abi.check(lib.emp_label_map_build(_hp(keys), _hp(vals), len(keys), _abi.ptr(self.keys), _abi.ptr(self.vals), cap,
+                                           _abi.stream_ptr(device)), 'emp_label_map_build')
+
+    def apply(self, key_addr, key_bytes, src_addr, src_bytes, out_addr, z0, depth, H, W, per_slice, device):
+        _abi.check(_abi.load().emp_label_apply_map(C.c_void_p(key_addr), key_bytes, C.c_void_p(src_addr), src_bytes, C.c_void_p(out_addr),
+                                                   z0, depth, H, W, int(per_slice), _abi.ptr(self.keys), _abi.ptr(self.vals),
+                                                   self.capacity, _abi.stream_ptr(device)), 'emp_label_apply_map')
+
+
+def _is_numpy(x):
+    return isinstance(x, np.ndarray)
+
+
+def _check_values(vals, dtype, what):
+    dt = np.dtype(str(dtype).replace('torch.', ''))
+    top = 1 if dt.kind == 'b' else np.iinfo(dt).max
+    vals = np.asarray(vals, dtype=np.int64)
+    if len(vals) and (vals.min() < 0 or vals.max() > top):
+        raise ValueError(f'{what}: a new label does not fit the array\'s dtype {dtype}')
+
+
+def _apply(labels, keys, vals, per_slice, device, out, inplace, slab, what):
+    """out[i] = map[key(i)] if present else labels[i]; keys are labels, or slice << 32 | label with per_slice"""
+    if isinstance(labels, torch.Tensor) and not labels.is_cuda:
+        raise TypeError(f'{what}: a torch tensor must be on the device (pass host data as a numpy array)')
+    src = _source(labels, device)
+    rows, H, W = _geometry(src.shape, per_slice, what)
+    _check_values(vals, src.t.dtype if isinstance(src, _DeviceSource) else src.dtype, what)
+    m = _Map(keys, vals, device)
+    stream = torch.cuda.current_stream(device)
+    if isinstance(src, _DeviceSource):
+        if out is not None:
+            raise TypeError(f'{what}: out= is for chunked stores; a device tensor is returned as a device tensor')
+        if inplace and src.t is not labels:
+            raise ValueError(f'{what}: inplace=True needs a contiguous tensor')
+        res = src.t if inplace else torch.empty_like(src.t)
+        m.apply(src.t.data_ptr(), src.ebytes, src.t.data_ptr(), src.ebytes, res.data_ptr(), 0, rows, H, W, per_slice, device)
+        return res
+    if _is_numpy(labels):
+        if out is not None:
+            raise TypeError(f'{what}: out= is for chunked stores; a numpy array is returned as a new array (or edited with inplace=True)')
+        out = labels if inplace else np.empty_like(labels)
+    elif out is None:
+        if not inplace:
+            raise TypeError(f'{what}: a chunked store is written slab by slab into out= (or into itself with inplace=True)')
+        out = labels
+    elif tuple(out.shape) != src.shape or np.dtype(out.dtype) != src.dtype:
+        raise ValueError(f'{what}: out= must have the shape and dtype of the labels')
+    slab, bounds = _slabs(src, slab, rows)
+    src.reserve(slab, torch.cuda.Stream(device=device))
+    back = torch.empty(max(1, slab * src.row_bytes), dtype=torch.uint8).pin_memory()
+    if bounds:
+        src.stage(*bounds[0], 0)
+    for k, (z0, z1) in enumerate(bounds):
+        if k + 1 < len(bounds):
+            src.stage(*bounds[k + 1], (k + 1) & 1)
+        addr = src.address(z0, z1, k & 1, stream)
+        m.apply(addr, src.ebytes, addr, src.ebytes, addr, z0, z1 - z0, H, W, per_slice, device)
+        nbytes = (z1 - z0) * src.row_bytes
+        back[:nbytes].copy_(src.dev[k & 1][:nbytes], non_blocking=True)
+        stream.synchronize()      # the slab is on the host; its device buffer is free for the upload after next
+        out[z0:z1] = back[:nbytes].numpy().view(src.dtype).reshape((z1 - z0,) + src.shape[1:])
+    return out
+
+
+def _map_keys(ids, per_slice):
+    ids = np.asarray(ids, dtype=np.int64)
+    if per_slice:
+        ids = ids.reshape(-1, 2)
+        return (ids[:, 0].astype(np.uint64) << np.uint64(32)) | ids[:, 1].astype(np.uint64)
+    return ids.reshape(-1).astype(np.uint64)
+
+
+@torch.no_grad()
+def delete_labels(labels, ids, device=None, out=None, inplace=False, slab=None):
+    """Delete Labels (_merge_split_widget.py:246-250): every voxel of the given ids becomes 0, all ids in one pass.  Zeros in
+    ``ids`` are dropped, as the widget does."""
+    _need_device()
+    device = _pick_device(device, labels)
+    ids = np.unique(np.asarray(ids, dtype=np.int64).reshape(-1))
+    ids = ids[ids > 0]
+    with torch.cuda.device(device):
+        return _apply(labels, _map_keys(ids, False), np.zeros(len(ids), np.int64), False, device, out, inplace, slab, 'delete_labels')
+
+
+@torch.no_grad()
+def merge_labels(labels, ids, new_label_id=None, device=None, out=None, inplace=False, slab=None):
+    """Merge Labels (_merge_split_widget.py:373-387): every voxel of the given ids becomes ``new_label_id`` (default: the
+    smallest of them, :378-381).  Zeros in ``ids`` are dropped."""
+    _need_device()
+    device = _pick_device(device, labels)
+    ids = np.unique(np.asarray(ids, dtype=np.int64).reshape(-1))
+    ids = ids[ids > 0]
+    if len(ids) == 0:
+        raise ValueError('merge_labels: no label to merge')
+    new = int(ids.min()) if new_label_id is None else int(new_label_id)
+    ids = ids[ids != new]
+    with torch.cuda.device(device):
+        return _apply(labels, _map_keys(ids, False), np.full(len(ids), new, np.int64), False, device, out, inplace, slab, 'merge_labels')
+
+
+@torch.no_grad()
+def filter_out_small_label_areas(img, minimum_area_allowed, per_slice=False, device=None, out=None, inplace=False, slab=None):
+    """_filter_small_labels.py:15-40: labels with ``area <= minimum_area_allowed`` are removed -> (image, number removed).
+    ``per_slice``: every image of a 3-D stack on its own (the widget's '2D patches'); the number is then the total over the
+    images.  An image without labels comes back unchanged with 0 (the reference raises an IndexError there)."""
+    _need_device()
+    device = _pick_device(device, img)
+    with torch.cuda.device(device):
+        table = label_table(img, per_slice=per_slice, device=device, slab=slab)
+        ids = small_labels(table, minimum_area_allowed)
+        res = _apply(img, _map_keys(ids, per_slice), np.zeros(len(ids), np.int64), per_slice, device, out, inplace, slab,
+                     'filter_out_small_label_areas')
+    return res, len(ids)
+
+
+def _vanished(before, after):
+    """how many keys of `before` (background excluded) do not occur in `after`"""
+    def keys(t):
+        k = t.labels[t.labels != 0]
+        return k if not t.per_slice else (t.slices[t.labels != 0] << 32) | k
+    return int(len(np.setdiff1d(keys(before), keys(after))))
+
+
+@torch.no_grad()
+def remove_boundary_labels(labels, whole_labels=False, per_slice=False, device=None, out=None, inplace=False, slab=None):
+    """_filter_small_labels.py:43-60 -> (labels, number of labels removed).
+
+    ``whole_labels=False`` reproduces the reference's ``clear_border``: the array is split into connected components (full
+    connectivity: 8 neighbours in an image, 26 in a volume; equal value) and the components that touch a face are cleared; a
+    label that has another, interior component keeps it and is not counted as removed (:47-49).  The components come from
+    ``emp_ccl_range``, whose limits this mode inherits: the whole array on the device, fewer than 2^30 voxels, labels below
+    2^31 - 1 (int32 / int64 input; narrower types are converted on the device).  Outside those limits a ``ValueError`` names
+    the alternative: ``whole_labels=True`` removes every voxel of a label whose box touches a face, needs the table only and
+    works slab by slab on arrays of any size.  ``per_slice``: every image of a 3-D stack on its own; the number is then the
+    total over the images."""
+    _need_device()
+    device = _pick_device(device, labels)
+    what = 'remove_boundary_labels'
+    with torch.cuda.device(device):
+        if whole_labels:
+            table = label_table(labels, per_slice=per_slice, device=device, slab=slab)
+            ids = boundary_labels(table)
+            res = _apply(labels, _map_keys(ids, per_slice), np.zeros(len(ids), np.int64), per_slice, device, out, inplace, slab, what)
+            return res, len(ids)
+        shape = tuple(int(s) for s in labels.shape)
+        _geometry(shape, per_slice, what)
+        if int(np.prod(shape, dtype=np.int64)) >= CCL_MAX_VOXELS:
+            raise ValueError(f'{what}: the connected components of the reference mode need fewer than 2^30 voxels, the array has '
+                             f'{shape}; use whole_labels=True (removes whole labels by their boxes, slab by slab)')
+        on_device = isinstance(labels, torch.Tensor) and labels.is_cuda
+        # what the call cannot do is said before any work: nothing is written, on the device or to the caller's array, by then
+        if isinstance(labels, torch.Tensor) and not on_device:
+            raise TypeError(f'{what}: a torch tensor must be on the device (pass host data as a numpy array)')
+        if on_device or _is_numpy(labels):
+            if out is not None:
+                raise TypeError(f'{what}: out= is for chunked stores')
+            if on_device and inplace and not labels.is_contiguous():
+                raise ValueError(f'{what}: inplace=True needs a contiguous tensor')
+        elif out is None:
+            if not inplace:
+                raise TypeError(f'{what}: a chunked store is written into out= (or into itself with inplace=True)')
+            out = labels
+        elif tuple(out.shape) != shape or np.dtype(out.dtype) != np.dtype(labels.dtype):
+            raise ValueError(f'{what}: out= must have the shape and dtype of the labels')
+        if on_device:
+            t = labels if labels.is_contiguous() else labels.contiguous()
+        else:
+            host = np.ascontiguousarray(np.asarray(labels[...] if not _is_numpy(labels) else labels))
+            t = torch.from_numpy(host.view(np.uint8).reshape(-1)).to(device)      # as bytes: torch has no arithmetic on uint16 / uint32
+        ebytes = _ebytes(t.dtype if on_device else host.dtype)
+        rows, H, W = _geometry(shape, per_slice, what)
+        before = _table_of_source(_Raw(t, ebytes, shape), shape, per_slice, device, None, None)
+        # the largest label of any row: a per-slice table is sorted by slice first, its last row is only the last slice's
+        top = int(before.labels.max()) if len(before.labels) else 0
+        if top > CCL_MAX_LABEL:
+            raise ValueError(f'{what}: the connected components of the reference mode need labels below 2^31 - 1, the array holds '
+                             f'{top}; use whole_labels=True')
+        lib = _abi.load()
+        # component ids: per image (8-connected) or of the one volume (26-connected)
+        images = len(shape) == 2 or per_slice
+        N, depth, cH, cW = (shape[0] if len(shape) == 3 else 1, 0, shape[-2], shape[-1]) if images else (1, shape[0], shape[1], shape[2])
+        wide = _as_ccl_input(t, ebytes, shape)
+        comps = torch.empty((N if images else depth, cH, cW), dtype=torch.int32, device=device)
+        work = torch.empty(int(lib.emp_ccl8_work_bytes(N, cH, cW) if images else lib.emp_ccl8_work_bytes(1, depth * cH, cW)),
+                           dtype=torch.uint8, device=device)
+        _abi.check(lib.emp_ccl_range(_abi.ptr(wide), 8 if wide.dtype == torch.int64 else 4, N, depth, cH, cW, 1, CCL_MAX_LABEL + 1,
+                                     _abi.ptr(comps), None, _abi.ptr(work), _abi.stream_ptr(device)), 'emp_ccl_range')
+        del wide, work
+        # components are numbered per image: their key is slice << 32 | id there
+        ctable = _table_of_source(_Raw(comps, -4, tuple(comps.shape)), tuple(comps.shape), images, device, None, None)
+        cids = boundary_labels(ctable)
+        m = _Map(_map_keys(cids, images), np.zeros(len(cids), np.int64), device)
+        res = t if (inplace and on_device) else torch.empty_like(t)
+        m.apply(comps.data_ptr(), -4, t.data_ptr(), ebytes, res.data_ptr(), 0, comps.shape[0], cH, cW, images, device)
+        after = _table_of_source(_Raw(res, ebytes, shape), shape, per_slice, device, None, None)
+        n_removed = _vanished(before, after)
+        if on_device:
+            return res, n_removed
+        arr = res.cpu().numpy().view(host.dtype).reshape(shape)
+        if _is_numpy(labels):
+            if inplace:
+                labels[...] = arr
+                return labels, n_removed
+            return arr, n_removed
+        out[...] = arr
+        return out, n_removed
+
+
+class _Raw:
+    """a device buffer with a given element size and shape as a table source (no dtype of torch's needed)"""
+
+    def __init__(self, t, ebytes, shape):
+        self.t = t
+        self.ebytes = ebytes
+        self.shape = tuple(shape)
+        self.row_bytes = int(np.prod(self.shape[1:], dtype=np.int64)) * abs(ebytes)
+
+    def address(self, z0, z1, slot, stream):
+        return self.t.data_ptr() + z0 * self.row_bytes
+
+
+def _as_ccl_input(t, ebytes, shape):
+    """the labels as the int32 / int64 tensor emp_ccl_range reads: itself, or a widened copy made on the device"""
+    raw = t.reshape(-1).view(torch.uint8)
+    if abs(ebytes) == 8:
+        return raw.view(torch.int64)      # values are below 2^31 - 1 (checked on the table): signedness does not matter
+    if ebytes == -4:
+        return raw.view(torch.int32)
+    if ebytes == 4:
+        return raw.view(torch.int32).to(torch.int64) & 0xffffffff
+    if abs(ebytes) == 2:
+        return raw.view(torch.int16).to(torch.int32) & 0xffff if ebytes > 0 else raw.view(torch.int16).to(torch.int32)
+    return (raw if ebytes > 0 else raw.view(torch.int8)).to(torch.int32)

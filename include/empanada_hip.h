@@ -668,6 +668,62 @@ EMP_API int emp_overlap_match(int64_t k, const int64_t* h_a, const int64_t* h_b,
                       int64_t* h_a_labels, int64_t* h_a_areas, int64_t* n_a, int64_t* h_b_labels, int64_t* h_b_areas, int64_t* n_b,
                       int64_t* h_rows, int64_t* h_cols, double* h_iou, int64_t* h_inter, int64_t* n_match);
 
+/* ------------------------------------------------------------------------
+ * 7. Clean-up of label volumes (csrc/labels.hip): the per-label table (voxel
+ *    count and bounding box of every label that occurs) and the edit of a
+ *    volume through a `from -> to` map.  The two primitives behind the
+ *    plugin's Filter Small Labels (empanada_napari/_filter_small_labels.py:
+ *    15-60), Count Labels (_label_counter_widget.py:105-118, :243), Delete
+ *    Labels (_merge_split_widget.py:212-280), Merge Labels (:282-420), Jump to
+ *    Label (:637-680) and Find Next Available Label (:682-763).
+ *
+ *    skimage is not available where this library is built: what
+ *    regionprops_table (area, bbox) and clear_border compute is restated from
+ *    their documented behaviour and is NOT pinned against them (like rows
+ *    a13 / a14 of the README table); the tests state it in numpy / scipy.
+ *
+ *    The table is a device buffer of emp_label_table_work_bytes(capacity)
+ *    bytes with the life cycle and the overflow contract of section 6: reset
+ *    once, fed slab by slab, grown when an accumulate reports an overflow.
+ * ---------------------------------------------------------------------- */
+/* 0 if the capacity is not a power of two in [64, 2^32] */
+EMP_API size_t emp_label_table_work_bytes(int64_t capacity);
+EMP_API int emp_label_table_reset(void* d_table, int64_t capacity, void* stream);
+/* Adds the slab d_labels (depth, H, W) whose first leading-axis index is z0 to the table: per key the uint64 voxel count
+ * (regionprops_table's `area`, _filter_small_labels.py:16; np.unique(return_counts=True)) and the min / max of z, y, x in GLOBAL
+ * coordinates (regionprops' bbox, _merge_split_widget.py:653-655; the box clear_border's border test needs,
+ * _filter_small_labels.py:45).  in_bytes: element size 1, 2, 4 or 8, NEGATIVE for a signed type, as emp_ccl_range and
+ * emp_label_overlap_accumulate take it.  per_slice 0: key = the label, any value in [0, 2^63); per_slice 1: key =
+ * slice << 32 | label with labels in [0, 2^32) (the widgets' "2D patches" mode, _filter_small_labels.py:120-125).  A value
+ * outside the domain, negative included, is EMP_ERR_INVALID (the table's content is then undefined), never wrapped.  Label 0 is
+ * a key like any other.  z0 + depth < 2^31.  Synchronises the stream.  *h_overflow = 1: the table is too small for this slab;
+ * the call has removed the counts it had added (the min / max it left in stored keys are idempotent: they are the right values
+ * once the slab is counted again): move the table to a larger one with emp_label_table_grow and call again. */
+EMP_API int emp_label_table_accumulate(const void* d_labels, int in_bytes, int64_t z0, int depth, int H, int W, int per_slice,
+                                 void* d_table, int64_t capacity, void* stream, int* h_overflow);
+/* Re-inserts the counted cells of d_from into the reset, larger table d_to.  Synchronises.  *h_overflow = 1: d_to is too small too. */
+EMP_API int emp_label_table_grow(const void* d_from, int64_t from_capacity, void* d_to, int64_t to_capacity, void* stream,
+                                 int* h_overflow);
+/* *h_num = the number of keys, of which min(*h_num, max_out) are written, in no particular order: d_keys[i], d_counts[i] and
+ * d_boxes[6 i ..] = {min z, min y, min x, max z, max y, max x}, the maxima INCLUSIVE (regionprops' bbox has them exclusive: + 1).
+ * Synchronises.  The table stays valid and can be fed further. */
+EMP_API int emp_label_table_finalize(void* d_table, int64_t capacity, uint64_t* d_keys, uint64_t* d_counts, uint32_t* d_boxes,
+                                 int64_t max_out, int64_t* h_num, void* stream);
+/* An open-addressing map of n entries h_keys[i] -> h_vals[i] (HOST arrays; keys in [0, 2^63), a key given twice keeps its last
+ * value) in the device arrays d_map_keys / d_map_vals of map_capacity uint64 each; map_capacity: a power of two in [64, 2^32],
+ * at least 2 n.  Synchronises. */
+EMP_API int emp_label_map_build(const uint64_t* h_keys, const uint64_t* h_vals, int64_t n, uint64_t* d_map_keys, uint64_t* d_map_vals,
+                                 int64_t map_capacity, void* stream);
+/* d_out[i] = map[key(i)] if present, else d_src[i], over the slab (depth, H, W) starting at leading-axis index z0: all
+ * `labels[labels == l] = v` passes of remove_label_from_image (_filter_small_labels.py:10-12,27-28), Delete Labels
+ * (_merge_split_widget.py:249-250) and Merge Labels (:385-387) in one.  key(i) = d_key[i], or slice << 32 | d_key[i] with
+ * per_slice 1.  d_key may be d_src (delete, merge, filter) or another array of the same shape (component ids: only the
+ * components of a label that touch a border go, as clear_border does it); d_out may be d_src.  d_out has d_src's element size.
+ * A key value of 0 is background and is never looked up; a value outside the key's domain is in no map.  Does not synchronise. */
+EMP_API int emp_label_apply_map(const void* d_key, int key_bytes, const void* d_src, int src_bytes, void* d_out, int64_t z0, int depth,
+                                 int H, int W, int per_slice, const uint64_t* d_map_keys, const uint64_t* d_map_vals,
+                                 int64_t map_capacity, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

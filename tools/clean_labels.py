@@ -1,0 +1,98 @@
+"""Clean up a label volume on the device and print one JSON object: the plugin's Filter Small Labels, Delete Labels, Merge Labels
+and Count Labels on a file.
+Usage: python tools/clean_labels.py IN [OUT] [--min-area N | --boundary [--whole-labels] | --delete IDS | --merge IDS [--into ID] |
+                                             --count --label-divisor D] [--per-slice]
+IN / OUT: .npy files (IN is memory-mapped and streamed in slabs, OUT is created) or zarr array directories (OUT is created with
+IN's shape, dtype and chunks).  IDS: comma-separated label ids.  --count needs no OUT."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import __graft_entry__ as ge  # noqa: E402
+
+ge.load_package()
+from empanada_napari_amd import labels as L, zstore  # noqa: E402
+
+
+def _open(path):
+    return np.load(path, mmap_mode='r') if path.endswith('.npy') else zstore.DirArray(path)
+
+
+def _create(path, like):
+    if path.endswith('.npy'):
+        return np.lib.format.open_memmap(path, mode='w+', dtype=np.dtype(like.dtype), shape=tuple(like.shape))
+    chunks = getattr(like, 'chunks', None) or tuple(min(s, 64) for s in like.shape)
+    return zstore.DirArray.create(path, tuple(like.shape), np.dtype(like.dtype), chunks, overwrite=True)
+
+
+def _ids(text):
+    return [int(v) for v in text.split(',') if v.strip()]
+
+
+def _occurring(table, ids):
+    """how many of the ids given occur in the volume (background never counts)"""
+    ids = np.unique(np.asarray(ids, dtype=np.int64))
+    return int(np.isin(ids[ids > 0], table.labels).sum())
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument('src')
+    ap.add_argument('dst', nargs='?')
+    op = ap.add_mutually_exclusive_group(required=True)
+    op.add_argument('--min-area', type=int)
+    op.add_argument('--boundary', action='store_true')
+    op.add_argument('--delete', type=_ids)
+    op.add_argument('--merge', type=_ids)
+    op.add_argument('--count', action='store_true')
+    ap.add_argument('--whole-labels', action='store_true')
+    ap.add_argument('--into', type=int, default=None, help='--merge: the id the others become (default: the smallest)')
+    ap.add_argument('--label-divisor', type=int, default=0)
+    ap.add_argument('--per-slice', action='store_true')
+    args = ap.parse_args(argv)
+    if not args.count and not args.dst:
+        ap.error('OUT is needed for every operation but --count')
+    src = _open(args.src)
+    if args.count:
+        table = L.label_table(src, per_slice=args.per_slice)
+        lists = L.class_label_lists(table, args.label_divisor)
+        count = (lambda q: {str(k): len(v) for k, v in q.items()})
+        out = {'shape': list(table.shape), 'labels': {str(z): count(q) for z, q in lists.items()} if args.per_slice else count(lists)}
+        print(json.dumps(out))
+        return out
+    dst = _create(args.dst, src)
+
+    def run(fn, *a, **k):
+        """stores are written slab by slab; a .npy input is an array to the library: its result is copied into the output map"""
+        if isinstance(src, np.ndarray):
+            res = fn(np.asarray(src), *a, **k)
+            dst[...] = res[0] if isinstance(res, tuple) else res
+        else:
+            res = fn(src, *a, out=dst, **k)
+        return res[1] if isinstance(res, tuple) else None
+
+    if args.min_area is not None:
+        n = run(L.filter_out_small_label_areas, args.min_area, per_slice=args.per_slice)
+    elif args.boundary:
+        n = run(L.remove_boundary_labels, whole_labels=args.whole_labels, per_slice=args.per_slice)
+    else:      # the edits by id do not look at the volume's labels: the number of ids that occur comes from its table
+        ids = args.delete if args.delete is not None else args.merge
+        n = _occurring(L.label_table(src), ids)
+        if args.delete is not None:
+            run(L.delete_labels, ids)
+        else:
+            run(L.merge_labels, ids, new_label_id=args.into)
+    if hasattr(dst, 'flush'):
+        dst.flush()
+    out = {'shape': list(src.shape), 'labels_affected': int(n), 'out': args.dst}
+    print(json.dumps(out))
+    return out
+
+
+if __name__ == '__main__':
+    main()
