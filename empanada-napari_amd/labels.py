@@ -34,7 +34,7 @@ import numpy as np
 import torch
 
 from . import _abi
-from .metrics import SLAB_BYTES, _DeviceSource, _HostSource, _ebytes, _hp, _source, initial_capacity
+from ._labelstream import GrowableTable, RawSource, ebytes, hp, initial_capacity, need_device, pick_device, slab_plan, source, stream_slabs
 
 __all__ = ['LabelTable', 'label_table', 'table_from_arrays', 'small_labels', 'boundary_labels', 'count_labels', 'class_label_lists',
            'next_available_labels', 'next_available_label', 'label_bbox', 'delete_labels', 'merge_labels',
@@ -88,22 +88,6 @@ def table_from_arrays(labels, areas, boxes, shape, slices=None, doublings=0):
 # ----------------------------------------------------------------------------
 # device: the table
 # ----------------------------------------------------------------------------
-def _need_device():
-    if not torch.cuda.is_available():
-        raise RuntimeError('empanada_napari_amd needs a HIP device (MI355X); there is no CPU fallback')
-    _abi.load()
-
-
-def _pick_device(device, *arrays):
-    if device is None:
-        dev_in = [x.device for x in arrays if isinstance(x, torch.Tensor) and x.is_cuda]
-        device = dev_in[0] if dev_in else torch.device('cuda', torch.cuda.current_device())
-    device = torch.device(device)
-    if device.index is None:
-        device = torch.device('cuda', torch.cuda.current_device())
-    return device
-
-
 def _geometry(shape, per_slice, what):
     """(rows, H, W) as the kernels see a slab of `rows` leading-axis entries.  A 2-D image (R, W) is R slabs of one row each:
     the kernels' z is the image's y, so that a host image is streamed by rows like a volume by slices."""
@@ -116,84 +100,13 @@ def _geometry(shape, per_slice, what):
     raise ValueError(f'{what}: 2-D or 3-D label arrays, got shape {shape}')
 
 
-class _Table:
-    def __init__(self, capacity, device):
-        self.lib = _abi.load()
-        self.device = device
-        self.doublings = 0
-        self.capacity = int(capacity)
-        self.buf = self._new(self.capacity)
-
-    def _new(self, capacity):
-        nbytes = self.lib.emp_label_table_work_bytes(capacity)
-        if nbytes == 0:
-            raise ValueError(f'label_table: capacity {capacity} is not a power of two in [64, 2^32]')
-        buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        _abi.check(self.lib.emp_label_table_reset(_abi.ptr(buf), capacity, _abi.stream_ptr(self.device)), 'emp_label_table_reset')
-        return buf
-
-    def _grow(self):
-        cap = self.capacity
-        while True:
-            cap *= 2
-            new = self._new(cap)
-            ov = C.c_int(0)
-            _abi.check(self.lib.emp_label_table_grow(_abi.ptr(self.buf), self.capacity, _abi.ptr(new), cap, _abi.stream_ptr(self.device),
-                                                     C.byref(ov)), 'emp_label_table_grow')
-            self.doublings += 1
-            if not ov.value:
-                break
-        self.buf, self.capacity = new, cap
-
-    def add(self, address, ebytes, z0, depth, H, W, per_slice):
-        while True:
-            ov = C.c_int(0)
-            _abi.check(self.lib.emp_label_table_accumulate(C.c_void_p(address), ebytes, z0, depth, H, W, int(per_slice), _abi.ptr(self.buf),
-                                                           self.capacity, _abi.stream_ptr(self.device), C.byref(ov)),
-                       'emp_label_table_accumulate')
-            if not ov.value:
-                return
-            self._grow()      # the failed call has taken its counts out again: count the slab once more
-
-    def rows(self):
-        """(keys, counts, boxes (k, 6)) as numpy arrays, sorted by key"""
-        num = C.c_int64(0)
-        stream = _abi.stream_ptr(self.device)
-        _abi.check(self.lib.emp_label_table_finalize(_abi.ptr(self.buf), self.capacity, None, None, None, 0, C.byref(num), stream),
-                   'emp_label_table_finalize')
-        k = num.value
-        keys = torch.empty(max(k, 1), dtype=torch.int64, device=self.device)
-        cnt = torch.empty(max(k, 1), dtype=torch.int64, device=self.device)
-        box = torch.empty((max(k, 1), 6), dtype=torch.int32, device=self.device)
-        _abi.check(self.lib.emp_label_table_finalize(_abi.ptr(self.buf), self.capacity, _abi.ptr(keys), _abi.ptr(cnt), _abi.ptr(box), k,
-                                                     C.byref(num), stream), 'emp_label_table_finalize')
-        skeys, order = torch.sort(keys[:k])      # keys lie below 2^63: the signed order is theirs
-        return skeys.cpu().numpy(), cnt[:k][order].cpu().numpy(), box[:k][order].cpu().numpy().astype(np.int64)
-
-
-def _slabs(src, slab, rows):
-    host = isinstance(src, _HostSource)
-    if slab is None:
-        slab = rows if not host else max(1, SLAB_BYTES // max(1, src.row_bytes))
-    slab = max(1, min(int(slab), max(rows, 1)))
-    return slab, [(z, min(rows, z + slab)) for z in range(0, rows, slab)]
-
-
 def _table_of_source(src, shape, per_slice, device, slab, capacity):
     rows, H, W = _geometry(shape, per_slice, 'label_table')
-    table = _Table(capacity or initial_capacity(rows * H * W), device)
-    slab, bounds = _slabs(src, slab, rows)
-    stream = torch.cuda.current_stream(device)
-    host = isinstance(src, _HostSource)
-    if host:
-        src.reserve(slab, torch.cuda.Stream(device=device))
-        if bounds:
-            src.stage(*bounds[0], 0)
-    for k, (z0, z1) in enumerate(bounds):
-        if host and k + 1 < len(bounds):
-            src.stage(*bounds[k + 1], (k + 1) & 1)      # that slot's last slab was counted, and waited for, at step k - 1
-        table.add(src.address(z0, z1, k & 1, stream), src.ebytes, z0, z1 - z0, H, W, per_slice)
-    keys, cnt, box = table.rows()
+    table = GrowableTable('emp_label_table', 'label_table', capacity or initial_capacity(rows * H * W), device)
+    for _, z0, z1, (address,) in stream_slabs([src], slab, device):
+        table.add(address, src.ebytes, z0, z1 - z0, H, W, int(per_slice))
+    keys, cnt, box = (t.cpu().numpy() for t in table.finalize(extra=[(6, torch.int32)]))      # the keys lie below 2^63
+    box = box.astype(np.int64)
     if len(shape) == 2:      # kernel (z, y, x) = image (y, 0, x)
         box = box[:, [0, 2, 3, 5]]
     box[:, box.shape[1] // 2:] += 1      # exclusive upper ends
@@ -209,10 +122,10 @@ def label_table(labels, per_slice=False, device=None, slab=None, capacity=None):
     store; host data is streamed in slabs of ``slab`` leading-axis entries (default: about 64 MiB).  ``per_slice``: a 3-D array
     as a stack of images, one row per (slice, label).  The result is exact, does not depend on ``slab`` and is
     bit-reproducible.  ``capacity``: first size of the device table in slots (it doubles when it is too small)."""
-    _need_device()
-    device = _pick_device(device, labels)
+    need_device()
+    device = pick_device(device, labels)
     with torch.cuda.device(device):
-        src = _source(labels, device)
+        src = source(labels, device)
         return _table_of_source(src, src.shape, bool(per_slice), device, slab, capacity)
 
 
@@ -338,7 +251,7 @@ class _Map:
         self.capacity = cap
         self.keys = torch.empty(cap, dtype=torch.int64, device=device)
         self.vals = torch.empty(cap, dtype=torch.int64, device=device)
-        _abi.check(lib.emp_label_map_build(_hp(keys), _hp(vals), len(keys), _abi.ptr(self.keys), _abi.ptr(self.vals), cap,
+        _abi.check(lib.emp_label_map_build(hp(keys), hp(vals), len(keys), _abi.ptr(self.keys), _abi.ptr(self.vals), cap,
                                            _abi.stream_ptr(device)), 'emp_label_map_build')
 
     def apply(self, key_addr, key_bytes, src_addr, src_bytes, out_addr, z0, depth, H, W, per_slice, device):
@@ -359,48 +272,64 @@ def _check_values(vals, dtype, what):
         raise ValueError(f'{what}: a new label does not fit the array\'s dtype {dtype}')
 
 
-def _apply(labels, keys, vals, per_slice, device, out, inplace, slab, what):
-    """out[i] = map[key(i)] if present else labels[i]; keys are labels, or slice << 32 | label with per_slice"""
-    if isinstance(labels, torch.Tensor) and not labels.is_cuda:
-        raise TypeError(f'{what}: a torch tensor must be on the device (pass host data as a numpy array)')
-    src = _source(labels, device)
-    rows, H, W = _geometry(src.shape, per_slice, what)
-    _check_values(vals, src.t.dtype if isinstance(src, _DeviceSource) else src.dtype, what)
-    m = _Map(keys, vals, device)
-    stream = torch.cuda.current_stream(device)
-    if isinstance(src, _DeviceSource):
+def _edit_target(labels, out, inplace, shape, dtype, what):
+    """The output rules of an edit: every check of (labels, out, inplace), and where the result goes.  A device tensor gives a
+    device tensor and a numpy array a numpy array, the caller's own with ``inplace=True`` and a new one (None is returned)
+    without; a chunked store of ``shape`` and ``dtype`` is written into ``out=``, or into itself with ``inplace=True``."""
+    if isinstance(labels, torch.Tensor):
+        if not labels.is_cuda:
+            raise TypeError(f'{what}: a torch tensor must be on the device (pass host data as a numpy array)')
         if out is not None:
             raise TypeError(f'{what}: out= is for chunked stores; a device tensor is returned as a device tensor')
-        if inplace and src.t is not labels:
+        if inplace and not labels.is_contiguous():
             raise ValueError(f'{what}: inplace=True needs a contiguous tensor')
-        res = src.t if inplace else torch.empty_like(src.t)
-        m.apply(src.t.data_ptr(), src.ebytes, src.t.data_ptr(), src.ebytes, res.data_ptr(), 0, rows, H, W, per_slice, device)
-        return res
+        return labels if inplace else None
     if _is_numpy(labels):
         if out is not None:
             raise TypeError(f'{what}: out= is for chunked stores; a numpy array is returned as a new array (or edited with inplace=True)')
-        out = labels if inplace else np.empty_like(labels)
-    elif out is None:
+        return labels if inplace else None
+    if out is None:
         if not inplace:
-            raise TypeError(f'{what}: a chunked store is written slab by slab into out= (or into itself with inplace=True)')
-        out = labels
-    elif tuple(out.shape) != src.shape or np.dtype(out.dtype) != src.dtype:
+            raise TypeError(f'{what}: a chunked store is written into out= (or into itself with inplace=True)')
+        return labels
+    if tuple(out.shape) != tuple(shape) or np.dtype(out.dtype) != np.dtype(dtype):
         raise ValueError(f'{what}: out= must have the shape and dtype of the labels')
-    slab, bounds = _slabs(src, slab, rows)
-    src.reserve(slab, torch.cuda.Stream(device=device))
+    return out
+
+
+def _write_back(target, z0, z1, host, dtype, shape):
+    """rows [z0, z1) of a finished result of ``shape``, downloaded as the bytes ``host``, go to the target ``_edit_target`` chose;
+    without one they are the new array"""
+    arr = host.numpy().view(dtype).reshape((z1 - z0,) + tuple(shape[1:]))
+    if target is None:
+        return arr
+    target[z0:z1] = arr
+    return target
+
+
+def _apply(labels, keys, vals, per_slice, device, out, inplace, slab, what):
+    """out[i] = map[key(i)] if present else labels[i]; keys are labels, or slice << 32 | label with per_slice"""
+    src = source(labels, device)
+    target = _edit_target(labels, out, inplace, src.shape, src.dtype, what)
+    rows, H, W = _geometry(src.shape, per_slice, what)
+    _check_values(vals, src.dtype, what)
+    m = _Map(keys, vals, device)
+    if not src.is_host:
+        res = src.t if inplace else torch.empty_like(src.t)
+        m.apply(src.t.data_ptr(), src.ebytes, src.t.data_ptr(), src.ebytes, res.data_ptr(), 0, rows, H, W, per_slice, device)
+        return res
+    if target is None:
+        target = np.empty_like(labels)
+    stream = torch.cuda.current_stream(device)
+    slab, _ = slab_plan(rows, src.row_bytes, slab)      # planned here for the size of the download buffer
     back = torch.empty(max(1, slab * src.row_bytes), dtype=torch.uint8).pin_memory()
-    if bounds:
-        src.stage(*bounds[0], 0)
-    for k, (z0, z1) in enumerate(bounds):
-        if k + 1 < len(bounds):
-            src.stage(*bounds[k + 1], (k + 1) & 1)
-        addr = src.address(z0, z1, k & 1, stream)
+    for k, z0, z1, (addr,) in stream_slabs([src], slab, device):
         m.apply(addr, src.ebytes, addr, src.ebytes, addr, z0, z1 - z0, H, W, per_slice, device)
         nbytes = (z1 - z0) * src.row_bytes
         back[:nbytes].copy_(src.dev[k & 1][:nbytes], non_blocking=True)
         stream.synchronize()      # the slab is on the host; its device buffer is free for the upload after next
-        out[z0:z1] = back[:nbytes].numpy().view(src.dtype).reshape((z1 - z0,) + src.shape[1:])
-    return out
+        _write_back(target, z0, z1, back[:nbytes], src.dtype, src.shape)
+    return target
 
 
 def _map_keys(ids, per_slice):
@@ -415,8 +344,8 @@ def _map_keys(ids, per_slice):
 def delete_labels(labels, ids, device=None, out=None, inplace=False, slab=None):
     """Delete Labels (_merge_split_widget.py:246-250): every voxel of the given ids becomes 0, all ids in one pass.  Zeros in
     ``ids`` are dropped, as the widget does."""
-    _need_device()
-    device = _pick_device(device, labels)
+    need_device()
+    device = pick_device(device, labels)
     ids = np.unique(np.asarray(ids, dtype=np.int64).reshape(-1))
     ids = ids[ids > 0]
     with torch.cuda.device(device):
@@ -427,8 +356,8 @@ def delete_labels(labels, ids, device=None, out=None, inplace=False, slab=None):
 def merge_labels(labels, ids, new_label_id=None, device=None, out=None, inplace=False, slab=None):
     """Merge Labels (_merge_split_widget.py:373-387): every voxel of the given ids becomes ``new_label_id`` (default: the
     smallest of them, :378-381).  Zeros in ``ids`` are dropped."""
-    _need_device()
-    device = _pick_device(device, labels)
+    need_device()
+    device = pick_device(device, labels)
     ids = np.unique(np.asarray(ids, dtype=np.int64).reshape(-1))
     ids = ids[ids > 0]
     if len(ids) == 0:
@@ -444,8 +373,8 @@ def filter_out_small_label_areas(img, minimum_area_allowed, per_slice=False, dev
     """_filter_small_labels.py:15-40: labels with ``area <= minimum_area_allowed`` are removed -> (image, number removed).
     ``per_slice``: every image of a 3-D stack on its own (the widget's '2D patches'); the number is then the total over the
     images.  An image without labels comes back unchanged with 0 (the reference raises an IndexError there)."""
-    _need_device()
-    device = _pick_device(device, img)
+    need_device()
+    device = pick_device(device, img)
     with torch.cuda.device(device):
         table = label_table(img, per_slice=per_slice, device=device, slab=slab)
         ids = small_labels(table, minimum_area_allowed)
@@ -474,8 +403,8 @@ def remove_boundary_labels(labels, whole_labels=False, per_slice=False, device=N
     the alternative: ``whole_labels=True`` removes every voxel of a label whose box touches a face, needs the table only and
     works slab by slab on arrays of any size.  ``per_slice``: every image of a 3-D stack on its own; the number is then the
     total over the images."""
-    _need_device()
-    device = _pick_device(device, labels)
+    need_device()
+    device = pick_device(device, labels)
     what = 'remove_boundary_labels'
     with torch.cuda.device(device):
         if whole_labels:
@@ -488,29 +417,16 @@ def remove_boundary_labels(labels, whole_labels=False, per_slice=False, device=N
         if int(np.prod(shape, dtype=np.int64)) >= CCL_MAX_VOXELS:
             raise ValueError(f'{what}: the connected components of the reference mode need fewer than 2^30 voxels, the array has '
                              f'{shape}; use whole_labels=True (removes whole labels by their boxes, slab by slab)')
-        on_device = isinstance(labels, torch.Tensor) and labels.is_cuda
         # what the call cannot do is said before any work: nothing is written, on the device or to the caller's array, by then
-        if isinstance(labels, torch.Tensor) and not on_device:
-            raise TypeError(f'{what}: a torch tensor must be on the device (pass host data as a numpy array)')
-        if on_device or _is_numpy(labels):
-            if out is not None:
-                raise TypeError(f'{what}: out= is for chunked stores')
-            if on_device and inplace and not labels.is_contiguous():
-                raise ValueError(f'{what}: inplace=True needs a contiguous tensor')
-        elif out is None:
-            if not inplace:
-                raise TypeError(f'{what}: a chunked store is written into out= (or into itself with inplace=True)')
-            out = labels
-        elif tuple(out.shape) != shape or np.dtype(out.dtype) != np.dtype(labels.dtype):
-            raise ValueError(f'{what}: out= must have the shape and dtype of the labels')
+        target = _edit_target(labels, out, inplace, shape, labels.dtype, what)
+        on_device = isinstance(labels, torch.Tensor)      # a tensor that passed the check is on the device
         if on_device:
             t = labels if labels.is_contiguous() else labels.contiguous()
         else:
             host = np.ascontiguousarray(np.asarray(labels[...] if not _is_numpy(labels) else labels))
             t = torch.from_numpy(host.view(np.uint8).reshape(-1)).to(device)      # as bytes: torch has no arithmetic on uint16 / uint32
-        ebytes = _ebytes(t.dtype if on_device else host.dtype)
-        rows, H, W = _geometry(shape, per_slice, what)
-        before = _table_of_source(_Raw(t, ebytes, shape), shape, per_slice, device, None, None)
+        eb = ebytes(t.dtype if on_device else host.dtype)
+        before = _table_of_source(RawSource(t, eb, shape), shape, per_slice, device, None, None)
         # the largest label of any row: a per-slice table is sorted by slice first, its last row is only the last slice's
         top = int(before.labels.max()) if len(before.labels) else 0
         if top > CCL_MAX_LABEL:
@@ -520,7 +436,7 @@ def remove_boundary_labels(labels, whole_labels=False, per_slice=False, device=N
         # component ids: per image (8-connected) or of the one volume (26-connected)
         images = len(shape) == 2 or per_slice
         N, depth, cH, cW = (shape[0] if len(shape) == 3 else 1, 0, shape[-2], shape[-1]) if images else (1, shape[0], shape[1], shape[2])
-        wide = _as_ccl_input(t, ebytes, shape)
+        wide = _as_ccl_input(t, eb, shape)
         comps = torch.empty((N if images else depth, cH, cW), dtype=torch.int32, device=device)
         work = torch.empty(int(lib.emp_ccl8_work_bytes(N, cH, cW) if images else lib.emp_ccl8_work_bytes(1, depth * cH, cW)),
                            dtype=torch.uint8, device=device)
@@ -528,47 +444,27 @@ def remove_boundary_labels(labels, whole_labels=False, per_slice=False, device=N
                                      _abi.ptr(comps), None, _abi.ptr(work), _abi.stream_ptr(device)), 'emp_ccl_range')
         del wide, work
         # components are numbered per image: their key is slice << 32 | id there
-        ctable = _table_of_source(_Raw(comps, -4, tuple(comps.shape)), tuple(comps.shape), images, device, None, None)
+        ctable = _table_of_source(RawSource(comps, -4, tuple(comps.shape)), tuple(comps.shape), images, device, None, None)
         cids = boundary_labels(ctable)
         m = _Map(_map_keys(cids, images), np.zeros(len(cids), np.int64), device)
         res = t if (inplace and on_device) else torch.empty_like(t)
-        m.apply(comps.data_ptr(), -4, t.data_ptr(), ebytes, res.data_ptr(), 0, comps.shape[0], cH, cW, images, device)
-        after = _table_of_source(_Raw(res, ebytes, shape), shape, per_slice, device, None, None)
+        m.apply(comps.data_ptr(), -4, t.data_ptr(), eb, res.data_ptr(), 0, comps.shape[0], cH, cW, images, device)
+        after = _table_of_source(RawSource(res, eb, shape), shape, per_slice, device, None, None)
         n_removed = _vanished(before, after)
         if on_device:
             return res, n_removed
-        arr = res.cpu().numpy().view(host.dtype).reshape(shape)
-        if _is_numpy(labels):
-            if inplace:
-                labels[...] = arr
-                return labels, n_removed
-            return arr, n_removed
-        out[...] = arr
-        return out, n_removed
+        return _write_back(target, 0, shape[0], res.cpu(), host.dtype, shape), n_removed
 
 
-class _Raw:
-    """a device buffer with a given element size and shape as a table source (no dtype of torch's needed)"""
-
-    def __init__(self, t, ebytes, shape):
-        self.t = t
-        self.ebytes = ebytes
-        self.shape = tuple(shape)
-        self.row_bytes = int(np.prod(self.shape[1:], dtype=np.int64)) * abs(ebytes)
-
-    def address(self, z0, z1, slot, stream):
-        return self.t.data_ptr() + z0 * self.row_bytes
-
-
-def _as_ccl_input(t, ebytes, shape):
+def _as_ccl_input(t, eb, shape):
     """the labels as the int32 / int64 tensor emp_ccl_range reads: itself, or a widened copy made on the device"""
     raw = t.reshape(-1).view(torch.uint8)
-    if abs(ebytes) == 8:
+    if abs(eb) == 8:
         return raw.view(torch.int64)      # values are below 2^31 - 1 (checked on the table): signedness does not matter
-    if ebytes == -4:
+    if eb == -4:
         return raw.view(torch.int32)
-    if ebytes == 4:
+    if eb == 4:
         return raw.view(torch.int32).to(torch.int64) & 0xffffffff
-    if abs(ebytes) == 2:
-        return raw.view(torch.int16).to(torch.int32) & 0xffff if ebytes > 0 else raw.view(torch.int16).to(torch.int32)
-    return (raw if ebytes > 0 else raw.view(torch.int8)).to(torch.int32)
+    if abs(eb) == 2:
+        return raw.view(torch.int16).to(torch.int32) & 0xffff if eb > 0 else raw.view(torch.int16).to(torch.int32)
+    return (raw if eb > 0 else raw.view(torch.int8)).to(torch.int32)

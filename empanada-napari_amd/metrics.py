@@ -20,15 +20,10 @@ import numpy as np
 import torch
 
 from . import _abi
+from ._labelstream import GrowableTable, hp, initial_capacity, need_device, pick_device, source, stream_slabs
 
 __all__ = ['LabelOverlap', 'label_overlap', 'overlap_from_cells', 'compute_pixel_metrics', 'compute_instance_metrics', 'evaluate',
            'initial_capacity']
-
-SLAB_BYTES = 64 << 20      # default slab of a host array / chunked store: this many bytes of the wider side
-
-
-def _hp(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 @dataclass
@@ -65,154 +60,6 @@ def overlap_from_cells(a, b, counts, shape=(), doublings=0):
     return LabelOverlap(al, aa, bl, ba, np.stack([a, b], axis=1), counts, tuple(shape), doublings)
 
 
-def initial_capacity(n):
-    """First capacity (slots, a power of two) of the device table for ``n`` voxels: one slot per 64 voxels, at least 2^16
-    (1 MiB) and at most 2^22 (64 MiB).  A label volume whose objects are more than a few voxels wide has far fewer
-    distinct pairs than that; one that has more makes the table double (``LabelOverlap.doublings``)."""
-    c = 1 << 16
-    while c < (1 << 22) and c * 64 < n:
-        c <<= 1
-    return c
-
-
-# ----------------------------------------------------------------------------
-# device: the table
-# ----------------------------------------------------------------------------
-class _Table:
-    def __init__(self, capacity, device):
-        self.lib = _abi.load()
-        self.device = device
-        self.doublings = 0
-        self.capacity = int(capacity)
-        self.buf = self._new(self.capacity)
-
-    def _new(self, capacity):
-        nbytes = self.lib.emp_label_overlap_work_bytes(capacity)
-        if nbytes == 0:
-            raise ValueError(f'label_overlap: capacity {capacity} is not a power of two in [64, 2^32]')
-        buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        _abi.check(self.lib.emp_label_overlap_reset(_abi.ptr(buf), capacity, _abi.stream_ptr(self.device)), 'emp_label_overlap_reset')
-        return buf
-
-    def _grow(self):
-        cap = self.capacity
-        while True:
-            cap *= 2
-            new = self._new(cap)
-            ov = C.c_int(0)
-            _abi.check(self.lib.emp_label_overlap_grow(_abi.ptr(self.buf), self.capacity, _abi.ptr(new), cap, _abi.stream_ptr(self.device),
-                                                       C.byref(ov)), 'emp_label_overlap_grow')
-            self.doublings += 1
-            if not ov.value:
-                break
-        self.buf, self.capacity = new, cap
-
-    def add(self, pa, abytes, pb, bbytes, n):
-        """count n voxels at device addresses pa / pb (element sizes abytes / bbytes, negative = signed) into the table"""
-        while True:
-            ov = C.c_int(0)
-            _abi.check(self.lib.emp_label_overlap_accumulate(C.c_void_p(pa), abytes, C.c_void_p(pb), bbytes, n, _abi.ptr(self.buf),
-                                                             self.capacity, _abi.stream_ptr(self.device), C.byref(ov)),
-                       'emp_label_overlap_accumulate')
-            if not ov.value:
-                return
-            self._grow()      # the failed call has taken its own additions out again: count the slab once more
-
-    def cells(self):
-        """(keys, counts) on the device, sorted by key = a << 32 | b"""
-        num = C.c_int64(0)      # first call: the number of cells only, so that the buffers are as long as the result
-        _abi.check(self.lib.emp_label_overlap_finalize(_abi.ptr(self.buf), self.capacity, None, None, 0, C.byref(num),
-                                                       _abi.stream_ptr(self.device)), 'emp_label_overlap_finalize')
-        k = num.value
-        keys = torch.empty(max(k, 1), dtype=torch.int64, device=self.device)
-        cnt = torch.empty(max(k, 1), dtype=torch.int64, device=self.device)
-        _abi.check(self.lib.emp_label_overlap_finalize(_abi.ptr(self.buf), self.capacity, _abi.ptr(keys), _abi.ptr(cnt), k, C.byref(num),
-                                                       _abi.stream_ptr(self.device)), 'emp_label_overlap_finalize')
-        # the keys are unsigned: flip the sign bit so that the signed sort orders them
-        flip = torch.iinfo(torch.int64).min
-        skeys, order = torch.sort(keys[:k] ^ flip)
-        return skeys ^ flip, cnt[:k][order]
-
-
-# ----------------------------------------------------------------------------
-# sources: device tensors, host arrays, chunked stores
-# ----------------------------------------------------------------------------
-_EBYTES = {np.dtype(np.int8): -1, np.dtype(np.int16): -2, np.dtype(np.int32): -4, np.dtype(np.int64): -8,
-           np.dtype(np.uint8): 1, np.dtype(np.uint16): 2, np.dtype(np.uint32): 4, np.dtype(np.uint64): 8, np.dtype(np.bool_): 1}
-
-
-def _ebytes(dtype):
-    try:
-        return _EBYTES[np.dtype(str(dtype).replace('torch.', ''))]
-    except (KeyError, TypeError):
-        raise TypeError(f'label_overlap: dtype {dtype} is not an integer label type') from None
-
-
-class _DeviceSource:
-    """a tensor that is on the device already: slabs are views, nothing is copied"""
-
-    def __init__(self, t, device):
-        if t.device != device:
-            raise ValueError(f'label_overlap: tensor on {t.device}, table on {device}')
-        self.shape = tuple(t.shape)
-        self.ebytes = _ebytes(t.dtype)
-        self.t = t if t.is_contiguous() else t.contiguous()
-        self.rows = self.shape[0] if self.shape else 1
-        self.row_elems = int(np.prod(self.shape[1:], dtype=np.int64)) if self.shape else 1
-        self.row_bytes = self.row_elems * abs(self.ebytes)
-
-    def address(self, z0, z1, slot, stream):
-        return self.t.data_ptr() + z0 * self.row_bytes
-
-
-class _HostSource:
-    """a numpy array or a chunked store (zstore.DirArray, a zarr array): slabs of whole leading-axis slices go through two
-    pinned staging buffers and two device buffers; the upload of a slab is queued on a copy stream before the count of the
-    previous one is waited for"""
-
-    def __init__(self, x, device):
-        self.x = x
-        self.shape = tuple(int(s) for s in x.shape)
-        self.dtype = np.dtype(x.dtype)
-        self.ebytes = _ebytes(self.dtype)
-        self.device = device
-        self.rows = self.shape[0] if self.shape else 1
-        self.row_elems = int(np.prod(self.shape[1:], dtype=np.int64)) if self.shape else 1
-        self.row_bytes = self.row_elems * abs(self.ebytes)
-        self.events = [None, None]
-
-    def reserve(self, slab_rows, copy_stream):
-        nbytes = max(1, slab_rows * self.row_bytes)
-        self.pinned = [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(2)]
-        self.dev = [torch.empty(nbytes, dtype=torch.uint8, device=self.device) for _ in range(2)]
-        self.copy_stream = copy_stream
-
-    def stage(self, z0, z1, slot):
-        block = self.x[z0:z1] if self.shape else self.x
-        block = np.ascontiguousarray(np.asarray(block), dtype=self.dtype).reshape(-1)
-        nbytes = block.size * abs(self.ebytes)
-        self.pinned[slot][:nbytes].numpy()[:] = block.view(np.uint8)
-        with torch.cuda.stream(self.copy_stream):
-            self.dev[slot][:nbytes].copy_(self.pinned[slot][:nbytes], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(self.copy_stream)
-        self.events[slot] = ev
-
-    def address(self, z0, z1, slot, stream):
-        stream.wait_event(self.events[slot])
-        return self.dev[slot].data_ptr()
-
-
-def _source(x, device):
-    if isinstance(x, torch.Tensor):
-        if x.is_cuda:
-            return _DeviceSource(x, device)
-        x = x.numpy()
-    if not (hasattr(x, 'shape') and hasattr(x, 'dtype') and hasattr(x, '__getitem__')):
-        x = np.asarray(x)
-    return _HostSource(x, device)
-
-
 @torch.no_grad()
 def label_overlap(a, b, device=None, slab=None, capacity=None):
     """The contingency table of two label arrays of one shape (2-D or 3-D; any integer dtype of 1, 2, 4 or 8 bytes, values in
@@ -227,40 +74,17 @@ def label_overlap(a, b, device=None, slab=None, capacity=None):
     decoding dominates, the decode is the wall time.  The counts are integers: the result does not depend on ``slab`` and is bit-reproducible.  ``capacity``: first size of
     the device table in slots (default ``initial_capacity(n)``); the table doubles when it is too small.  A value outside
     [0, 2^32) raises ``EmpError``."""
-    if not torch.cuda.is_available():
-        raise RuntimeError('empanada_napari_amd needs a HIP device (MI355X); there is no CPU fallback')
-    _abi.load()
-    if device is None:
-        dev_in = [x.device for x in (a, b) if isinstance(x, torch.Tensor) and x.is_cuda]
-        device = dev_in[0] if dev_in else torch.device('cuda', torch.cuda.current_device())
-    device = torch.device(device)
-    if device.index is None:
-        device = torch.device('cuda', torch.cuda.current_device())
+    need_device()
+    device = pick_device(device, a, b)
     with torch.cuda.device(device):
-        sa, sb = _source(a, device), _source(b, device)
+        sa, sb = source(a, device), source(b, device)
         if sa.shape != sb.shape:
             raise ValueError('The shape of the prediction and ground truth images must match.')
-        rows = sa.rows
-        table = _Table(capacity or initial_capacity(rows * sa.row_elems), device)
-        host = [s for s in (sa, sb) if isinstance(s, _HostSource)]
-        if slab is None:
-            slab = rows if not host else max(1, SLAB_BYTES // max(1, max(s.row_bytes for s in host)))
-        slab = max(1, min(int(slab), max(rows, 1)))
-        stream = torch.cuda.current_stream(device)
-        if host:
-            copy_stream = torch.cuda.Stream(device=device)
-            for s in host:
-                s.reserve(slab, copy_stream)
-        bounds = [(z, min(rows, z + slab)) for z in range(0, rows, slab)]
-        if bounds:
-            for s in host:
-                s.stage(*bounds[0], 0)
-        for k, (z0, z1) in enumerate(bounds):
-            if k + 1 < len(bounds):
-                for s in host:
-                    s.stage(*bounds[k + 1], (k + 1) & 1)      # that slot's last slab was counted, and waited for, at step k - 1
-            table.add(sa.address(z0, z1, k & 1, stream), sa.ebytes, sb.address(z0, z1, k & 1, stream), sb.ebytes, (z1 - z0) * sa.row_elems)
-        keys, cnt = table.cells()
+        table = GrowableTable('emp_label_overlap', 'label_overlap', capacity or initial_capacity(sa.rows * sa.row_elems), device)
+        for _, z0, z1, (pa, pb) in stream_slabs((sa, sb), slab, device):
+            # n voxels at device addresses pa / pb (element sizes negative = signed)
+            table.add(pa, sa.ebytes, pb, sb.ebytes, (z1 - z0) * sa.row_elems)
+        keys, cnt = table.finalize()      # sorted by key = a << 32 | b
         keys = keys.cpu().numpy().view(np.uint64)
         cnt = cnt.cpu().numpy()
     av = (keys >> np.uint64(32)).astype(np.int64)
@@ -284,8 +108,8 @@ def _match(ov, index_space):
     rows, cols, inter = (np.zeros(m, np.int64) for _ in range(3))
     iou = np.zeros(m, np.float64)
     na, nb, nm = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-    _abi.check(lib.emp_overlap_match(k, _hp(a), _hp(b), _hp(c), int(index_space), _hp(al), _hp(aa), C.byref(na), _hp(bl), _hp(ba),
-                                     C.byref(nb), _hp(rows), _hp(cols), _hp(iou), _hp(inter), C.byref(nm)), 'emp_overlap_match')
+    _abi.check(lib.emp_overlap_match(k, hp(a), hp(b), hp(c), int(index_space), hp(al), hp(aa), C.byref(na), hp(bl), hp(ba),
+                                     C.byref(nb), hp(rows), hp(cols), hp(iou), hp(inter), C.byref(nm)), 'emp_overlap_match')
     na, nb, nm = na.value, nb.value, nm.value
     return al[:na], aa[:na], bl[:nb], ba[:nb], rows[:nm], cols[:nm], iou[:nm], inter[:nm]
 

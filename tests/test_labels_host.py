@@ -8,14 +8,15 @@ contract states it.
 * boundary_labels: four edges of an image, six faces of a volume, four edges per image in per-slice mode;
 * next_available_labels / next_available_label: the widget's queue (_merge_split_widget.py:730-759), a class that does not occur
   included;
-* label_bbox raises on an absent id as the widget does (:658-659)."""
+* label_bbox raises on an absent id as the widget does (:658-659);
+* slab_plan (empanada_napari_amd/_labelstream.py): the slab every streamed tool cuts its input into."""
 import os
 
 import numpy as np
 import pytest
 
 import labels_case as LC
-from empanada_napari_amd import labels as L
+from empanada_napari_amd import _labelstream as S, labels as L
 
 GOLD = dict(np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'labels.npz')))
 
@@ -183,6 +184,26 @@ def test_statements_of_the_boundary_modes_differ_where_they_should():
     whole, n_whole = LC.want_whole_label_border(img)
     assert n_whole == 1 and not (whole == 5).any() and whole[8, 2] == 6
     assert L.boundary_labels(_table(img)).tolist() == [5]
+
+
+@pytest.mark.parametrize('host_row_bytes, default', [(None, None), (1, S.SLAB_BYTES), (1 << 20, 64), (S.SLAB_BYTES + 1, 1)])
+def test_slab_plan(host_row_bytes, default):
+    """slab=None: everything at once without a host source (default None here), else SLAB_BYTES // row bytes, at least 1; the
+    slab is clamped to [1, max(rows, 1)]; the bounds tile [0, rows) in steps of the slab, none for rows == 0"""
+    assert S.SLAB_BYTES == 64 << 20
+    for rows in (0, 1, 5, 128):
+        for slab in (None, 1, 3, 128, 1000):
+            asked = slab if slab is not None else (rows if default is None else default)
+            want = max(1, min(asked, max(rows, 1)))
+            got, bounds = S.slab_plan(rows, host_row_bytes, slab)
+            assert got == want and type(got) is int, (rows, slab)
+            if rows == 0:
+                assert bounds == []
+                continue
+            assert bounds[0][0] == 0 and bounds[-1][1] == rows
+            assert all(a[1] == b[0] for a, b in zip(bounds, bounds[1:]))      # no gap, no overlap
+            assert all(z1 - z0 == want for z0, z1 in bounds[:-1]) and 0 < bounds[-1][1] - bounds[-1][0] <= want
+            assert S.slab_plan(rows, host_row_bytes, got) == (got, bounds)      # a plan made from its own slab is the same plan
 
 
 def test_no_cpu_fallback(monkeypatch):

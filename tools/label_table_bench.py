@@ -23,6 +23,7 @@ import __graft_entry__ as ge  # noqa: E402
 
 ge.load_package()
 from empanada_napari_amd import _abi, labels as L, metrics  # noqa: E402
+from empanada_napari_amd._labelstream import GrowableTable  # noqa: E402
 from overlap_bench import COPY_TBS, blob_labels, timed as overlap_timed  # noqa: E402
 
 
@@ -34,18 +35,18 @@ def _rate(nbytes, ms):
 
 def table_timed(a, reps, per_slice=False, capacity=None):
     D, H, W = a.shape
-    t = L._Table(capacity or metrics.initial_capacity(a.numel()), a.device)
+    t = GrowableTable('emp_label_table', 'label_table', capacity or metrics.initial_capacity(a.numel()), a.device)
     ms = []
     for i in range(reps + 2):
         _abi.check(t.lib.emp_label_table_reset(_abi.ptr(t.buf), t.capacity, _abi.stream_ptr(a.device)), 'reset')
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        t.add(a.data_ptr(), a.element_size(), 0, D, H, W, per_slice)
+        t.add(a.data_ptr(), a.element_size(), 0, D, H, W, int(per_slice))
         e1.record()
         torch.cuda.synchronize()
         if i >= 2:
             ms.append(e0.elapsed_time(e1))
-    keys, cnt, _ = t.rows()
+    keys, cnt, _ = (x.cpu().numpy() for x in t.finalize(extra=[(6, torch.int32)]))
     out = _rate(a.numel() * a.element_size(), ms)
     out.update({'distinct_keys': int(len(keys)), 'doublings': t.doublings})
     return out, keys, cnt

@@ -22,6 +22,7 @@ import __graft_entry__ as ge  # noqa: E402
 
 ge.load_package()
 from empanada_napari_amd import _abi, metrics  # noqa: E402
+from empanada_napari_amd._labelstream import GrowableTable  # noqa: E402
 
 COPY_TBS = 6.3
 
@@ -40,7 +41,7 @@ def blob_labels(shape, cell, seed):
 
 
 def timed(a, b, reps, capacity=None):
-    t = metrics._Table(capacity or metrics.initial_capacity(a.numel()), a.device)
+    t = GrowableTable('emp_label_overlap', 'label_overlap', capacity or metrics.initial_capacity(a.numel()), a.device)
     n, eb = a.numel(), a.element_size()
     ms = []
     for i in range(reps + 2):
@@ -52,7 +53,7 @@ def timed(a, b, reps, capacity=None):
         torch.cuda.synchronize()
         if i >= 2:
             ms.append(e0.elapsed_time(e1))
-    keys, _ = t.cells()
+    keys, _ = t.finalize()
     med = float(np.median(ms))
     return {'ms_median': round(med, 4), 'ms_min': round(min(ms), 4), 'ms_max': round(max(ms), 4), 'distinct_pairs': int(keys.numel()),
             'doublings': t.doublings, 'TB_per_s': round(2 * n * eb / med / 1e9, 3), 'fraction_of_copy_rate': round(2 * n * eb / med / 1e9 / COPY_TBS, 3)}
