@@ -157,6 +157,9 @@ PROTOTYPES = {
     'emp_label_table_finalize': (c_int, [vp, c_i64, vp, vp, vp, c_i64, C.POINTER(c_i64), vp]),
     'emp_label_map_build': (c_int, [vp, vp, c_i64, vp, vp, c_i64, vp]),
     'emp_label_apply_map': (c_int, [vp, c_int, vp, c_int, vp, c_i64, c_int, c_int, c_int, c_int, vp, vp, c_i64, vp]),
+    'emp_morph_tile_shape': (c_int, [c_int, c_int, c_int, C.POINTER(c_int), C.POINTER(c_int), C.POINTER(c_int)]),
+    'emp_morph_labels': (c_int, [vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp, c_i64, vp, vp, c_int, vp, c_i64, vp,
+                                 C.POINTER(c_int)]),
 }
 
 

@@ -12,6 +12,10 @@ On top of them, as pure numpy on a ``LabelTable`` (no device needed): ``small_la
 ``class_label_lists``, ``next_available_labels``, ``next_available_label``, ``label_bbox``; and the edits ``delete_labels``,
 ``merge_labels``, ``filter_out_small_label_areas``, ``remove_boundary_labels``.
 
+``morph_labels`` (csrc/morph.hip) is Morph Labels (_merge_split_widget.py:46-209): dilation, erosion, closing and opening of single
+labels with a disk or ball, every label inside its own padded box.  ``morph_schedule`` (pure numpy) orders the loop's turns into
+levels whose turns touch disjoint parts of the array; a level is two or three launches over the padded boxes of its turns.
+
 Inputs are those of ``metrics.label_overlap``: device tensors (read in place), numpy arrays and chunked stores
 (``zstore.DirArray``, zarr arrays) streamed in leading-axis slabs through pinned staging buffers.  An edit returns the kind of
 object it was given: a device tensor for a device tensor, a new numpy array for a numpy array (the caller's array is only written
@@ -38,7 +42,8 @@ from ._labelstream import GrowableTable, RawSource, ebytes, hp, initial_capacity
 
 __all__ = ['LabelTable', 'label_table', 'table_from_arrays', 'small_labels', 'boundary_labels', 'count_labels', 'class_label_lists',
            'next_available_labels', 'next_available_label', 'label_bbox', 'delete_labels', 'merge_labels',
-           'filter_out_small_label_areas', 'remove_boundary_labels']
+           'filter_out_small_label_areas', 'remove_boundary_labels', 'morph_labels', 'morph_schedule', 'morph_footprint_rows',
+           'morph_footprint_offsets']
 
 CCL_MAX_VOXELS = 1 << 30      # emp_ccl_range: D * H * W < 2^30
 CCL_MAX_LABEL = (1 << 31) - 2      # ... and labels below 2^31 - 1
@@ -468,3 +473,229 @@ def _as_ccl_input(t, eb, shape):
     if abs(eb) == 2:
         return raw.view(torch.int16).to(torch.int32) & 0xffff if eb > 0 else raw.view(torch.int16).to(torch.int32)
     return (raw if eb > 0 else raw.view(torch.int8)).to(torch.int32)
+
+
+# ----------------------------------------------------------------------------
+# Morph Labels
+# ----------------------------------------------------------------------------
+MORPH_OPS = {'Dilate': 0, 'Erode': 1, 'Close': 2, 'Open': 3}      # the widget's strings (_merge_split_widget.py:48-53) -> EMP_MORPH_*
+MORPH_MAX_RADIUS = 7      # the widget's slider (:73)
+_MORPH_GROWS = ('Dilate', 'Close')
+
+
+def _morph_args(operation, radius, what):
+    if operation not in MORPH_OPS:
+        raise ValueError(f"{what}: operation must be one of {list(MORPH_OPS)}, got {operation!r} ('Fill holes' is not built)")
+    if isinstance(radius, bool) or int(radius) != radius or not 1 <= int(radius) <= MORPH_MAX_RADIUS:
+        raise ValueError(f'{what}: radius must be an integer in 1..{MORPH_MAX_RADIUS}, got {radius!r}')
+    return int(radius)
+
+
+def morph_footprint_rows(radius, ball):
+    """The footprint as the kernel walks it: rows (dz, dy, h) of ``disk(radius)`` (``ball`` false: dz = 0 only) or
+    ``ball(radius)``, each the x-interval [-h, h] with h = floor(sqrt(r^2 - dy^2 - dz^2)) in integers."""
+    r = _morph_args('Dilate', radius, 'morph_footprint_rows')
+    rows = []
+    for dz in (range(-r, r + 1) if ball else (0,)):
+        for dy in range(-r, r + 1):
+            rem = r * r - dz * dz - dy * dy
+            if rem < 0:
+                continue
+            h = 0
+            while (h + 1) * (h + 1) <= rem:
+                h += 1
+            rows.append((dz, dy, h))
+    return np.asarray(rows, dtype=np.int64).reshape(-1, 3)
+
+
+def morph_footprint_offsets(radius, ndim):
+    """the offsets (k, ndim) of ``disk(radius)`` (ndim 2) / ``ball(radius)`` (ndim 3), sorted: ``morph_footprint_rows`` expanded"""
+    if ndim not in (2, 3):
+        raise ValueError('morph_footprint_offsets: ndim 2 (disk) or 3 (ball)')
+    offs = [(dz, dy, dx) for dz, dy, h in morph_footprint_rows(radius, ndim == 3).tolist() for dx in range(-h, h + 1)]
+    offs = np.asarray(sorted(offs), dtype=np.int64).reshape(-1, 3)
+    return offs if ndim == 3 else offs[:, 1:]
+
+
+def _morph_turns(table, turns, radius, operation):
+    """(ids, rows, lo, hi): per turn its label, its row of the table (-1: the id does not occur) and the box that holds the
+    label's voxels when the turn comes (exclusive upper ends, not clipped): the table's box, grown by the radius for every
+    earlier turn of the same id where the operation can grow a label."""
+    if table.per_slice:
+        raise ValueError('morph_schedule: a whole-array table is needed')
+    ids = np.asarray(turns, dtype=np.int64).reshape(-1)
+    nd = table.boxes.shape[1] // 2
+    rows = np.full(len(ids), -1, np.int64)
+    if len(table.labels):
+        pos = np.minimum(np.searchsorted(table.labels, ids), len(table.labels) - 1)
+        rows = np.where((ids > 0) & (table.labels[pos] == ids), pos, -1)
+    lo = np.zeros((len(ids), nd), np.int64)
+    hi = np.zeros((len(ids), nd), np.int64)
+    earlier = {}
+    for i, (l, row) in enumerate(zip(ids.tolist(), rows.tolist())):
+        if row < 0:
+            continue
+        k = earlier.get(l, 0)
+        earlier[l] = k + 1
+        grow = radius * k if operation in _MORPH_GROWS else 0
+        lo[i] = table.boxes[row, :nd] - grow
+        hi[i] = table.boxes[row, nd:] + grow
+    return ids, rows, lo, hi
+
+
+def morph_schedule(table, turns, radius, operation):
+    """The loop of Morph Labels over ``turns`` (label ids in the loop's order, a repeat being a second turn) as levels: a list
+    of lists of turn indices.  The turns of a level can run in any order or at once, the levels in order, with the result of
+    the sequential loop (_merge_split_widget.py:123-134).  Ids that do not occur in ``table`` are in no level.
+
+    ``Erode`` / ``Open`` never leave a label's own voxels: every label is independent of every other, and everything is one
+    level -- but for a repeated id, whose turns follow each other.  ``Dilate`` / ``Close`` write into the box padded by the
+    radius: two turns conflict when their padded boxes intersect, and a turn's level is 1 + the highest level of an earlier
+    turn it conflicts with.  A turn's box is the ``LabelTable``'s; a repeated id's later turns take it grown by the radius per
+    earlier turn, which is where that label can have got to by then."""
+    radius = _morph_args(operation, radius, 'morph_schedule')
+    ids, rows, lo, hi = _morph_turns(table, turns, radius, operation)
+    grows = operation in _MORPH_GROWS
+    level = np.zeros(len(ids), np.int64)      # 0: in no level
+    plo, phi = lo - radius, hi + radius
+    for i in range(len(ids)):
+        if rows[i] < 0:
+            continue
+        if grows:
+            hit = (rows[:i] >= 0) & (plo[:i] < phi[i]).all(axis=1) & (plo[i] < phi[:i]).all(axis=1)
+        else:
+            hit = ids[:i] == ids[i]
+        level[i] = 1 + (level[:i][hit].max() if hit.any() else 0)
+    return [np.flatnonzero(level == l).tolist() for l in range(1, int(level.max()) + 1 if len(level) else 1)]
+
+
+def _morph_tiles(table, turns, radius, operation, ball, levels, core):
+    """(tiles (n, 4) int32 {turn, z0, y0, x0}, level offsets (len(levels) + 1) int64, boxes (turns, 6) uint32): the tile lists
+    of emp_morph_labels.  A turn's tiles cover the box its label can lie in, padded by the radius and clipped to the array."""
+    ids, rows, lo, hi = _morph_turns(table, turns, radius, operation)
+    nd = lo.shape[1]
+    shape = np.asarray((1,) * (3 - nd) + tuple(table.shape), np.int64)
+    pad = np.asarray([radius if (ball or a > 0) else 0 for a in range(3)], np.int64)
+    boxes = np.zeros((len(ids), 6), np.uint32)
+    boxes[:, :3] = 0xffffffff
+    tiles, offsets, n = [], [0], 0
+    for k, lvl in enumerate(levels):
+        for i in lvl:
+            l3 = np.concatenate([np.zeros(3 - nd, np.int64), lo[i]])
+            h3 = np.concatenate([np.ones(3 - nd, np.int64), hi[i]])
+            if k == 0:      # nothing has been written yet: the table's box is the label's box
+                boxes[i, :3], boxes[i, 3:] = l3, h3 - 1
+            a = np.maximum(l3 - pad, 0)
+            b = np.minimum(h3 + pad, shape)
+            grid = np.meshgrid(*[np.arange(a[d], b[d], core[d]) for d in range(3)], indexing='ij')
+            tiles.append(np.stack([np.full(grid[0].size, i, np.int64)] + [g.reshape(-1) for g in grid], axis=1))
+            n += grid[0].size
+        offsets.append(n)
+    tiles = np.concatenate(tiles).astype(np.int32) if tiles else np.zeros((0, 4), np.int32)
+    return np.ascontiguousarray(tiles), np.asarray(offsets, np.int64), boxes
+
+
+def _morph_device(t, eb, shape, operation, radius, ball, ids, device, events=False):
+    """Morph Labels in place on the contiguous device buffer ``t`` (element size ``eb``, a 2-D or 3-D ``shape``) -> statistics:
+    turns, levels, tiles, launches and, with ``events``, a pair of HIP events around the launches (for tools/morph_labels_bench.py)"""
+    lib = _abi.load()
+    table = _table_of_source(RawSource(t, eb, shape), shape, False, device, None, None)
+    if ids is None:
+        turns = table.labels[table.labels != 0]
+    else:
+        turns = np.asarray(ids, dtype=np.int64).reshape(-1)
+        turns = turns[turns > 0]
+    levels = morph_schedule(table, turns, radius, operation)
+    op = MORPH_OPS[operation]
+    cz, cy, cx = C.c_int(0), C.c_int(0), C.c_int(0)
+    _abi.check(lib.emp_morph_tile_shape(radius, int(ball), op, C.byref(cz), C.byref(cy), C.byref(cx)), 'emp_morph_tile_shape')
+    tiles, offsets, boxes = _morph_tiles(table, turns, radius, operation, ball, levels, (cz.value, cy.value, cx.value))
+    stats = {'turns': int(len(turns)), 'turns_scheduled': int(sum(len(l) for l in levels)), 'levels': len(levels), 'tiles': int(len(tiles)),
+             'launches': 0}
+    if len(tiles) == 0:
+        return stats
+    D, H, W = (1,) * (3 - len(shape)) + tuple(shape)
+    d_labels = torch.from_numpy(turns.astype(np.int64)).to(device)
+    d_boxes = torch.from_numpy(boxes.view(np.int32)).to(device)
+    d_tiles = torch.from_numpy(tiles).to(device)
+    words = int(np.diff(offsets).max()) * cz.value * cy.value
+    scratch = torch.empty(words, dtype=torch.int64, device=device)
+    launches = C.c_int(0)
+    if events:
+        stats['events'] = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        stats['events'][0].record()
+    _abi.check(lib.emp_morph_labels(C.c_void_p(t.data_ptr()), eb, D, H, W, radius, int(ball), op, _abi.ptr(d_labels), _abi.ptr(d_boxes),
+                                    len(turns), _abi.ptr(d_tiles), hp(offsets), len(levels), _abi.ptr(scratch), words,
+                                    _abi.stream_ptr(device), C.byref(launches)), 'emp_morph_labels')
+    if events:
+        stats['events'][1].record()
+    stats['launches'] = launches.value
+    return stats
+
+
+_RAW_DTYPE = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}      # an element of that size, whatever it means
+
+
+@torch.no_grad()
+def morph_labels(labels, operation, radius=1, apply3d=False, ids=None, plane=None, axis=0, device=None, out=None, inplace=False):
+    """Morph Labels (_merge_split_widget.py:46-209): ``operation`` -- 'Dilate', 'Erode', 'Close' (erode(dilate)) or 'Open'
+    (dilate(erode)), the widget's strings -- on single labels with ``disk(radius)`` / ``ball(radius)``, radius 1..7.
+
+    The loop (:123-134) runs over ``ids``: every non-zero label ascending with ``ids=None`` (no points layer, :101), otherwise
+    the ids given, in their order, a repeat being a second turn (the labels under the points, :113); zeros are dropped
+    (:117).  A turn takes the box of its label as the array is then, pads it by the radius and clips it to the array (:56-67);
+    inside that crop the label's voxels become 0, the mask ``crop == label`` goes through the operation, and the voxels of the
+    result become the label, whatever they were.  Dilation sees false outside the crop and erosion true
+    (``ndi.binary_dilation(structure=footprint)``, ``ndi.binary_erosion(structure=footprint, border_value=True)``: skimage's
+    documented behaviour restated, not pinned against skimage, which is not available here).
+
+    A 2-D array takes the disk (``apply3d`` is ignored, as the widget does, :97-98).  A 3-D array takes the ball with
+    ``apply3d=True``, or with ``plane=k`` the disk on the image ``take(labels, k, axis)``, all other planes untouched (:153-169,
+    without the reference's clipping of the image's box by the volume's shape).  A 3-D array with neither raises a
+    ``ValueError`` (the reference's branch for it compares an int with a list, :143, and cannot run).
+
+    Inputs and outputs are those of ``delete_labels``: a device tensor gives a device tensor (its own with ``inplace=True``), a
+    numpy array a new numpy array (its own with ``inplace=True``); ``out=`` is for chunked stores, and a chunked store raises a
+    ``ValueError``: the whole array must be on the device, a ball needs a halo across slabs.  Any integer dtype of 1-8 bytes,
+    labels in [0, 2^63).  The result is exact and bit-reproducible; there is no numpy fallback.
+
+    The one deliberate difference: a label that has no voxel left when its turn comes -- eaten by earlier dilations, or an id
+    that never occurred -- is skipped; the reference dies there with an ``IndexError`` (``[...][0]`` of an empty list, :125)."""
+    what = 'morph_labels'
+    radius = _morph_args(operation, radius, what)
+    if not isinstance(labels, torch.Tensor) and not _is_numpy(labels):
+        if hasattr(labels, 'shape') and hasattr(labels, 'dtype') and hasattr(labels, '__getitem__'):
+            raise ValueError(f'{what}: a chunked store is not supported: the whole array must be on the device (a ball needs a halo '
+                             'across slabs); load it as a numpy array')
+        raise TypeError(f'{what}: a device tensor or a numpy array, got {type(labels).__name__}')
+    shape = tuple(int(s) for s in labels.shape)
+    if len(shape) not in (2, 3):
+        raise ValueError(f'{what}: 2-D or 3-D label arrays, got shape {shape}')
+    ball = len(shape) == 3 and bool(apply3d)
+    if len(shape) == 3 and not ball:
+        if plane is None:
+            raise ValueError(f'{what}: a 3-D array needs apply3d=True (the ball) or plane=k (the disk on one image)')
+        if axis not in (0, 1, 2) or not 0 <= int(plane) < shape[axis]:
+            raise ValueError(f'{what}: plane {plane} of axis {axis} is not in an array of shape {shape}')
+    eb = ebytes(labels.dtype)
+    need_device()
+    device = pick_device(device, labels)
+    with torch.cuda.device(device):
+        target = _edit_target(labels, out, inplace, shape, labels.dtype, what)
+        on_device = isinstance(labels, torch.Tensor)
+        if on_device:
+            res = labels if inplace else labels.contiguous().clone()
+            t = res
+        else:
+            host = np.ascontiguousarray(labels)
+            t = torch.from_numpy(host.view(np.uint8).reshape(-1)).to(device)
+        if len(shape) == 3 and not ball:
+            vol = t.reshape(-1).view(torch.uint8).view(_RAW_DTYPE[abs(eb)]).reshape(shape)
+            img = vol.select(axis, int(plane)).contiguous()
+            _morph_device(img, eb, tuple(img.shape), operation, radius, False, ids, device)
+            vol.select(axis, int(plane)).copy_(img)
+        else:
+            _morph_device(t, eb, shape, operation, radius, ball, ids, device)
+        if on_device:
+            return res
+        return _write_back(target, 0, shape[0], t.cpu(), host.dtype, shape)

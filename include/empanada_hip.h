@@ -724,6 +724,48 @@ EMP_API int emp_label_apply_map(const void* d_key, int key_bytes, const void* d_
                                  int H, int W, int per_slice, const uint64_t* d_map_keys, const uint64_t* d_map_vals,
                                  int64_t map_capacity, void* stream);
 
+/* ------------------------------------------------------------------------
+ * 8. Morph Labels (csrc/morph.hip): binary dilation, erosion, closing and
+ *    opening of single labels with a disk / ball of radius 1..7, every label
+ *    inside its own padded box -- the plugin's Morph Labels
+ *    (empanada_napari/_merge_split_widget.py:46-209) without `Fill holes`.
+ *
+ *    skimage is not available where this library is built: binary_dilation
+ *    and binary_erosion are restated from their documented behaviour
+ *    (scipy.ndimage.binary_dilation(structure=footprint) and
+ *    scipy.ndimage.binary_erosion(structure=footprint, border_value=True);
+ *    disk / ball = x^2 + y^2 (+ z^2) <= r^2) and are NOT pinned against
+ *    skimage; the tests state the loop with scipy.
+ * ---------------------------------------------------------------------- */
+/* the ops of the widget's table (_merge_split_widget.py:48-53) */
+#define EMP_MORPH_DILATE 0
+#define EMP_MORPH_ERODE 1
+#define EMP_MORPH_CLOSE 2 /* erode(dilate) */
+#define EMP_MORPH_OPEN 3  /* dilate(erode) */
+/* The core (cz, cy, cx) of the tiles emp_morph_labels works on: cx = 64 - 2 * radius * stages (a mask row with its halo is one
+ * 64-bit word; stages: 2 for Close and Open), (cz, cy) = (1, 64) for the disk and (8, 16) for the ball (ball != 0,
+ * _merge_split_widget.py:92-95). */
+EMP_API int emp_morph_tile_shape(int radius, int ball, int op, int* cz, int* cy, int* cx);
+/* The loop over label_ids of _merge_split_widget.py:123-134, IN PLACE on d_vol (D, H, W; a 2-D image is D = 1, ball = 0;
+ * elem_bytes as in section 7), by levels: the turns (one label each) of a level must touch disjoint parts of the array -- their
+ * boxes, padded by the radius, do not intersect -- and levels run in order, so that the result is the sequential loop's.
+ *   d_turn_labels[t]   the label of turn t
+ *   d_turn_boxes[6 t]  {min z, y, x, max z, y, x} (inclusive) of the label when its turn comes: given for the turns of the first
+ *                      level (regionprops' bbox, :125); for later levels initialised to {2^32 - 1 x 3, 0 x 3} and computed here
+ *                      from the array as it is then.  A label without a voxel left is skipped (the reference raises an
+ *                      IndexError there, `[...][0]` of an empty list, :125).
+ *   d_tiles[4 i]       {turn, z0, y0, x0}: the first voxel of a tile's core; the cores of a turn's tiles are disjoint and cover
+ *                      the largest padded box (_pad_box, :56-67) the turn can have; level l owns the tiles
+ *                      [h_level_offsets[l], h_level_offsets[l + 1])
+ *   d_scratch          scratch_words uint64: cz * cy per tile of the largest level
+ * Per level: the boxes (not for the first level), the new masks into the scratch buffer (`binary = op(crop == label_id)`,
+ * :130-133; outside the crop is false for a dilation and true for an erosion), then the edit (`crop[binary_before] = 0`,
+ * `crop[binary] = label_id`, :132,134).  *h_launches = the number of kernel launches.  Does not synchronise. */
+EMP_API int emp_morph_labels(void* d_vol, int elem_bytes, int D, int H, int W, int radius, int ball, int op,
+                             const uint64_t* d_turn_labels, uint32_t* d_turn_boxes, int64_t n_turns, const int32_t* d_tiles,
+                             const int64_t* h_level_offsets, int n_levels, uint64_t* d_scratch, int64_t scratch_words, void* stream,
+                             int* h_launches);
+
 #ifdef __cplusplus
 }
 #endif
