@@ -160,6 +160,9 @@ PROTOTYPES = {
     'emp_morph_tile_shape': (c_int, [c_int, c_int, c_int, C.POINTER(c_int), C.POINTER(c_int), C.POINTER(c_int)]),
     'emp_morph_labels': (c_int, [vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp, c_i64, vp, vp, c_int, vp, c_i64, vp,
                                  C.POINTER(c_int)]),
+    'emp_fill_holes_tile_shape': (c_int, [c_int, C.POINTER(c_int), C.POINTER(c_int), C.POINTER(c_int)]),
+    'emp_fill_holes_labels': (c_int, [vp, c_int, c_int, c_int, c_int, c_int, c_int, c_i64, vp, vp, vp, c_i64, vp, vp, c_int, vp, vp, c_i64,
+                                      vp, C.POINTER(c_int)]),
 }
 
 

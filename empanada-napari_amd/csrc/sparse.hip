@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "common.h"
+#include "union_find.h"
 
 namespace emp {
 namespace {
@@ -71,31 +72,8 @@ typedef Img<int32_t, false> ImgPlain;
 // ---------------------------------------------------------------------------
 // connected components: lock-free union-find on linear pixel indices; a root is the smallest
 // index of its component, so ranking the roots in index order IS raster order of first pixels.
+// uf_load / uf_find / uf_union: union_find.h (shared with the background components of morph.hip)
 // ---------------------------------------------------------------------------
-// parent words are read past the per-CU L1 (agent-scope relaxed loads): other workgroups update them
-// with atomicMin while this one walks the tree
-__device__ __forceinline__ int uf_load(int* parent, int a) {
-  return __hip_atomic_load(&parent[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ int uf_find(int* parent, int a) {
-  int p = uf_load(parent, a);
-  while (p != a) {
-    a = p;
-    p = uf_load(parent, a);
-  }
-  return a;
-}
-__device__ __forceinline__ void uf_union(int* parent, int a, int b) {
-  while (true) {
-    a = uf_find(parent, a);
-    b = uf_find(parent, b);
-    if (a == b) return;
-    if (a < b) { int t = a; a = b; b = t; }   // a > b: hang the larger root under the smaller
-    int old = atomicMin(&parent[a], b);
-    if (old == a) return;
-    a = old;
-  }
-}
 
 template <class IM>
 __global__ void __launch_bounds__(256) ccl_init_kernel(const IM in, int* __restrict__ parent,

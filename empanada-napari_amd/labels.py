@@ -15,6 +15,8 @@ On top of them, as pure numpy on a ``LabelTable`` (no device needed): ``small_la
 ``morph_labels`` (csrc/morph.hip) is Morph Labels (_merge_split_widget.py:46-209): dilation, erosion, closing and opening of single
 labels with a disk or ball, every label inside its own padded box.  ``morph_schedule`` (pure numpy) orders the loop's turns into
 levels whose turns touch disjoint parts of the array; a level is two or three launches over the padded boxes of its turns.
+``fill_label_holes`` is the widget's fifth operation, 'Fill holes' (``remove_small_holes`` inside the same padded box): the 4- /
+6-connected components of the background of every crop, by union-find over the same levels and tile lists.
 
 Inputs are those of ``metrics.label_overlap``: device tensors (read in place), numpy arrays and chunked stores
 (``zstore.DirArray``, zarr arrays) streamed in leading-axis slabs through pinned staging buffers.  An edit returns the kind of
@@ -42,8 +44,8 @@ from ._labelstream import GrowableTable, RawSource, ebytes, hp, initial_capacity
 
 __all__ = ['LabelTable', 'label_table', 'table_from_arrays', 'small_labels', 'boundary_labels', 'count_labels', 'class_label_lists',
            'next_available_labels', 'next_available_label', 'label_bbox', 'delete_labels', 'merge_labels',
-           'filter_out_small_label_areas', 'remove_boundary_labels', 'morph_labels', 'morph_schedule', 'morph_footprint_rows',
-           'morph_footprint_offsets']
+           'filter_out_small_label_areas', 'remove_boundary_labels', 'morph_labels', 'fill_label_holes', 'morph_schedule',
+           'morph_footprint_rows', 'morph_footprint_offsets']
 
 CCL_MAX_VOXELS = 1 << 30      # emp_ccl_range: D * H * W < 2^30
 CCL_MAX_LABEL = (1 << 31) - 2      # ... and labels below 2^31 - 1
@@ -485,7 +487,7 @@ _MORPH_GROWS = ('Dilate', 'Close')
 
 def _morph_args(operation, radius, what):
     if operation not in MORPH_OPS:
-        raise ValueError(f"{what}: operation must be one of {list(MORPH_OPS)}, got {operation!r} ('Fill holes' is not built)")
+        raise ValueError(f"{what}: operation must be one of {list(MORPH_OPS)}, got {operation!r} ('Fill holes' is fill_label_holes)")
     if isinstance(radius, bool) or int(radius) != radius or not 1 <= int(radius) <= MORPH_MAX_RADIUS:
         raise ValueError(f'{what}: radius must be an integer in 1..{MORPH_MAX_RADIUS}, got {radius!r}')
     return int(radius)
@@ -570,14 +572,16 @@ def morph_schedule(table, turns, radius, operation):
 
 
 def _morph_tiles(table, turns, radius, operation, ball, levels, core):
-    """(tiles (n, 4) int32 {turn, z0, y0, x0}, level offsets (len(levels) + 1) int64, boxes (turns, 6) uint32): the tile lists
-    of emp_morph_labels.  A turn's tiles cover the box its label can lie in, padded by the radius and clipped to the array."""
+    """(tiles (n, 4) int32 {turn, z0, y0, x0}, level offsets (len(levels) + 1) int64, boxes (turns, 6) uint32, frames (turns, 6)
+    int64 {z0, y0, x0, nz, ny, nx}): the tile lists of emp_morph_labels / emp_fill_holes_labels.  A turn's tiles cover its frame:
+    the box its label can lie in, padded by the radius and clipped to the array."""
     ids, rows, lo, hi = _morph_turns(table, turns, radius, operation)
     nd = lo.shape[1]
     shape = np.asarray((1,) * (3 - nd) + tuple(table.shape), np.int64)
     pad = np.asarray([radius if (ball or a > 0) else 0 for a in range(3)], np.int64)
     boxes = np.zeros((len(ids), 6), np.uint32)
     boxes[:, :3] = 0xffffffff
+    frames = np.zeros((len(ids), 6), np.int64)
     tiles, offsets, n = [], [0], 0
     for k, lvl in enumerate(levels):
         for i in lvl:
@@ -587,18 +591,18 @@ def _morph_tiles(table, turns, radius, operation, ball, levels, core):
                 boxes[i, :3], boxes[i, 3:] = l3, h3 - 1
             a = np.maximum(l3 - pad, 0)
             b = np.minimum(h3 + pad, shape)
+            frames[i, :3], frames[i, 3:] = a, b - a
             grid = np.meshgrid(*[np.arange(a[d], b[d], core[d]) for d in range(3)], indexing='ij')
             tiles.append(np.stack([np.full(grid[0].size, i, np.int64)] + [g.reshape(-1) for g in grid], axis=1))
             n += grid[0].size
         offsets.append(n)
     tiles = np.concatenate(tiles).astype(np.int32) if tiles else np.zeros((0, 4), np.int32)
-    return np.ascontiguousarray(tiles), np.asarray(offsets, np.int64), boxes
+    return np.ascontiguousarray(tiles), np.asarray(offsets, np.int64), boxes, frames
 
 
-def _morph_device(t, eb, shape, operation, radius, ball, ids, device, events=False):
-    """Morph Labels in place on the contiguous device buffer ``t`` (element size ``eb``, a 2-D or 3-D ``shape``) -> statistics:
-    turns, levels, tiles, launches and, with ``events``, a pair of HIP events around the launches (for tools/morph_labels_bench.py)"""
-    lib = _abi.load()
+def _morph_plan(t, eb, shape, ids, radius, operation, ball, core, device):
+    """What a device loop over the labels of the contiguous buffer ``t`` starts from: the turns (``ids``, or every label
+    ascending), their levels under ``operation``'s scheduling rule, the tile lists for tiles of ``core`` and the statistics"""
     table = _table_of_source(RawSource(t, eb, shape), shape, False, device, None, None)
     if ids is None:
         turns = table.labels[table.labels != 0]
@@ -606,12 +610,32 @@ def _morph_device(t, eb, shape, operation, radius, ball, ids, device, events=Fal
         turns = np.asarray(ids, dtype=np.int64).reshape(-1)
         turns = turns[turns > 0]
     levels = morph_schedule(table, turns, radius, operation)
+    tiles, offsets, boxes, frames = _morph_tiles(table, turns, radius, operation, ball, levels, core)
+    stats = {'turns': int(len(turns)), 'turns_scheduled': int(sum(len(l) for l in levels)), 'levels': len(levels), 'tiles': int(len(tiles)),
+             'launches': 0}
+    return turns, levels, tiles, offsets, boxes, frames, stats
+
+
+def _timed_launches(stats, events, call):
+    """``call()`` launches the levels and returns the number of launches; with ``events`` a pair of HIP events around it"""
+    if events:
+        stats['events'] = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        stats['events'][0].record()
+    stats['launches'] = call()
+    if events:
+        stats['events'][1].record()
+    return stats
+
+
+def _morph_device(t, eb, shape, operation, radius, ball, ids, device, events=False):
+    """Morph Labels in place on the contiguous device buffer ``t`` (element size ``eb``, a 2-D or 3-D ``shape``) -> statistics:
+    turns, levels, tiles, launches and, with ``events``, a pair of HIP events around the launches (for tools/morph_labels_bench.py)"""
+    lib = _abi.load()
     op = MORPH_OPS[operation]
     cz, cy, cx = C.c_int(0), C.c_int(0), C.c_int(0)
     _abi.check(lib.emp_morph_tile_shape(radius, int(ball), op, C.byref(cz), C.byref(cy), C.byref(cx)), 'emp_morph_tile_shape')
-    tiles, offsets, boxes = _morph_tiles(table, turns, radius, operation, ball, levels, (cz.value, cy.value, cx.value))
-    stats = {'turns': int(len(turns)), 'turns_scheduled': int(sum(len(l) for l in levels)), 'levels': len(levels), 'tiles': int(len(tiles)),
-             'launches': 0}
+    turns, levels, tiles, offsets, boxes, _, stats = _morph_plan(t, eb, shape, ids, radius, operation, ball, (cz.value, cy.value, cx.value),
+                                                                 device)
     if len(tiles) == 0:
         return stats
     D, H, W = (1,) * (3 - len(shape)) + tuple(shape)
@@ -620,17 +644,60 @@ def _morph_device(t, eb, shape, operation, radius, ball, ids, device, events=Fal
     d_tiles = torch.from_numpy(tiles).to(device)
     words = int(np.diff(offsets).max()) * cz.value * cy.value
     scratch = torch.empty(words, dtype=torch.int64, device=device)
-    launches = C.c_int(0)
-    if events:
-        stats['events'] = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        stats['events'][0].record()
-    _abi.check(lib.emp_morph_labels(C.c_void_p(t.data_ptr()), eb, D, H, W, radius, int(ball), op, _abi.ptr(d_labels), _abi.ptr(d_boxes),
-                                    len(turns), _abi.ptr(d_tiles), hp(offsets), len(levels), _abi.ptr(scratch), words,
-                                    _abi.stream_ptr(device), C.byref(launches)), 'emp_morph_labels')
-    if events:
-        stats['events'][1].record()
-    stats['launches'] = launches.value
-    return stats
+
+    def call():
+        launches = C.c_int(0)
+        _abi.check(lib.emp_morph_labels(C.c_void_p(t.data_ptr()), eb, D, H, W, radius, int(ball), op, _abi.ptr(d_labels), _abi.ptr(d_boxes),
+                                        len(turns), _abi.ptr(d_tiles), hp(offsets), len(levels), _abi.ptr(scratch), words,
+                                        _abi.stream_ptr(device), C.byref(launches)), 'emp_morph_labels')
+        return launches.value
+    return _timed_launches(stats, events, call)
+
+
+FILL_MAX_HOLE_SIZE = (1 << 31) - 1      # no component can have more voxels: a level's boxes hold fewer (FILL_MAX_LEVEL_VOXELS)
+FILL_MAX_LEVEL_VOXELS = (1 << 31) - 1      # emp_fill_holes_labels: int32 entries of the parent / size arrays
+
+
+def _fill_device(t, eb, shape, radius, hole_size, ball, ids, device, events=False):
+    """Fill holes in place on the contiguous device buffer ``t`` -> the statistics of ``_morph_device`` and ``scratch_entries``.
+    A turn writes only inside its padded box and reads only ``== label``: the levels are those of a dilation.  The parent and
+    size arrays hold one entry per voxel of the frames (padded, clipped boxes) of the largest level, not of the array."""
+    lib = _abi.load()
+    cz, cy, cx = C.c_int(0), C.c_int(0), C.c_int(0)
+    _abi.check(lib.emp_fill_holes_tile_shape(int(ball), C.byref(cz), C.byref(cy), C.byref(cx)), 'emp_fill_holes_tile_shape')
+    turns, levels, tiles, offsets, boxes, frames, stats = _morph_plan(t, eb, shape, ids, radius, 'Dilate', ball,
+                                                                      (cz.value, cy.value, cx.value), device)
+    stats['scratch_entries'] = 0
+    if len(tiles) == 0:
+        return stats
+    # a turn's entries follow those of the turns before it in its level
+    placed = np.zeros((len(turns), 7), np.int64)
+    placed[:, :6] = frames
+    entries = 0
+    for k, lvl in enumerate(levels):
+        voxels = frames[lvl, 3:].prod(axis=1)
+        if int(voxels.sum()) >= FILL_MAX_LEVEL_VOXELS:
+            raise ValueError(f'fill_label_holes: the padded boxes of the turns of level {k} hold {int(voxels.sum())} voxels; a level '
+                             'must hold fewer than 2^31 - 1 (pass fewer or smaller labels as ids=)')
+        placed[lvl, 6] = np.cumsum(voxels) - voxels
+        entries = max(entries, int(voxels.sum()))
+    stats['scratch_entries'] = entries
+    D, H, W = (1,) * (3 - len(shape)) + tuple(shape)
+    d_labels = torch.from_numpy(turns.astype(np.int64)).to(device)
+    d_boxes = torch.from_numpy(boxes.view(np.int32)).to(device)
+    d_frames = torch.from_numpy(placed).to(device)
+    d_tiles = torch.from_numpy(tiles).to(device)
+    parent = torch.empty(entries, dtype=torch.int32, device=device)
+    size = torch.empty(entries, dtype=torch.int32, device=device)
+
+    def call():
+        launches = C.c_int(0)
+        _abi.check(lib.emp_fill_holes_labels(C.c_void_p(t.data_ptr()), eb, D, H, W, radius, int(ball), hole_size, _abi.ptr(d_labels),
+                                             _abi.ptr(d_boxes), _abi.ptr(d_frames), len(turns), _abi.ptr(d_tiles), hp(offsets), len(levels),
+                                             _abi.ptr(parent), _abi.ptr(size), entries, _abi.stream_ptr(device), C.byref(launches)),
+                   'emp_fill_holes_labels')
+        return launches.value
+    return _timed_launches(stats, events, call)
 
 
 _RAW_DTYPE = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}      # an element of that size, whatever it means
@@ -663,6 +730,14 @@ def morph_labels(labels, operation, radius=1, apply3d=False, ids=None, plane=Non
     that never occurred -- is skipped; the reference dies there with an ``IndexError`` (``[...][0]`` of an empty list, :125)."""
     what = 'morph_labels'
     radius = _morph_args(operation, radius, what)
+    return _morph_call(labels, what, lambda t, eb, shape, ball, device: _morph_device(t, eb, shape, operation, radius, ball, ids, device),
+                       apply3d, plane, axis, device, out, inplace)
+
+
+def _morph_call(labels, what, run, apply3d, plane, axis, device, out, inplace):
+    """The inputs and outputs of ``morph_labels`` and ``fill_label_holes``: every check of the array, ``apply3d`` / ``plane`` /
+    ``axis`` and ``out`` / ``inplace``, the way to the device and back, and in between ``run(t, eb, shape, ball, device)`` on the
+    contiguous device buffer ``t`` -- the whole array, or the image ``take(labels, plane, axis)``"""
     if not isinstance(labels, torch.Tensor) and not _is_numpy(labels):
         if hasattr(labels, 'shape') and hasattr(labels, 'dtype') and hasattr(labels, '__getitem__'):
             raise ValueError(f'{what}: a chunked store is not supported: the whole array must be on the device (a ball needs a halo '
@@ -692,10 +767,44 @@ def morph_labels(labels, operation, radius=1, apply3d=False, ids=None, plane=Non
         if len(shape) == 3 and not ball:
             vol = t.reshape(-1).view(torch.uint8).view(_RAW_DTYPE[abs(eb)]).reshape(shape)
             img = vol.select(axis, int(plane)).contiguous()
-            _morph_device(img, eb, tuple(img.shape), operation, radius, False, ids, device)
+            run(img, eb, tuple(img.shape), False, device)
             vol.select(axis, int(plane)).copy_(img)
         else:
-            _morph_device(t, eb, shape, operation, radius, ball, ids, device)
+            run(t, eb, shape, ball, device)
         if on_device:
             return res
         return _write_back(target, 0, shape[0], t.cpu(), host.dtype, shape)
+
+
+@torch.no_grad()
+def fill_label_holes(labels, hole_size=64, radius=1, apply3d=False, ids=None, plane=None, axis=0, device=None, out=None, inplace=False):
+    """Morph Labels' fifth operation, 'Fill holes' (_merge_split_widget.py:53, :90-91), on single labels:
+    ``skimage.morphology.remove_small_holes(crop == label, hole_size)`` inside the label's padded box.
+
+    The loop, ``ids``, the crop -- the label's box as the array is when its turn comes, padded by ``radius`` (1..7; the widget's
+    slider applies to every operation, :56-67) and clipped -- ``apply3d`` / ``plane`` / ``axis``, the inputs and outputs and the
+    dtypes are those of ``morph_labels``; chunked stores and 4-D arrays are refused in the same way.  A turn (:123-134): the
+    complement of ``crop == label`` INSIDE THE CROP is split into its components of connectivity 1 (4 neighbours in an image, 6
+    in a volume: no diagonals), and every voxel of a component with fewer than ``hole_size`` voxels (``<``) becomes the label.
+    So voxels of other labels inside a small component are overwritten (a label that disappears that way has its own turn
+    skipped, as in ``morph_labels``); a component that touches the crop's border is a component like any other -- this is not
+    ``binary_fill_holes`` -- and when the background left around a label in its crop is smaller than ``hole_size`` the whole
+    crop becomes the label; and the result depends on the crop: voxels outside it are in no component.
+
+    ``hole_size``: an integer >= 0 (the widget's default is 64); 0 and 1 change nothing, and nothing is launched.
+    ``remove_small_holes`` / ``remove_small_objects`` are restated from their source and, like the rest of Morph Labels, are not
+    pinned against skimage, which is not available here; the tests state the loop with ``scipy.ndimage.label``.
+
+    The work arrays are as large as the padded boxes of the turns that run together, not as the array; such a level whose boxes
+    hold 2^31 - 1 voxels or more raises a ``ValueError``.  The result is exact and bit-reproducible; there is no numpy fallback."""
+    what = 'fill_label_holes'
+    radius = _morph_args('Dilate', radius, what)
+    if isinstance(hole_size, bool) or not isinstance(hole_size, (int, float, np.integer, np.floating)) or int(hole_size) != hole_size \
+            or hole_size < 0:
+        raise ValueError(f'{what}: hole_size must be an integer >= 0, got {hole_size!r}')
+    hole_size = min(int(hole_size), FILL_MAX_HOLE_SIZE)
+
+    def run(t, eb, shape, ball, device):
+        if hole_size > 1:      # no component has fewer than 1 voxel
+            _fill_device(t, eb, shape, radius, hole_size, ball, ids, device)
+    return _morph_call(labels, what, run, apply3d, plane, axis, device, out, inplace)

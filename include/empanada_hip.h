@@ -728,7 +728,9 @@ EMP_API int emp_label_apply_map(const void* d_key, int key_bytes, const void* d_
  * 8. Morph Labels (csrc/morph.hip): binary dilation, erosion, closing and
  *    opening of single labels with a disk / ball of radius 1..7, every label
  *    inside its own padded box -- the plugin's Morph Labels
- *    (empanada_napari/_merge_split_widget.py:46-209) without `Fill holes`.
+ *    (empanada_napari/_merge_split_widget.py:46-209); its fifth operation,
+ *    `Fill holes` (remove_small_holes inside the same padded box), is
+ *    emp_fill_holes_labels at the end of this section.
  *
  *    skimage is not available where this library is built: binary_dilation
  *    and binary_erosion are restated from their documented behaviour
@@ -765,6 +767,30 @@ EMP_API int emp_morph_labels(void* d_vol, int elem_bytes, int D, int H, int W, i
                              const uint64_t* d_turn_labels, uint32_t* d_turn_boxes, int64_t n_turns, const int32_t* d_tiles,
                              const int64_t* h_level_offsets, int n_levels, uint64_t* d_scratch, int64_t scratch_words, void* stream,
                              int* h_launches);
+
+/* The core (cz, cy, cx) of the tiles emp_fill_holes_labels works on: (1, 64, 64) for an image and (8, 16, 64) for a volume
+ * (ball != 0); there is no halo. */
+EMP_API int emp_fill_holes_tile_shape(int ball, int* cz, int* cy, int* cx);
+/* The same loop with operation == 'Fill holes' (_merge_split_widget.py:53,90-91,123-134), IN PLACE on d_vol:
+ * `binary = remove_small_holes(crop == label_id, hole_size)`, `crop[binary] = label_id`, where crop is the label's box as the
+ * array is then, padded by the radius and clipped (the radius applies to every operation, :56-67; ball: pad along z as well).
+ * The complement of the mask INSIDE THE CROP is split into its components of connectivity 1 (4 neighbours in an image, 6 in a
+ * volume, no diagonals), and every voxel of a component with fewer than hole_size voxels (`<`) becomes the label, whatever it
+ * held; a component that touches the crop's border is a component like any other.  hole_size <= 1 changes nothing (no launch).
+ * Levels, d_turn_labels, d_turn_boxes, d_tiles (cores of emp_fill_holes_tile_shape) and h_level_offsets as in emp_morph_labels;
+ * the turns of a level write inside their padded boxes, so the levels are those of a dilation.
+ *   d_turn_frames[7 t]  {z0, y0, x0, nz, ny, nx, offset}: the box the host padded, clipped and covered with tiles for turn t --
+ *                       it holds the turn's crop -- and the turn's first entry in d_parent / d_size; a voxel's entry is offset +
+ *                       its linear position in the frame.  The frames of a level do not share entries; levels reuse them.
+ *   d_parent, d_size    scratch_entries int32 each (< 2^31 - 1): the voxels of the frames of the largest level
+ * Per level: the boxes (not for the first level), the parents of the background voxels, the unions with the x - 1, y - 1 and
+ * z - 1 neighbours (lock-free union-find, the root is the smallest entry), the component sizes (integer atomics: the result is
+ * bit-reproducible), then the edit.  *h_launches = the number of kernel launches.  Does not synchronise.
+ * remove_small_holes / remove_small_objects are restated from their source and are NOT pinned against skimage. */
+EMP_API int emp_fill_holes_labels(void* d_vol, int elem_bytes, int D, int H, int W, int radius, int ball, int64_t hole_size,
+                                  const uint64_t* d_turn_labels, uint32_t* d_turn_boxes, const int64_t* d_turn_frames,
+                                  int64_t n_turns, const int32_t* d_tiles, const int64_t* h_level_offsets, int n_levels,
+                                  int32_t* d_parent, int32_t* d_size, int64_t scratch_entries, void* stream, int* h_launches);
 
 #ifdef __cplusplus
 }

@@ -1,11 +1,14 @@
 """Clean up a label volume on the device and print one JSON object: the plugin's Filter Small Labels, Delete Labels, Merge Labels,
 Count Labels and Morph Labels on a file.
 Usage: python tools/clean_labels.py IN [OUT] [--min-area N | --boundary [--whole-labels] | --delete IDS | --merge IDS [--into ID] |
-                                             --count --label-divisor D | --morph OP [--radius R] [--3d]] [--per-slice]
+                                             --count --label-divisor D | --morph OP [--radius R] [--3d] |
+                                             --fill-holes [HOLE_SIZE] [--radius R] [--3d]] [--per-slice]
 IN / OUT: .npy files (IN is memory-mapped and streamed in slabs, OUT is created) or zarr array directories (OUT is created with
 IN's shape, dtype and chunks).  IDS: comma-separated label ids.  --count needs no OUT.  --morph OP: Dilate, Erode, Close or Open
 of every label with a disk of radius R (a 2-D IN) or, with --3d, a ball (a 3-D IN); IN must be a .npy file (the whole array goes
-to the device); labels_affected is the number of labels that had a turn."""
+to the device); labels_affected is the number of labels that had a turn.  --fill-holes [HOLE_SIZE]: Morph Labels' 'Fill holes' on
+every label: the holes of fewer than HOLE_SIZE voxels (default 64) inside the label's box padded by R; same rules and the same JSON
+line as --morph."""
 import argparse
 import json
 import os
@@ -53,8 +56,9 @@ def main(argv=None):
     op.add_argument('--merge', type=_ids)
     op.add_argument('--count', action='store_true')
     op.add_argument('--morph', choices=list(L.MORPH_OPS), metavar='OP')
-    ap.add_argument('--radius', type=int, default=1, help='--morph: radius of the disk / ball, 1..7')
-    ap.add_argument('--3d', dest='apply3d', action='store_true', help='--morph: the ball on a 3-D array')
+    op.add_argument('--fill-holes', type=int, nargs='?', const=64, default=None, metavar='HOLE_SIZE')
+    ap.add_argument('--radius', type=int, default=1, help='--morph: radius of the disk / ball, 1..7; --fill-holes: the padding of the box')
+    ap.add_argument('--3d', dest='apply3d', action='store_true', help='--morph / --fill-holes: the ball / the volume\'s components on a 3-D array')
     ap.add_argument('--whole-labels', action='store_true')
     ap.add_argument('--into', type=int, default=None, help='--merge: the id the others become (default: the smallest)')
     ap.add_argument('--label-divisor', type=int, default=0)
@@ -81,9 +85,12 @@ def main(argv=None):
             res = fn(src, *a, out=dst, **k)
         return res[1] if isinstance(res, tuple) else None
 
-    if args.morph is not None:
+    if args.morph is not None or args.fill_holes is not None:
         n = len(np.unique(src)) - int((np.asarray(src) == 0).any())
-        run(L.morph_labels, args.morph, radius=args.radius, apply3d=args.apply3d)
+        if args.morph is not None:
+            run(L.morph_labels, args.morph, radius=args.radius, apply3d=args.apply3d)
+        else:
+            run(L.fill_label_holes, hole_size=args.fill_holes, radius=args.radius, apply3d=args.apply3d)
     elif args.min_area is not None:
         n = run(L.filter_out_small_label_areas, args.min_area, per_slice=args.per_slice)
     elif args.boundary:
