@@ -88,6 +88,18 @@ PROTOTYPES = {
     'emp_sepconvp_ws_nhwc_f16': (c_int, [vp, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp, vp, c_int, c_int, vp,
                                          c_int, vp, vp, c_int, vp, vp]),
     'emp_sepconv3x3_nhwc_f16': (c_int, [vp, c_int, c_int, c_int, c_int, c_int, vp, vp, vp, c_int, c_int, vp, c_int, vp]),
+    'emp_pr_upsample2x_keys': (c_int, [vp, c_int, c_int, c_int, c_int, vp, vp, vp]),
+    'emp_pr_topk_work_bytes': (c_int, [c_int, c_i64, C.POINTER(sz)]),
+    'emp_pr_topk_smallest': (c_int, [vp, c_int, c_i64, c_int, vp, sz, vp, vp]),
+    'emp_pr_point_features_f16': (c_int, [vp, c_int, c_int, c_int, c_int, c_int, vp, c_int, vp, c_int, c_int, c_int, vp, vp,
+                                          c_int, vp]),
+    'emp_pr_point_features_f32': (c_int, [vp, c_int, c_int, c_int, c_int, c_int, vp, c_int, vp, c_int, c_int, c_int, vp, vp,
+                                          c_int, vp]),
+    'emp_pr_point_head_supported': (c_int, [c_int, c_int, c_int, c_int]),
+    'emp_pr_point_head': (c_int, [vp, c_int, c_int, c_int, c_int, c_int, vp, c_int, vp, c_int, c_int, c_int, C.POINTER(vp),
+                                  C.POINTER(vp), c_int, c_int, vp, vp, vp, c_i64, vp]),
+    'emp_head1x1_scatter_f16': (c_int, [vp, c_int, c_int, c_int, c_int, vp, vp, c_int, vp, c_i64, vp, vp]),
+    'emp_head1x1_scatter_f32': (c_int, [vp, c_int, c_int, c_int, c_int, vp, vp, c_int, vp, c_i64, vp, vp]),
     'emp_sm_create': (vp, [c_i64, c_i64, c_f64, c_f64, c_int]),
     'emp_sm_destroy': (None, [vp]),
     'emp_sm_push_slice_runs': (c_int, [vp, vp, c_i64, c_i64, c_i64]),

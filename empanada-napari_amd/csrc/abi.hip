@@ -388,4 +388,81 @@ int emp_sepconv3x3_nhwc_f16(const void* d_in, int N, int H, int W, int C, int in
                          (hipStream_t)stream, 3);
 }
 
+// ---- PointRend subdivision, operator by operator (pointrend.hip, ref32.hip, layers.hip): the launches of run() / run32() ----
+int emp_pr_upsample2x_keys(const float* d_in, int N, int C, int h, int w, float* d_out, uint32_t* d_keys, void* stream) {
+  EMP_REQUIRE(d_in && d_out && d_keys, "pr_upsample2x_keys: null pointer");
+  EMP_REQUIRE(N > 0 && C > 0 && h > 0 && w > 0 && (int64_t)N * 4 * h * w < (1ll << 31), "pr_upsample2x_keys: bad geometry");
+  return launch_upsample2x_keys(d_in, N, C, h, w, d_out, d_keys, (hipStream_t)stream);
+}
+
+int emp_pr_topk_work_bytes(int N, int64_t plane, size_t* h_bytes) {
+  EMP_REQUIRE(h_bytes && N > 0 && plane > 0, "pr_topk_work_bytes: bad argument");
+  *h_bytes = topk_work_bytes(N, plane);
+  return EMP_OK;
+}
+
+int emp_pr_topk_smallest(const uint32_t* d_keys, int N, int64_t plane, int k, void* d_work, size_t work_bytes, int32_t* d_idx,
+                         void* stream) {
+  EMP_REQUIRE(d_keys && d_idx && N > 0, "pr_topk_smallest: bad argument");
+  EMP_REQUIRE(plane < (1ll << 31) && (int64_t)N * k < (1ll << 31), "pr_topk_smallest: indices are int32");
+  EMP_REQUIRE(d_work || (int64_t)k >= plane, "pr_topk_smallest: null workspace");
+  return launch_topk_smallest(d_keys, N, plane, k, d_work, work_bytes, d_idx, (hipStream_t)stream);
+}
+
+int emp_pr_point_features_f16(const void* d_feat, int N, int fh, int fw, int C, int feat_ld, const float* d_coarse, int ncls,
+                              const int32_t* d_idx, int P, int H2, int W2, void* d_x0, void* d_x1, int ld, void* stream) {
+  EMP_REQUIRE(d_feat && d_coarse && d_idx && d_x0 && d_x1, "pr_point_features_f16: null pointer");
+  EMP_REQUIRE(N > 0 && fh > 0 && fw > 0 && P > 0 && H2 > 0 && W2 > 0 && ncls >= 1 && C > 0 && feat_ld >= C && feat_ld % 8 == 0,
+              "pr_point_features_f16: bad geometry");
+  EMP_REQUIRE(((uintptr_t)d_feat % 16) == 0 && ((uintptr_t)d_x0 % 16) == 0 && ((uintptr_t)d_x1 % 16) == 0,
+              "pr_point_features_f16: pointers must be 16-byte aligned");
+  return launch_point_features((const half_t*)d_feat, N, fh, fw, C, feat_ld, d_coarse, ncls, d_idx, P, H2, W2, (half_t*)d_x0,
+                               (half_t*)d_x1, ld, (hipStream_t)stream);
+}
+
+int emp_pr_point_features_f32(const float* d_feat, int N, int fh, int fw, int C, int feat_ld, const float* d_coarse, int ncls,
+                              const int32_t* d_idx, int P, int H2, int W2, float* d_x0, float* d_x1, int ld, void* stream) {
+  EMP_REQUIRE(d_feat && d_coarse && d_idx && d_x0 && d_x1, "pr_point_features_f32: null pointer");
+  EMP_REQUIRE(N > 0 && fh > 0 && fw > 0 && P > 0 && H2 > 0 && W2 > 0 && ncls >= 1 && C > 0 && feat_ld >= C && ld >= C + ncls,
+              "pr_point_features_f32: bad geometry");
+  return launch_point_features_f32(d_feat, N, fh, fw, C, feat_ld, d_coarse, ncls, d_idx, P, H2, W2, d_x0, d_x1, ld,
+                                   (hipStream_t)stream);
+}
+
+int emp_pr_point_head_supported(int C, int ld, int ncls, int num_fc) { return pr_mlp_supported(C, ld, ncls, num_fc) ? 1 : 0; }
+
+int emp_pr_point_head(const void* d_feat, int N, int fh, int fw, int C, int feat_ld, const float* d_coarse, int ncls,
+                      const int32_t* d_idx, int P, int H2, int W2, const void* const* h_fc_w, const float* const* h_fc_b, int num_fc,
+                      int ld, const float* d_pred_w, const float* d_pred_b, float* d_out, int64_t plane, void* stream) {
+  EMP_REQUIRE(d_feat && d_coarse && d_idx && h_fc_w && h_fc_b && d_pred_w && d_pred_b && d_out, "pr_point_head: null pointer");
+  EMP_REQUIRE(pr_mlp_supported(C, ld, ncls, num_fc), "pr_point_head: unsupported shape C=%d ld=%d ncls=%d num_fc=%d", C, ld, ncls, num_fc);
+  EMP_REQUIRE(N > 0 && fh > 0 && fw > 0 && P > 0 && H2 > 0 && W2 > 0 && feat_ld >= C && feat_ld % 8 == 0 && plane >= (int64_t)H2 * W2,
+              "pr_point_head: bad geometry");
+  EMP_REQUIRE(((uintptr_t)d_feat % 16) == 0 && ((uintptr_t)d_pred_w % 16) == 0, "pr_point_head: pointers must be 16-byte aligned");
+  const half_t* fw_[4];
+  for (int f = 0; f < num_fc; ++f) {
+    EMP_REQUIRE(h_fc_w[f] && h_fc_b[f] && ((uintptr_t)h_fc_w[f] % 16) == 0 && ((uintptr_t)h_fc_b[f] % 16) == 0,
+                "pr_point_head: fc layer %d: null or misaligned pointer", f);
+    fw_[f] = (const half_t*)h_fc_w[f];
+  }
+  return launch_pr_mlp((const half_t*)d_feat, N, fh, fw, C, feat_ld, d_coarse, ncls, d_idx, P, H2, W2, fw_, h_fc_b, num_fc, ld,
+                       d_pred_w, d_pred_b, d_out, plane, (hipStream_t)stream);
+}
+
+int emp_head1x1_scatter_f16(const void* d_in, int N, int P, int K, int in_ld, const float* d_w, const float* d_b, int C,
+                            float* d_out, int64_t plane, const int32_t* d_scatter_idx, void* stream) {
+  EMP_REQUIRE(d_in && d_w && d_b && d_out, "head1x1_scatter_f16: null pointer");
+  EMP_REQUIRE(N > 0 && P > 0 && C > 0 && in_ld >= K && in_ld % 8 == 0 && ((uintptr_t)d_in % 16) == 0 && ((uintptr_t)d_w % 16) == 0 &&
+                  (d_scatter_idx || plane >= P),
+              "head1x1_scatter_f16: bad geometry");
+  return launch_head1x1((const half_t*)d_in, N, P, K, in_ld, d_w, d_b, C, d_out, plane, d_scatter_idx, (hipStream_t)stream);
+}
+
+int emp_head1x1_scatter_f32(const float* d_in, int N, int P, int K, int in_ld, const float* d_w, const float* d_b, int C,
+                            float* d_out, int64_t plane, const int32_t* d_scatter_idx, void* stream) {
+  EMP_REQUIRE(d_in && d_w && d_b && d_out, "head1x1_scatter_f32: null pointer");
+  EMP_REQUIRE(N > 0 && P > 0 && C > 0 && K > 0 && in_ld >= K && (d_scatter_idx || plane >= P), "head1x1_scatter_f32: bad geometry");
+  return launch_head1x1_f32(d_in, N, P, K, in_ld, d_w, d_b, C, d_out, plane, d_scatter_idx, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -267,6 +267,19 @@ int launch_point_features(const half_t* feat, int N, int fh, int fw, int C, int 
                           int ncls, const int32_t* idx, int P, int H2, int W2, half_t* x0, half_t* x1, int ld,
                           hipStream_t s);
 
+// Position, in pixels of a map `size` wide, of the centre of cell i of a `grid`-wide PointRend grid: point_rend.py:131-135 (fp32):
+// coord = 0.5*step + step*i, step = 1/grid; point_sample: g = 2*coord - 1; grid_sample(align_corners=False): ((g+1)*size - 1)/2.
+// Every product and sum is rounded on its own, as torch rounds them: left to the compiler, a*b + c became an fma in one sampling
+// kernel and not in another, and with step or size not a power of two the fused point head then was no longer bit-identical
+// to the launches it replaces (FINDINGS 87).  The four sampling kernels (pointrend.hip, ref32.hip) all call this.
+__device__ __forceinline__ float pr_sample_pos(int i, int grid, int size) {
+#pragma clang fp contract(off)
+  const float step = 1.0f / (float)grid;
+  const float c = 0.5f * step + step * (float)i;
+  const float g = 2.0f * c - 1.0f;
+  return ((g + 1.f) * (float)size - 1.f) * 0.5f;
+}
+
 // fused point head: sampling + fc layers + predictor + scatter in one launch (pointrend.hip)
 bool pr_mlp_supported(int C, int ld, int ncls, int num_fc);
 int launch_pr_mlp(const half_t* feat, int N, int fh, int fw, int C, int feat_ld, const float* coarse, int ncls,

@@ -215,14 +215,7 @@ __global__ void __launch_bounds__(256) point_features_kernel(const half_t* __res
   const int n = (int)(pt / P);
   const int id = idx[pt];
   const int iy = id / W2, ix = id - iy * W2;
-  // point_rend.py:131-135 (fp32): coord = 0.5*step + step*index, step = 1/size
-  const float w_step = 1.0f / (float)W2, h_step = 1.0f / (float)H2;
-  const float cx = 0.5f * w_step + w_step * (float)ix;
-  const float cy = 0.5f * h_step + h_step * (float)iy;
-  // point_sample: grid = 2*coord - 1; grid_sample(align_corners=False): ((g+1)*size - 1)/2
-  const float gx = 2.0f * cx - 1.0f, gy = 2.0f * cy - 1.0f;
-  const float sx = ((gx + 1.f) * (float)fw - 1.f) * 0.5f;
-  const float sy = ((gy + 1.f) * (float)fh - 1.f) * 0.5f;
+  const float sx = pr_sample_pos(ix, W2, fw), sy = pr_sample_pos(iy, H2, fh);      // common.h: no fma contraction
   const float fx0 = floorf(sx), fy0 = floorf(sy);
   const int xa = (int)fx0, ya = (int)fy0, xb = xa + 1, yb = ya + 1;
   const float lx = sx - fx0, ly = sy - fy0;
@@ -333,14 +326,7 @@ __global__ void __launch_bounds__(512, 1) pr_mlp_kernel(const PrParams p) {
       const int id = live ? p.idx[pt] : 0;
       n = live ? (int)(pt / p.P) : 0;
       const int iy = id / p.W2, ix = id - iy * p.W2;
-      // point_rend.py:131-135 (fp32): coord = 0.5*step + step*index, step = 1/size; point_sample: grid = 2*coord - 1;
-      // grid_sample(align_corners=False): ((g+1)*size - 1)/2
-      const float w_step = 1.0f / (float)p.W2, h_step = 1.0f / (float)p.H2;
-      const float cx = 0.5f * w_step + w_step * (float)ix;
-      const float cy = 0.5f * h_step + h_step * (float)iy;
-      const float gx = 2.0f * cx - 1.0f, gy = 2.0f * cy - 1.0f;
-      const float sx = ((gx + 1.f) * (float)p.fw - 1.f) * 0.5f;
-      const float sy = ((gy + 1.f) * (float)p.fh - 1.f) * 0.5f;
+      const float sx = pr_sample_pos(ix, p.W2, p.fw), sy = pr_sample_pos(iy, p.H2, p.fh);      // common.h: no fma contraction
       const float fx0 = floorf(sx), fy0 = floorf(sy);
       xa = (int)fx0; ya = (int)fy0;
       const int xb = xa + 1, yb = ya + 1;

@@ -382,12 +382,7 @@ __global__ void __launch_bounds__(256) point_features32_kernel(const float* __re
   const int n = (int)(pt / P);
   const int id = idx[pt];
   const int iy = id / W2, ix = id - iy * W2;
-  const float w_step = 1.0f / (float)W2, h_step = 1.0f / (float)H2;
-  const float cx = 0.5f * w_step + w_step * (float)ix;
-  const float cy = 0.5f * h_step + h_step * (float)iy;
-  const float gx = 2.0f * cx - 1.0f, gy = 2.0f * cy - 1.0f;
-  const float sx = ((gx + 1.f) * (float)fw - 1.f) * 0.5f;
-  const float sy = ((gy + 1.f) * (float)fh - 1.f) * 0.5f;
+  const float sx = pr_sample_pos(ix, W2, fw), sy = pr_sample_pos(iy, H2, fh);      // common.h: no fma contraction
   const float fx0 = floorf(sx), fy0 = floorf(sy);
   const int xa = (int)fx0, ya = (int)fy0, xb = xa + 1, yb = ya + 1;
   const float lx = sx - fx0, ly = sy - fy0;
@@ -434,12 +429,7 @@ __global__ void __launch_bounds__(256) point_features32v_kernel(const float* __r
   const int n = (int)(pt / P);
   const int id = idx[pt];
   const int iy = id / W2, ix = id - iy * W2;
-  const float w_step = 1.0f / (float)W2, h_step = 1.0f / (float)H2;
-  const float cx = 0.5f * w_step + w_step * (float)ix;
-  const float cy = 0.5f * h_step + h_step * (float)iy;
-  const float gx = 2.0f * cx - 1.0f, gy = 2.0f * cy - 1.0f;
-  const float sx = ((gx + 1.f) * (float)fw - 1.f) * 0.5f;
-  const float sy = ((gy + 1.f) * (float)fh - 1.f) * 0.5f;
+  const float sx = pr_sample_pos(ix, W2, fw), sy = pr_sample_pos(iy, H2, fh);      // common.h: no fma contraction
   const float fx0 = floorf(sx), fy0 = floorf(sy);
   const int xa = (int)fx0, ya = (int)fy0, xb = xa + 1, yb = ya + 1;
   const float lx = sx - fx0, ly = sy - fy0;

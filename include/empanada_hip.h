@@ -391,6 +391,50 @@ EMP_API int emp_sepconvp_ws_nhwc_f16(const void* d_in, int N, int H, int W, int 
                         const float* d_head_w, const float* d_head_b, int head_c, float* d_head_out,
                         void* stream);
 
+/* PointRend subdivision, operator by operator (csrc/pointrend.hip; the launches emp_pdl_forward makes per render step,
+ * point_rend.py:241-269 eval branch).  Exported so that each kernel is tested against a plain reference on inputs the
+ * network does not produce (tests/test_gpu_pointrend_kernels.py).  Thin wrappers: no new kernel, nothing synchronises.
+ *
+ * emp_pr_upsample2x_keys: d_in (N,C,h,w) fp32 -> d_out (N,C,2h,2w) fp32, F.interpolate(scale_factor=2, bilinear,
+ *   align_corners=False), and d_keys (N,2h*2w) uint32: the fp32 bit pattern of |v| (C == 1) or top1 - top2 over the classes
+ *   (C > 1) of the up-sampled logits -- the negated uncertainty of point_rend.py:11-31, never negative.
+ * emp_pr_topk_smallest: per image the k cells with the smallest keys (fp32 bit patterns of non-negative values): every key
+ *   below the k-th smallest value and, among the cells equal to it, those with the lowest index.  d_idx (N,k) int32, order
+ *   unspecified.  k == plane returns every cell; k > plane, k <= 0 or work_bytes < emp_pr_topk_work_bytes is an error and
+ *   launches nothing.  The workspace needs no initialisation and may be reused by the next call on the same stream.
+ * emp_pr_point_features_f16 / _f32: point_sample (point_rend.py:33-60: grid_sample, bilinear, align_corners=False, zero
+ *   padding) of the NHWC feature map d_feat (N,fh,fw,feat_ld; C channels used) and of the NCHW coarse logits d_coarse
+ *   (N,ncls,fh,fw) fp32 at the centres of the cells d_idx (N,P) of an H2 x W2 grid (point_rend.py:131-135).  Row p of d_x0 is
+ *   [C features | ncls coarse | zeros up to ld]; row p of d_x1 receives the columns [C, ld) only (the MLP's second buffer).
+ *   f16: C % 8 == 0, ld % 8 == 0, C + 8 <= ld <= C + 256, ncls <= 8.
+ * emp_pr_point_head: sampling + num_fc x (1x1 conv + bias + ReLU, coarse logits re-attached) + predictor + scatter in one
+ *   launch, bit-identical to emp_pr_point_features_f16, num_fc x emp_conv2d_nhwc_f16 and emp_head1x1_scatter_f16.
+ *   h_fc_w[f] / h_fc_b[f]: HOST arrays of num_fc device pointers, (C, ld) fp16 weights whose columns [C + ncls, ld) are zero
+ *   and C fp32 biases; d_pred_w (ncls, ld) fp32, d_pred_b ncls fp32; d_out (N,ncls,plane) fp32, written at d_idx only.
+ *   emp_pr_point_head_supported returns 1 for the shapes it takes -- (C, ld) = (256, 320) or (128, 192), ncls 1..8,
+ *   num_fc 1..4 -- and 0 otherwise; emp_pr_point_head returns EMP_ERR_INVALID for the others.
+ * emp_head1x1_scatter_f16 / _f32: out[n, c, idx[n, p]] = sum_k in[n*P + p, k] * w[c, k] + b[c] for rows of fp16 (K % 8 == 0,
+ *   K <= 512) or fp32; d_w (C, K) fp32.  d_scatter_idx NULL: the row's own position p (plane >= P). */
+EMP_API int emp_pr_upsample2x_keys(const float* d_in, int N, int C, int h, int w, float* d_out, uint32_t* d_keys, void* stream);
+EMP_API int emp_pr_topk_work_bytes(int N, int64_t plane, size_t* h_bytes);
+EMP_API int emp_pr_topk_smallest(const uint32_t* d_keys, int N, int64_t plane, int k, void* d_work, size_t work_bytes,
+                                 int32_t* d_idx, void* stream);
+EMP_API int emp_pr_point_features_f16(const void* d_feat, int N, int fh, int fw, int C, int feat_ld, const float* d_coarse,
+                                      int ncls, const int32_t* d_idx, int P, int H2, int W2, void* d_x0, void* d_x1, int ld,
+                                      void* stream);
+EMP_API int emp_pr_point_features_f32(const float* d_feat, int N, int fh, int fw, int C, int feat_ld, const float* d_coarse,
+                                      int ncls, const int32_t* d_idx, int P, int H2, int W2, float* d_x0, float* d_x1, int ld,
+                                      void* stream);
+EMP_API int emp_pr_point_head_supported(int C, int ld, int ncls, int num_fc);
+EMP_API int emp_pr_point_head(const void* d_feat, int N, int fh, int fw, int C, int feat_ld, const float* d_coarse, int ncls,
+                              const int32_t* d_idx, int P, int H2, int W2, const void* const* h_fc_w,
+                              const float* const* h_fc_b, int num_fc, int ld, const float* d_pred_w, const float* d_pred_b,
+                              float* d_out, int64_t plane, void* stream);
+EMP_API int emp_head1x1_scatter_f16(const void* d_in, int N, int P, int K, int in_ld, const float* d_w, const float* d_b, int C,
+                                    float* d_out, int64_t plane, const int32_t* d_scatter_idx, void* stream);
+EMP_API int emp_head1x1_scatter_f32(const float* d_in, int N, int P, int K, int in_ld, const float* d_w, const float* d_b, int C,
+                                    float* d_out, int64_t plane, const int32_t* d_scatter_idx, void* stream);
+
 /* ------------------------------------------------------------------------
  * 3. Instance post-processing (hot loop 2), one launch group per batch
  * ---------------------------------------------------------------------- */
