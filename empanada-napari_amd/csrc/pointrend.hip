@@ -6,10 +6,12 @@
 //   coarse logits and of the decoder features (grid_sample, :33-60), a 3-layer
 //   point MLP (runs on the implicit-GEMM kernel as a 1x1 conv over the point
 //   list) and a scatter of the refined logits back into the grid.
-// Top-k is an exact 4-pass radix select on the fp32 bit pattern of a
-// non-negative key (smaller key = more uncertain) followed by an ORDERED
-// compaction, so the selected set is deterministic: all keys below the k-th
-// value, plus the lowest-index cells among those equal to it.
+// Top-k is an exact radix select on the fp32 bit pattern of a non-negative key
+// (smaller key = more uncertain) followed by an ORDERED compaction, so the
+// selected set is deterministic: all keys below the k-th value, plus the
+// lowest-index cells among those equal to it.  Two forms with the same output:
+// the two-read select (default, "Two-read select" below) and the four-pass
+// select that reads the keys six times (EMP_TOPK_LEGACY=1).
 #include "common.h"
 
 namespace emp {
@@ -193,6 +195,325 @@ __global__ void __launch_bounds__(256) compact_write_kernel(const uint32_t* __re
       if (pe < krem) o[nless + pe] = (int32_t)(e0 + j);
       ++pe;
     }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Two-read select (default; EMP_TOPK_LEGACY=1 takes the four-pass kernels above).  The keys are read twice, 16 bytes per lane:
+//   digit pass     per-image histogram of the SEL_BITS bits below the sign bit (bit 31 of a non-negative float is 0);
+//                  sel_find_kernel finds the threshold bin B, the count still to take from it and whether the bin fits the
+//                  candidate buffer (SEL_CAP keys);
+//   candidate pass keys whose digit is below B are selected outright: one bit per key in the `less` mask; keys in bin B set
+//                  their bit in the `eq` mask and go, with their index, to the image's candidate buffer; per-chunk counts of
+//                  both masks as in the legacy compaction;
+//   resolve        one workgroup per image: the exact 32-bit threshold T by bisection over the candidates in registers; the
+//                  candidates below T move to the `less` mask, those above T leave the `eq` mask (atomics on the few words and
+//                  chunk counts concerned), then the exclusive scan of the chunk counts;
+//   ordered write  compact_write_kernel's arithmetic on the two masks: the keys are not read again.
+// An image whose threshold bin holds more than SEL_CAP keys (a constant image: padding, a blank slice) sets its overflow
+// flag on the device and refines the threshold with two more histogram levels (bits 18..7, bits 6..0: launches whose
+// workgroups return at once for every other image); the candidate pass then compares such an image's keys with the exact
+// T and appends nothing: five reads, against the six of the legacy select.  No host synchronisation; a batch may mix both.
+// Alignment: an image's keys start s = (address / 4) & 3 elements past a 16-byte boundary.  Every pass indexes the image by
+// v = i + s, so that the group v / 4 is one aligned uint4; the groups that hold v < s or v >= plane + s are read by guarded
+// scalar loads.  Masks, chunk counts and candidate indices are in v; the ordered write subtracts s.
+// state[n] = {prefix / T, k remaining, overflow, candidates, unused x 4}
+// ---------------------------------------------------------------------------
+constexpr int SEL_BITS = 12;                       // width of the leading digit (bits 30..19)
+constexpr int SEL_CAP = 8192;                      // candidate keys per image
+constexpr int SEL_BINS = 1 << SEL_BITS;
+constexpr int SEL_SHIFT = 31 - SEL_BITS;           // 19
+constexpr int SEL_L2_BITS = 12, SEL_L2_SHIFT = SEL_SHIFT - SEL_L2_BITS;      // overflow level 2: bits 18..7
+constexpr int SEL_HIST_CHUNKS = 4;                 // chunks of CHUNK keys per workgroup of the histogram pass
+constexpr int SEL_STATE = 8;
+constexpr int SEL_WORDS = CHUNK / 32;              // mask words per chunk
+
+__device__ __forceinline__ uint32_t sel_shift_of(const uint32_t* kp) { return (uint32_t)(((uintptr_t)kp >> 2) & 3u); }
+
+// the four keys of group g (v = 4g .. 4g + 3) of an image; ok = bit j set where v is a key of the image
+__device__ __forceinline__ uint4 sel_load4(const uint32_t* __restrict__ kp, int64_t plane, uint32_t sh, int64_t g,
+                                           uint32_t* ok) {
+  const int64_t i0 = 4 * g - (int64_t)sh;
+  if (i0 >= 0 && i0 + 3 < plane) {
+    *ok = 15u;
+    return *reinterpret_cast<const uint4*>(kp + i0);
+  }
+  uint32_t k[4], m = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int64_t i = i0 + j;
+    const bool in = i >= 0 && i < plane;
+    k[j] = in ? kp[in ? i : 0] : 0u;
+    m |= (uint32_t)in << j;
+  }
+  *ok = m;
+  return make_uint4(k[0], k[1], k[2], k[3]);
+}
+
+__global__ void sel_init_kernel(uint32_t* __restrict__ state, uint32_t* __restrict__ hist, int N, uint32_t k) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < N * SEL_STATE) state[i] = (i % SEL_STATE) == 1 ? k : 0u;
+  if (i < N * SEL_BINS) hist[i] = 0;
+}
+
+// one workgroup per image: the bin that holds the k-th key; the histogram is left zeroed for the next level
+__global__ void __launch_bounds__(256) sel_find_kernel(uint32_t* __restrict__ hist, uint32_t* __restrict__ state, int level,
+                                                       int shift) {
+  __shared__ uint32_t sh[8];
+  const int n = blockIdx.x;
+  if (level > 0 && state[SEL_STATE * n + 2] == 0) return;
+  constexpr int PER = SEL_BINS / 256;
+  uint32_t c[PER], sum = 0;
+  uint32_t* h = hist + (size_t)n * SEL_BINS + threadIdx.x * PER;
+#pragma unroll
+  for (int j = 0; j < PER; ++j) {
+    c[j] = h[j];
+    h[j] = 0;
+    sum += c[j];
+  }
+  uint32_t total;
+  uint32_t ex = block_excl_scan(sum, sh, &total);
+  const uint32_t krem = state[SEL_STATE * n + 1];
+  const uint32_t prefix = state[SEL_STATE * n];
+  __syncthreads();
+  if (sum > 0 && ex < krem && krem <= ex + sum) {
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+      if (c[j] > 0 && ex < krem && krem <= ex + c[j]) {
+        state[SEL_STATE * n] = prefix | ((uint32_t)(threadIdx.x * PER + j) << shift);
+        state[SEL_STATE * n + 1] = krem - ex;
+        if (level == 0) state[SEL_STATE * n + 2] = c[j] > (uint32_t)SEL_CAP ? 1u : 0u;
+      }
+      ex += c[j];
+    }
+  }
+}
+
+// level 0: every image, digit = bits 30..19.  levels 1, 2: overflow images only, keys that match the prefix found so far.
+// [measured on the bench's keys, both stages of a step: plain LDS atomics, one per key, 45 us; electing one lane per
+// distinct bin of the wave (two rounds of ballot + broadcast) before the atomics, 61 us: the clustered keys do not serialise
+// enough to pay for the election.  Letting the image's last workgroup find the threshold bin (a ticket behind a
+// __threadfence(), to save the launches of sel_find_kernel): 573 us for the six launches of a step against 63 + 28 with the
+// separate kernel -- a device-scope release in each of 5 000 workgroups costs far more than three small launches]
+__global__ void __launch_bounds__(256) sel_hist_kernel(const uint32_t* __restrict__ keys, int64_t plane,
+                                                       const uint32_t* __restrict__ state, uint32_t* __restrict__ hist,
+                                                       int level, int shift, uint32_t binmask, uint32_t himask) {
+  __shared__ uint32_t lh[SEL_BINS];
+  const int n = blockIdx.y;
+  if (level > 0 && state[SEL_STATE * n + 2] == 0) return;
+  for (int i = threadIdx.x; i < SEL_BINS; i += 256) lh[i] = 0;
+  __syncthreads();
+  const uint32_t prefix = state[SEL_STATE * n];
+  const uint32_t* kp = keys + (size_t)n * plane;
+  const uint32_t sft = sel_shift_of(kp);
+  const int64_t groups = (plane + sft + 3) >> 2;
+  const int64_t gpb = (int64_t)SEL_HIST_CHUNKS * CHUNK / 4;        // groups per workgroup per round
+  for (int64_t gb = (int64_t)blockIdx.x * gpb; gb < groups; gb += (int64_t)gridDim.x * gpb) {
+#pragma unroll 1
+    for (int j0 = 0; j0 < SEL_HIST_CHUNKS * 2; j0 += 4) {
+      uint4 kv[4];
+      uint32_t ok[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int64_t g = gb + (int64_t)(j0 + u) * 256 + threadIdx.x;
+        ok[u] = 0;
+        kv[u] = make_uint4(0, 0, 0, 0);
+        if (g < groups) kv[u] = sel_load4(kp, plane, sft, g, &ok[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const uint32_t k4[4] = {kv[u].x, kv[u].y, kv[u].z, kv[u].w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (((ok[u] >> e) & 1u) && (k4[e] & himask) == prefix) atomicAdd(&lh[(k4[e] >> shift) & binmask], 1u);
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < SEL_BINS; i += 256) {
+    const uint32_t c = lh[i];
+    if (c) atomicAdd(&hist[(size_t)n * SEL_BINS + i], c);
+  }
+}
+
+// one chunk per WAVE (64 lanes x 8 aligned groups of 4 keys, all eight loads in flight at once; no LDS, no barrier): masks,
+// the chunk's counts (less | eq << 16) and, for an image that did not overflow, the candidates
+__global__ void __launch_bounds__(256) sel_cand_kernel(const uint32_t* __restrict__ keys, int64_t plane,
+                                                       uint32_t* __restrict__ state, uint32_t* __restrict__ blockcnt,
+                                                       uint32_t* __restrict__ lessm, uint32_t* __restrict__ eqm,
+                                                       uint32_t* __restrict__ cand, int nb) {
+  const int n = blockIdx.y;
+  const int lane = threadIdx.x & 63;
+  const int chunk = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (chunk >= nb) return;
+  const uint32_t T = state[SEL_STATE * n];
+  const bool over = state[SEL_STATE * n + 2] != 0;
+  const uint32_t lowmask = over ? 0xffffffffu : ~((1u << SEL_SHIFT) - 1u);      // exact compare / digit compare
+  const uint32_t* kp = keys + (size_t)n * plane;
+  const uint32_t sft = sel_shift_of(kp);
+  const int64_t groups = (plane + sft + 3) >> 2;
+  uint32_t* cbuf = cand + (size_t)n * SEL_CAP * 2;
+  constexpr int G = CHUNK / 256;                     // groups per lane
+  uint4 kv[G];
+  uint32_t ok[G];
+#pragma unroll
+  for (int j = 0; j < G; ++j) {
+    const int64_t g = (int64_t)chunk * (CHUNK / 4) + j * 64 + lane;
+    ok[j] = 0;
+    kv[j] = make_uint4(0, 0, 0, 0);
+    if (g < groups) kv[j] = sel_load4(kp, plane, sft, g, &ok[j]);
+  }
+  uint32_t cnt = 0;
+#pragma unroll
+  for (int j = 0; j < G; ++j) {
+    const int64_t g = (int64_t)chunk * (CHUNK / 4) + j * 64 + lane;
+    const uint32_t k4[4] = {kv[j].x, kv[j].y, kv[j].z, kv[j].w};
+    uint32_t fl = 0, fe = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const uint32_t d = k4[e] & lowmask;
+      fl |= (uint32_t)(d < T) << e;
+      fe |= (uint32_t)(d == T) << e;
+    }
+    fl &= ok[j];
+    fe &= ok[j];
+    cnt += (uint32_t)__popc(fl) | ((uint32_t)__popc(fe) << 16);
+    if (!over && __ballot(fe != 0) != 0) {             // rare: the threshold bin holds at most SEL_CAP keys of the image
+      const uint32_t c = (uint32_t)__popc(fe);
+      const uint32_t inc = wave_incl_scan(c, lane);
+      uint32_t base = 0;
+      if (lane == 63) base = atomicAdd(&state[SEL_STATE * n + 3], inc);
+      base = __shfl(base, 63);
+      uint32_t slot = base + inc - c;
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if ((fe >> e) & 1u) {
+          if (slot < (uint32_t)SEL_CAP) { cbuf[2 * slot] = k4[e]; cbuf[2 * slot + 1] = (uint32_t)(4 * g + e); }
+          ++slot;
+        }
+    }
+    // eight lanes' nibbles make one mask word
+    const int q = 4 * (lane & 7);
+    uint32_t wl = fl << q, we = fe << q;
+#pragma unroll
+    for (int o = 1; o < 8; o <<= 1) { wl |= __shfl_xor(wl, o); we |= __shfl_xor(we, o); }
+    if ((lane & 7) == 0) {
+      const size_t word = ((size_t)n * nb + chunk) * SEL_WORDS + j * 8 + (lane >> 3);
+      lessm[word] = wl;
+      eqm[word] = we;
+    }
+  }
+  // chunk total: both 16-bit fields stay below 2^16 (CHUNK = 2048)
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+  if (lane == 0) blockcnt[(size_t)n * nb + chunk] = cnt;
+}
+
+// one workgroup per image: exact threshold from the candidates, masks and chunk counts corrected, chunk counts scanned
+__global__ void __launch_bounds__(256) sel_resolve_kernel(uint32_t* __restrict__ state, uint32_t* __restrict__ blockcnt,
+                                                          uint32_t* __restrict__ blockoff, uint32_t* __restrict__ lessm,
+                                                          uint32_t* __restrict__ eqm, const uint32_t* __restrict__ cand,
+                                                          int nb) {
+  __shared__ uint32_t sh[8];
+  __shared__ uint32_t below[SEL_SHIFT + 1];
+  const int n = blockIdx.x;
+  const int lane = threadIdx.x & 63;
+  if (state[SEL_STATE * n + 2] == 0) {
+    constexpr int PER = SEL_CAP / 256;
+    const uint32_t ncand = min(state[SEL_STATE * n + 3], (uint32_t)SEL_CAP);
+    const int per = (int)((ncand + 255u) / 256u);           // rounds of 256 candidates that hold any: a handful on real keys
+    const uint32_t prefix = state[SEL_STATE * n], krem = state[SEL_STATE * n + 1];
+    const uint32_t* cbuf = cand + (size_t)n * SEL_CAP * 2;
+    uint32_t ck[PER], cv[PER];
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+      const uint32_t slot = j * 256 + threadIdx.x;
+      ck[j] = slot < ncand ? cbuf[2 * slot] : 0xffffffffu;      // key and index in one round trip
+      cv[j] = slot < ncand ? cbuf[2 * slot + 1] : 0u;
+    }
+    if (threadIdx.x <= SEL_SHIFT) below[threadIdx.x] = 0;
+    __syncthreads();
+    // T = the largest value with fewer than krem candidates below it = the krem-th smallest candidate
+    uint32_t T = prefix;
+    for (int bit = SEL_SHIFT - 1; bit >= -1; --bit) {
+      const uint32_t trial = bit >= 0 ? (T | (1u << bit)) : T;      // last round: the count below T itself
+      uint32_t c = 0;                                               // the wave's count: the same in every lane
+#pragma unroll
+      for (int j = 0; j < PER; ++j)
+        if (j < per) c += (uint32_t)__popcll((unsigned long long)__ballot(ck[j] < trial));
+      if (lane == 0 && c) atomicAdd(&below[bit + 1], c);
+      __syncthreads();
+      if (bit >= 0 && below[bit + 1] < krem) T = trial;
+    }
+    const uint32_t nbelow = below[0];
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+      const uint32_t slot = j * 256 + threadIdx.x;
+      if (slot < ncand && ck[j] != T) {
+        const uint32_t v = cv[j];
+        const size_t word = (size_t)n * nb * SEL_WORDS + (v >> 5);
+        const uint32_t bitm = 1u << (v & 31u);
+        atomicAnd(&eqm[word], ~bitm);
+        uint32_t delta = 0u - (1u << 16);                 // one key fewer in the eq field
+        if (ck[j] < T) { atomicOr(&lessm[word], bitm); delta += 1u; }
+        atomicAdd(&blockcnt[(size_t)n * nb + v / CHUNK], delta);
+      }
+    }
+    __syncthreads();                                       // every thread has read state and below[]
+    if (threadIdx.x == 0) { state[SEL_STATE * n] = T; state[SEL_STATE * n + 1] = krem - nbelow; }
+  }
+  // the corrections above and the loads below are atomics on the same words, issued by threads of this workgroup on either
+  // side of a barrier: no device-scope fence is needed (one here costs a write-back of the masks the pass before left in L2)
+  __syncthreads();
+  uint32_t carry_l = 0, carry_e = 0;
+  for (int b0 = 0; b0 < nb; b0 += 256) {
+    const int b = b0 + threadIdx.x;
+    const uint32_t c = b < nb ? __hip_atomic_load(&blockcnt[(size_t)n * nb + b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+    uint32_t tl, te;
+    const uint32_t el = block_excl_scan(c & 0xffffu, sh, &tl);
+    const uint32_t ee = block_excl_scan(c >> 16, sh, &te);
+    if (b < nb) {
+      blockoff[((size_t)n * nb + b) * 2] = carry_l + el;
+      blockoff[((size_t)n * nb + b) * 2 + 1] = carry_e + ee;
+    }
+    carry_l += tl;
+    carry_e += te;
+    __syncthreads();
+  }
+}
+
+// the ordered write from the masks: one chunk per wave, one mask word (32 keys) per lane; compact_write_kernel's positions
+__global__ void __launch_bounds__(256) sel_write_kernel(const uint32_t* __restrict__ keys, int64_t plane,
+                                                        const uint32_t* __restrict__ state,
+                                                        const uint32_t* __restrict__ blockoff,
+                                                        const uint32_t* __restrict__ lessm, const uint32_t* __restrict__ eqm,
+                                                        int nb, int k, int32_t* __restrict__ idx_out) {
+  const int n = blockIdx.y;
+  const int lane = threadIdx.x & 63;
+  const int chunk = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (chunk >= nb) return;
+  const uint32_t krem = state[SEL_STATE * n + 1];
+  const uint32_t nless = (uint32_t)k - krem;
+  const int32_t sft = (int32_t)sel_shift_of(keys + (size_t)n * plane);
+  const size_t word = ((size_t)n * nb + chunk) * SEL_WORDS + lane;
+  uint32_t fl = lessm[word], fe = eqm[word];
+  const uint32_t cl = (uint32_t)__popc(fl), ce = (uint32_t)__popc(fe);
+  if (__ballot((cl | ce) != 0) == 0) return;
+  uint32_t pl = wave_incl_scan(cl, lane) - cl + blockoff[((size_t)n * nb + chunk) * 2];
+  uint32_t pe = wave_incl_scan(ce, lane) - ce + blockoff[((size_t)n * nb + chunk) * 2 + 1];
+  const int32_t e0 = (int32_t)((int64_t)chunk * CHUNK + lane * 32) - sft;
+  int32_t* o = idx_out + (size_t)n * k;
+  while (fl) {
+    const int j = __ffs((int)fl) - 1;
+    fl &= fl - 1;
+    if (pl < nless) o[pl] = e0 + j;
+    ++pl;
+  }
+  while (fe && pe < krem) {
+    const int j = __ffs((int)fe) - 1;
+    fe &= fe - 1;
+    o[nless + pe] = e0 + j;
+    ++pe;
   }
 }
 
@@ -516,22 +837,17 @@ int launch_upsample2x_keys(const float* in, int N, int C, int h, int w, float* o
   return EMP_OK;
 }
 
+static inline int sel_chunks(int64_t plane) { return (int)cdiv64(plane + 3, CHUNK); }      // + 3: the alignment shift
+
 size_t topk_work_bytes(int N, int64_t plane) {
-  int nb = (int)cdiv64(plane, CHUNK);
-  return (size_t)N * (256 + 4 + (size_t)nb * 3) * sizeof(uint32_t) + 256;
+  // hist | state | chunk counts | chunk offsets (2) | less mask | eq mask | candidates (key, index); the legacy select
+  // lays its smaller arrays over the start of the same buffer
+  const size_t nb = (size_t)sel_chunks(plane);
+  return (size_t)N * (SEL_BINS + SEL_STATE + nb * 3 + nb * SEL_WORDS * 2 + (size_t)SEL_CAP * 2) * sizeof(uint32_t) + 256;
 }
 
-// keys: (N, plane) non-negative-float bit patterns; selects the k smallest per image.
-int launch_topk_smallest(const uint32_t* keys, int N, int64_t plane, int k, void* work, size_t work_bytes,
-                         int32_t* idx_out, hipStream_t s) {
-  EMP_REQUIRE(k > 0 && plane > 0, "topk: k=%d plane=%lld", k, (long long)plane);
-  if ((int64_t)k >= plane) {
-    EMP_REQUIRE((int64_t)k == plane, "topk: k > plane");
-    hipLaunchKernelGGL(iota_kernel, dim3(cdiv(N * k, 256)), dim3(256), 0, s, idx_out, N, k);
-    EMP_LAUNCH_CHECK();
-    return EMP_OK;
-  }
-  EMP_REQUIRE(work_bytes >= topk_work_bytes(N, plane), "topk: workspace too small");
+static int launch_topk_legacy(const uint32_t* keys, int N, int64_t plane, int k, void* work, int32_t* idx_out,
+                              hipStream_t s) {
   const int nb = (int)cdiv64(plane, CHUNK);
   uint32_t* hist = (uint32_t*)work;
   uint32_t* state = hist + (size_t)N * 256;
@@ -552,6 +868,53 @@ int launch_topk_smallest(const uint32_t* keys, int N, int64_t plane, int k, void
   hipLaunchKernelGGL(compact_scan_kernel, dim3(N), dim3(256), 0, s, blockcnt, blockoff, nb);
   EMP_LAUNCH_CHECK();
   hipLaunchKernelGGL(compact_write_kernel, dim3(nb, N), dim3(256), 0, s, keys, plane, state, blockoff, nb, k, idx_out);
+  EMP_LAUNCH_CHECK();
+  return EMP_OK;
+}
+
+// keys: (N, plane) non-negative-float bit patterns; selects the k smallest per image.
+int launch_topk_smallest(const uint32_t* keys, int N, int64_t plane, int k, void* work, size_t work_bytes,
+                         int32_t* idx_out, hipStream_t s) {
+  EMP_REQUIRE(k > 0 && plane > 0, "topk: k=%d plane=%lld", k, (long long)plane);
+  if ((int64_t)k >= plane) {
+    EMP_REQUIRE((int64_t)k == plane, "topk: k > plane");
+    hipLaunchKernelGGL(iota_kernel, dim3(cdiv(N * k, 256)), dim3(256), 0, s, idx_out, N, k);
+    EMP_LAUNCH_CHECK();
+    return EMP_OK;
+  }
+  EMP_REQUIRE(work_bytes >= topk_work_bytes(N, plane), "topk: workspace too small");
+  const char* legacy_env = getenv("EMP_TOPK_LEGACY");      // =1: the four-pass radix select (read per call: A/B; identical output)
+  if (legacy_env && legacy_env[0] == '1') return launch_topk_legacy(keys, N, plane, k, work, idx_out, s);
+  const int nb = sel_chunks(plane);
+  uint32_t* hist = (uint32_t*)work;
+  uint32_t* state = hist + (size_t)N * SEL_BINS;
+  uint32_t* blockcnt = state + (size_t)N * SEL_STATE;
+  uint32_t* blockoff = blockcnt + (size_t)N * nb;
+  uint32_t* lessm = blockoff + (size_t)N * nb * 2;
+  uint32_t* eqm = lessm + (size_t)N * nb * SEL_WORDS;
+  uint32_t* cand = eqm + (size_t)N * nb * SEL_WORDS;
+  hipLaunchKernelGGL(sel_init_kernel, dim3(cdiv(N * SEL_BINS, 256)), dim3(256), 0, s, state, hist, N, (uint32_t)k);
+  EMP_LAUNCH_CHECK();
+  const int hb = (int)cdiv64(plane + 3, (int64_t)SEL_HIST_CHUNKS * CHUNK);
+  // level 0 for every image; levels 1 and 2 return at once unless the image's threshold bin overflowed the candidate
+  // buffer, so their grids are capped (the workgroups of an overflow image walk it in rounds)
+  const int lv_shift[3] = {SEL_SHIFT, SEL_L2_SHIFT, 0};
+  const uint32_t lv_bins[3] = {(uint32_t)SEL_BINS - 1u, (1u << SEL_L2_BITS) - 1u, (1u << SEL_L2_SHIFT) - 1u};
+  const uint32_t lv_hi[3] = {0u, 0xffffffffu << SEL_SHIFT, 0xffffffffu << SEL_L2_SHIFT};
+  for (int level = 0; level < 3; ++level) {
+    const int gx = level == 0 ? hb : (hb < 64 ? hb : 64);
+    hipLaunchKernelGGL(sel_hist_kernel, dim3(gx, N), dim3(256), 0, s, keys, plane, state, hist, level, lv_shift[level],
+                       lv_bins[level], lv_hi[level]);
+    EMP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sel_find_kernel, dim3(N), dim3(256), 0, s, hist, state, level, lv_shift[level]);
+    EMP_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(sel_cand_kernel, dim3(cdiv(nb, 4), N), dim3(256), 0, s, keys, plane, state, blockcnt, lessm, eqm, cand, nb);
+  EMP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(sel_resolve_kernel, dim3(N), dim3(256), 0, s, state, blockcnt, blockoff, lessm, eqm, cand, nb);
+  EMP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(sel_write_kernel, dim3(cdiv(nb, 4), N), dim3(256), 0, s, keys, plane, state, blockoff, lessm, eqm, nb, k,
+                     idx_out);
   EMP_LAUNCH_CHECK();
   return EMP_OK;
 }

@@ -540,6 +540,134 @@ __global__ void __launch_bounds__(256) merge_write_kernel(const float* __restric
   }
 }
 
+// 16-byte forms of the two streaming kernels (default; EMP_MERGE_SCALAR=1, or a base that is not 16-byte aligned, or a plane
+// that is no multiple of 4, takes the kernels above).  A lane owns 4 consecutive pixels: one float4 per class plane, one int4
+// of cells, two 16-byte stores of pan, so that a wave's load covers 1 KiB without gaps.  The counts are integers: the order in
+// which pixels are added does not show in the result.
+__device__ __forceinline__ void harden4(const float* __restrict__ sem, int C, int64_t plane, int64_t pix, float thr, int cls[4]) {
+  const float4 v0 = *reinterpret_cast<const float4*>(sem + pix);
+  float bv[4] = {v0.x, v0.y, v0.z, v0.w};
+  if (C == 1) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) cls[j] = bv[j] >= thr ? 1 : 0;
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) cls[j] = 0;
+  for (int c = 1; c < C; ++c) {
+    const float4 vc = *reinterpret_cast<const float4*>(sem + c * plane + pix);
+    const float v[4] = {vc.x, vc.y, vc.z, vc.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (v[j] > bv[j]) { bv[j] = v[j]; cls[j] = c; }
+  }
+}
+
+// merge_count_kernel with vector loads: a workgroup covers 4096 pixels, a thread MERGE_VEC_GROUPS groups of 4 (256 groups
+// apart); its run carries over from one group to the next
+constexpr int MERGE_VEC_GROUPS = 4;
+__global__ void __launch_bounds__(256) merge_count_vec_kernel(const float* __restrict__ sem, const int32_t* __restrict__ cells,
+                                                              int C, int CLS, int64_t plane, float thr, ThingList tl,
+                                                              int max_ids, int32_t* __restrict__ counts_all,
+                                                              size_t img_stride_i32) {
+  __shared__ int tkey[256];
+  __shared__ int tval[256];
+  const int n = blockIdx.y;
+  const float* s = sem + (size_t)n * C * plane;
+  const int32_t* ce = cells + (size_t)n * plane;
+  int32_t* counts = counts_all + (size_t)n * img_stride_i32;
+  tkey[threadIdx.x] = -1;
+  tval[threadIdx.x] = 0;
+  __syncthreads();
+  const int stuff_base = (max_ids + 1) * CLS;
+  int run_key = -1, run_cnt = 0;
+  auto flush = [&]() {
+    if (run_cnt == 0) return;
+    unsigned h = ((unsigned)run_key * 2654435761u) >> 24;
+    bool done = false;
+    for (int probe = 0; probe < 256 && !done; ++probe) {
+      int old = atomicCAS(&tkey[h], -1, run_key);
+      if (old == -1 || old == run_key) {
+        atomicAdd(&tval[h], run_cnt);
+        done = true;
+      } else {
+        h = (h + 1) & 255u;
+      }
+    }
+    if (!done) atomicAdd(&counts[run_key], run_cnt);  // table full (never seen in practice)
+    run_cnt = 0;
+  };
+  // every load of the thread's groups is issued before the first run is flushed
+  int cls[MERGE_VEC_GROUPS][4];
+  int4 cv[MERGE_VEC_GROUPS];
+#pragma unroll
+  for (int r = 0; r < MERGE_VEC_GROUPS; ++r) {
+    const int64_t p0 = (((int64_t)blockIdx.x * MERGE_VEC_GROUPS + r) * 256 + threadIdx.x) * 4;
+    cv[r] = make_int4(0, 0, 0, 0);
+    if (p0 < plane) {                                   // plane % 4 == 0: the whole group is inside
+      harden4(s, C, plane, p0, thr, cls[r]);
+      cv[r] = *reinterpret_cast<const int4*>(ce + p0);
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < MERGE_VEC_GROUPS; ++r) {
+    const int64_t p0 = (((int64_t)blockIdx.x * MERGE_VEC_GROUPS + r) * 256 + threadIdx.x) * 4;
+    if (p0 < plane) {
+      const int ids[4] = {cv[r].x, cv[r].y, cv[r].z, cv[r].w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        int id = is_thing(tl, cls[r][j]) ? ids[j] : 0;
+        if (id > max_ids || id < 0) id = 0;
+        const int key = id > 0 ? id * CLS + cls[r][j] : stuff_base + cls[r][j];
+        if (key != run_key) { flush(); run_key = key; }
+        ++run_cnt;
+      }
+    }
+  }
+  flush();
+  __syncthreads();
+  const int k = tkey[threadIdx.x];
+  if (k >= 0) atomicAdd(&counts[k], tval[threadIdx.x]);
+}
+
+__global__ void __launch_bounds__(256) merge_write_vec_kernel(const float* __restrict__ sem, const int32_t* __restrict__ cells,
+                                                              int C, int CLS, int64_t plane, float thr, ThingList tl,
+                                                              int max_ids, int64_t divisor, int64_t stuff_area,
+                                                              int64_t void_label, const int32_t* __restrict__ stuff_all,
+                                                              const int64_t* __restrict__ map_all, size_t img_stride_i32,
+                                                              size_t map_stride, int64_t* __restrict__ pan) {
+  const int n = blockIdx.y;
+  const float* s = sem + (size_t)n * C * plane;
+  const int32_t* ce = cells + (size_t)n * plane;
+  const int32_t* stuff = stuff_all + (size_t)n * img_stride_i32;
+  const int64_t* map = map_all + (size_t)n * map_stride;
+  int64_t* o = pan + (size_t)n * plane;
+  for (int64_t p = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; p < plane; p += (int64_t)gridDim.x * 1024) {
+    int cls[4];
+    harden4(s, C, plane, p, thr, cls);
+    const int4 cv = *reinterpret_cast<const int4*>(ce + p);
+    const int ids[4] = {cv.x, cv.y, cv.z, cv.w};
+    int64_t v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      v[j] = void_label;
+      if (is_thing(tl, cls[j])) {
+        const int id = ids[j];
+        if (id > 0 && id <= max_ids) {
+          const int64_t m = map[id];
+          if (m >= 0) v[j] = m;
+        }
+      } else if ((int64_t)stuff[cls[j]] >= stuff_area) {
+        v[j] = (int64_t)cls[j] * divisor;
+      }
+    }
+    longlong2 a, b;
+    a.x = v[0]; a.y = v[1]; b.x = v[2]; b.y = v[3];
+    *reinterpret_cast<longlong2*>(o + p) = a;
+    *reinterpret_cast<longlong2*>(o + p + 2) = b;
+  }
+}
+
 }  // namespace
 }  // namespace emp
 
@@ -656,15 +784,27 @@ int emp_panoptic_merge(const float* d_sem, const int32_t* d_cells, int N, int C,
   EMP_CHECK_HIP(hipMemsetAsync(d_work, 0, (size_t)N * stride * 4, s));
   const int64_t plane = (int64_t)H * W;
   const int nb = (int)cdiv64(plane, 256 * 8);
-  hipLaunchKernelGGL(merge_count_kernel, dim3(nb, N), dim3(256), 0, s, d_sem, d_cells, C, CLS, plane, confidence_thr,
-                     tl, max_ids, counts, stride);
+  const char* scalar_env = getenv("EMP_MERGE_SCALAR");      // =1: one pixel per load and store (read per call: A/B; identical output)
+  const bool vec = !(scalar_env && scalar_env[0] == '1') && plane % 4 == 0 &&
+                   (((uintptr_t)d_sem | (uintptr_t)d_cells | (uintptr_t)d_pan) & 15u) == 0;
+  if (vec)
+    hipLaunchKernelGGL(merge_count_vec_kernel, dim3((int)cdiv64(plane, 256 * 4 * MERGE_VEC_GROUPS), N), dim3(256), 0, s, d_sem, d_cells, C, CLS, plane, confidence_thr,
+                       tl, max_ids, counts, stride);
+  else
+    hipLaunchKernelGGL(merge_count_kernel, dim3(nb, N), dim3(256), 0, s, d_sem, d_cells, C, CLS, plane, confidence_thr,
+                       tl, max_ids, counts, stride);
   EMP_LAUNCH_CHECK();
   hipLaunchKernelGGL(merge_assign_kernel, dim3(N), dim3(256), 0, s, CLS, max_ids, label_divisor, counts, map, stride,
                      map_stride);
   EMP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(merge_write_kernel, dim3(grid_for(plane, 256, 2048), N), dim3(256), 0, s, d_sem, d_cells, C, CLS,
-                     plane, confidence_thr, tl, max_ids, label_divisor, stuff_area, void_label, stuff, map, stride,
-                     map_stride, d_pan);
+  if (vec)
+    hipLaunchKernelGGL(merge_write_vec_kernel, dim3(grid_for(plane / 4, 256, 2048), N), dim3(256), 0, s, d_sem, d_cells, C,
+                       CLS, plane, confidence_thr, tl, max_ids, label_divisor, stuff_area, void_label, stuff, map, stride,
+                       map_stride, d_pan);
+  else
+    hipLaunchKernelGGL(merge_write_kernel, dim3(grid_for(plane, 256, 2048), N), dim3(256), 0, s, d_sem, d_cells, C, CLS,
+                       plane, confidence_thr, tl, max_ids, label_divisor, stuff_area, void_label, stuff, map, stride,
+                       map_stride, d_pan);
   EMP_LAUNCH_CHECK();
   return EMP_OK;
 }

@@ -399,9 +399,15 @@ EMP_API int emp_sepconvp_ws_nhwc_f16(const void* d_in, int N, int H, int W, int 
  *   align_corners=False), and d_keys (N,2h*2w) uint32: the fp32 bit pattern of |v| (C == 1) or top1 - top2 over the classes
  *   (C > 1) of the up-sampled logits -- the negated uncertainty of point_rend.py:11-31, never negative.
  * emp_pr_topk_smallest: per image the k cells with the smallest keys (fp32 bit patterns of non-negative values): every key
- *   below the k-th smallest value and, among the cells equal to it, those with the lowest index.  d_idx (N,k) int32, order
- *   unspecified.  k == plane returns every cell; k > plane, k <= 0 or work_bytes < emp_pr_topk_work_bytes is an error and
- *   launches nothing.  The workspace needs no initialisation and may be reused by the next call on the same stream.
+ *   below the k-th smallest value and, among the cells equal to it, those with the lowest index.  d_idx (N,k) int32: first
+ *   the cells below the k-th value in ascending order, then the tied cells in ascending order.  k == plane returns every
+ *   cell; k > plane, k <= 0 or work_bytes < emp_pr_topk_work_bytes is an error and launches nothing.  The workspace needs
+ *   no initialisation and may be reused by the next call on the same stream.  The keys are read twice with 16-byte loads
+ *   (a histogram of their 12 leading bits, then one pass that marks the cells below the threshold bin in a bit mask and
+ *   collects the keys of that bin, at most 8192 per image, from which the exact threshold is resolved); an image whose
+ *   threshold bin holds more keys (a constant image) is refined on the device by two more histogram passes, without a host
+ *   synchronisation, and a batch may mix both kinds.  d_keys needs 4-byte alignment only.  EMP_TOPK_LEGACY=1 (read per
+ *   call): the four-pass radix select that reads the keys six times; same output, element for element.
  * emp_pr_point_features_f16 / _f32: point_sample (point_rend.py:33-60: grid_sample, bilinear, align_corners=False, zero
  *   padding) of the NHWC feature map d_feat (N,fh,fw,feat_ld; C channels used) and of the NCHW coarse logits d_coarse
  *   (N,ncls,fh,fw) fp32 at the centres of the cells d_idx (N,P) of an H2 x W2 grid (point_rend.py:131-135).  Row p of d_x0 is
@@ -485,7 +491,10 @@ EMP_API int emp_instance_cells(const float* d_ctr_hmp, const float* d_offsets, i
  *   d_sem (N,C,H,W) fp32 probabilities; d_cells (N,H,W) int32
  *   thing_list: host array of n_things class ids
  *   d_pan (N,H,W) int64 (reference dtype) ; max_ids: upper bound on cell ids
- *   d_work: scratch of emp_panoptic_merge_work_bytes(N, C, max_ids) bytes */
+ *   d_work: scratch of emp_panoptic_merge_work_bytes(N, C, max_ids) bytes
+ * The two streaming kernels move 16 bytes per lane when H * W is a multiple of 4 and d_sem, d_cells and d_pan are 16-byte
+ * aligned, and one pixel per lane otherwise; EMP_MERGE_SCALAR=1 (read per call) takes the latter everywhere.  The counts
+ * are integers: the result is the same either way. */
 EMP_API size_t emp_panoptic_merge_work_bytes(int N, int C, int max_ids);
 EMP_API int emp_panoptic_merge(const float* d_sem, const int32_t* d_cells, int N, int C, int H, int W,
                        float confidence_thr, const int32_t* h_thing_list, int n_things,
