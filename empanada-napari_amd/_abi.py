@@ -100,6 +100,18 @@ PROTOTYPES = {
                                   C.POINTER(vp), c_int, c_int, vp, vp, vp, c_i64, vp]),
     'emp_head1x1_scatter_f16': (c_int, [vp, c_int, c_int, c_int, c_int, vp, vp, c_int, vp, c_i64, vp, vp]),
     'emp_head1x1_scatter_f32': (c_int, [vp, c_int, c_int, c_int, c_int, vp, vp, c_int, vp, c_i64, vp, vp]),
+    'emp_op_stem7x7': (c_int, [vp, c_int, c_f32, c_f32, c_int, c_int, c_int, c_int, c_int, vp, vp, vp, c_int, vp]),
+    'emp_op_stem_pool': (c_int, [vp, c_int, c_f32, c_f32, c_int, c_int, c_int, c_int, c_int, vp, vp, vp, c_int, vp]),
+    'emp_op_stem3x3s2': (c_int, [vp, c_int, c_f32, c_f32, c_int, c_int, c_int, c_int, c_int, vp, vp, c_int, vp, c_int, c_int, vp]),
+    'emp_op_maxpool3x3s2': (c_int, [vp, c_int, c_int, c_int, c_int, vp, c_int, vp]),
+    'emp_op_fuse_combine': (c_int, [vp, vp, vp, c_f32, c_f32, c_f32, c_int, c_int, c_int, c_int, c_int, vp, vp, c_int, c_int, vp]),
+    'emp_op_bilinear_ac_nhwc': (c_int, [vp, c_int, c_int, c_int, c_int, c_int, vp, c_int, c_int, c_int, c_int, c_int, vp]),
+    'emp_op_bilinear_ac_nchw_f32': (c_int, [vp, c_int, c_int, c_int, vp, c_int, vp]),
+    'emp_op_avgpool_work_bytes': (c_int, [c_int, c_int, c_int, C.POINTER(sz)]),
+    'emp_op_avgpool': (c_int, [vp, c_int, c_int, c_int, c_int, vp, vp, sz, c_int, vp]),
+    'emp_op_gemv': (c_int, [vp, c_int, c_int, vp, vp, c_int, c_int, vp, vp]),
+    'emp_op_gate_mul': (c_int, [vp, c_int, vp, c_int, c_i64, c_int, c_int, vp]),
+    'emp_op_dwconv_nhwc_f32': (c_int, [vp, c_int, c_int, c_int, c_int, c_int, vp, c_int, vp, c_int, vp]),
     'emp_sm_create': (vp, [c_i64, c_i64, c_f64, c_f64, c_int]),
     'emp_sm_destroy': (None, [vp]),
     'emp_sm_push_slice_runs': (c_int, [vp, vp, c_i64, c_i64, c_i64]),

@@ -465,4 +465,109 @@ int emp_head1x1_scatter_f32(const float* d_in, int N, int P, int K, int in_ld, c
   return launch_head1x1_f32(d_in, N, P, K, in_ld, d_w, d_b, C, d_out, plane, d_scatter_idx, (hipStream_t)stream);
 }
 
+// ---- the network's glue layers, operator by operator (layers.hip, stem.hip, ref32.hip, conv16x3p.hip): the launches of run() /
+// run32() between the convolutions.  prec: EMP_OP_F16 the fp16 engine's kernel, EMP_OP_F32 its fp32 twin, EMP_OP_HL32 (average
+// pool only) the plane region's.  The launchers check the shapes; here the pointers ----
+#define EMP_OP_PREC(prec, what) EMP_REQUIRE((prec) == EMP_OP_F16 || (prec) == EMP_OP_F32, what ": prec must be EMP_OP_F16 or EMP_OP_F32 (got %d)", (prec))
+
+int emp_op_stem7x7(const void* d_img, int image_dtype, float sub, float mul, int N, int H, int W, int vh, int vw, const float* d_w,
+                   const float* d_b, void* d_out, int prec, void* stream) {
+  EMP_REQUIRE(d_img && d_w && d_b && d_out, "op_stem7x7: null pointer");
+  EMP_OP_PREC(prec, "op_stem7x7");
+  if (prec == EMP_OP_F32) return launch_stem7x7_f32(d_img, image_dtype, sub, mul, N, H, W, vh, vw, d_w, d_b, (float*)d_out, (hipStream_t)stream);
+  return launch_stem7x7(d_img, image_dtype, sub, mul, N, H, W, vh, vw, d_w, d_b, (half_t*)d_out, (hipStream_t)stream);
+}
+
+int emp_op_stem_pool(const void* d_img, int image_dtype, float sub, float mul, int N, int H, int W, int vh, int vw, const float* d_w,
+                     const float* d_b, void* d_out, int prec, void* stream) {
+  EMP_REQUIRE(d_img && d_w && d_b && d_out, "op_stem_pool: null pointer");
+  EMP_OP_PREC(prec, "op_stem_pool");
+  if (prec == EMP_OP_F32) return launch_stem_pool_f32(d_img, image_dtype, sub, mul, N, H, W, vh, vw, d_w, d_b, (float*)d_out, (hipStream_t)stream);
+  return launch_stem_pool(d_img, image_dtype, sub, mul, N, H, W, vh, vw, d_w, d_b, (half_t*)d_out, (hipStream_t)stream);
+}
+
+int emp_op_stem3x3s2(const void* d_img, int image_dtype, float sub, float mul, int N, int H, int W, int vh, int vw, const float* d_w,
+                     const float* d_b, int C, void* d_out, int out_ld, int prec, void* stream) {
+  EMP_REQUIRE(d_img && d_w && d_b && d_out && ((uintptr_t)d_w % 16) == 0 && ((uintptr_t)d_b % 16) == 0 && ((uintptr_t)d_out % 16) == 0,
+              "op_stem3x3s2: null or misaligned pointer");
+  EMP_OP_PREC(prec, "op_stem3x3s2");
+  EMP_REQUIRE(C > 0, "op_stem3x3s2: bad channel count %d", C);
+  if (prec == EMP_OP_F32)
+    return launch_stem3x3s2_f32(d_img, image_dtype, sub, mul, N, H, W, vh, vw, d_w, d_b, C, (float*)d_out, out_ld, (hipStream_t)stream);
+  return launch_stem3x3s2_f16(d_img, image_dtype, sub, mul, N, H, W, vh, vw, d_w, d_b, C, (half_t*)d_out, out_ld, (hipStream_t)stream);
+}
+
+int emp_op_maxpool3x3s2(const void* d_in, int N, int H, int W, int C, void* d_out, int prec, void* stream) {
+  EMP_REQUIRE(d_in && d_out && ((uintptr_t)d_in % 16) == 0 && ((uintptr_t)d_out % 16) == 0, "op_maxpool3x3s2: null or misaligned pointer");
+  EMP_OP_PREC(prec, "op_maxpool3x3s2");
+  if (prec == EMP_OP_F32) return launch_maxpool3x3s2_f32((const float*)d_in, N, H, W, C, (float*)d_out, (hipStream_t)stream);
+  return launch_maxpool3x3s2((const half_t*)d_in, N, H, W, C, (half_t*)d_out, (hipStream_t)stream);
+}
+
+int emp_op_fuse_combine(const void* d_a, const void* d_b, const void* d_c, float ca, float cb, float cc, int mode, int N, int H, int W,
+                        int C, void* d_out, void* d_out_lo, int out_ld, int prec, void* stream) {
+  EMP_REQUIRE(d_a && d_b && d_out && ((uintptr_t)d_a % 16) == 0 && ((uintptr_t)d_b % 16) == 0 && ((uintptr_t)d_c % 16) == 0 &&
+                  ((uintptr_t)d_out % 16) == 0 && ((uintptr_t)d_out_lo % 16) == 0, "op_fuse_combine: null or misaligned pointer");
+  EMP_OP_PREC(prec, "op_fuse_combine");
+  if (prec == EMP_OP_F32) {
+    EMP_REQUIRE(d_out_lo == nullptr && (out_ld == 0 || out_ld == C), "op_fuse_combine: the fp32 kernel writes dense rows and no lo part");
+    return launch_fuse_combine_f32((const float*)d_a, (const float*)d_b, (const float*)d_c, ca, cb, cc, mode, N, H, W, C, (float*)d_out,
+                                   (hipStream_t)stream);
+  }
+  return launch_fuse_combine((const half_t*)d_a, (const half_t*)d_b, (const half_t*)d_c, ca, cb, cc, mode, N, H, W, C, (half_t*)d_out,
+                             (hipStream_t)stream, (half_t*)d_out_lo, out_ld);
+}
+
+int emp_op_bilinear_ac_nhwc(const void* d_in, int N, int h, int w, int C, int in_ld, void* d_out, int H, int W, int out_ld, int prec,
+                            int variant, void* stream) {
+  EMP_REQUIRE(d_in && d_out && ((uintptr_t)d_in % 16) == 0 && ((uintptr_t)d_out % 16) == 0, "op_bilinear_ac_nhwc: null or misaligned pointer");
+  EMP_OP_PREC(prec, "op_bilinear_ac_nhwc");
+  if (prec == EMP_OP_F32) {
+    EMP_REQUIRE(variant == 0, "op_bilinear_ac_nhwc: the fp32 kernels are chosen by EMP_BILINEAR32_X4 (read per call), variant must be 0");
+    return launch_bilinear_ac_f32_nhwc((const float*)d_in, N, h, w, C, in_ld, (float*)d_out, H, W, out_ld, (hipStream_t)stream);
+  }
+  return launch_bilinear_ac((const half_t*)d_in, N, h, w, C, in_ld, (half_t*)d_out, H, W, out_ld, (hipStream_t)stream, variant);
+}
+
+int emp_op_bilinear_ac_nchw_f32(const float* d_in, int NC, int h, int w, float* d_out, int scale, void* stream) {
+  return launch_bilinear_ac_f32_nchw(d_in, NC, h, w, d_out, scale, (hipStream_t)stream);
+}
+
+int emp_op_avgpool_work_bytes(int N, int C, int prec, size_t* h_bytes) {
+  EMP_REQUIRE(h_bytes && N > 0 && C > 0 && (int64_t)N * C < (1ll << 26), "op_avgpool_work_bytes: bad argument");
+  EMP_REQUIRE(prec == EMP_OP_F16 || prec == EMP_OP_F32 || prec == EMP_OP_HL32, "op_avgpool_work_bytes: unknown prec %d", prec);
+  *h_bytes = prec == EMP_OP_F16 ? (size_t)avgpool_scratch_floats(N, C) * sizeof(float) : 0;
+  return EMP_OK;
+}
+
+int emp_op_avgpool(const void* d_in, int N, int HW, int C, int in_ld, float* d_out, void* d_work, size_t work_bytes, int prec,
+                   void* stream) {
+  EMP_REQUIRE(d_in && d_out && ((uintptr_t)d_in % 16) == 0, "op_avgpool: null or misaligned pointer");
+  EMP_REQUIRE(N > 0 && C > 0 && (int64_t)N * C < (1ll << 26), "op_avgpool: bad geometry");
+  if (prec == EMP_OP_F32) return launch_avgpool_f32((const float*)d_in, N, HW, C, in_ld, d_out, (hipStream_t)stream);
+  if (prec == EMP_OP_HL32) return launch_avgpool_hl32((const half_t*)d_in, N, HW, C, in_ld, d_out, (hipStream_t)stream);
+  EMP_REQUIRE(prec == EMP_OP_F16, "op_avgpool: unknown prec %d", prec);
+  EMP_REQUIRE(d_work && ((uintptr_t)d_work % 4) == 0 && work_bytes >= (size_t)avgpool_scratch_floats(N, C) * sizeof(float),
+              "op_avgpool: the fp16 kernel needs emp_op_avgpool_work_bytes of scratch");
+  return launch_avgpool((const half_t*)d_in, N, HW, C, in_ld, d_out, (float*)d_work, (hipStream_t)stream);
+}
+
+int emp_op_gemv(const float* d_in, int N, int K, const float* d_w, const float* d_b, int Cout, int relu, float* d_out, void* stream) {
+  return launch_gemv(d_in, N, K, d_w, d_b, Cout, relu, d_out, (hipStream_t)stream);
+}
+
+int emp_op_gate_mul(void* d_x, int x_ld, void* d_g, int g_ld, int64_t rows, int C, int prec, void* stream) {
+  EMP_REQUIRE(d_x && d_g && ((uintptr_t)d_x % 16) == 0 && ((uintptr_t)d_g % 16) == 0, "op_gate_mul: null or misaligned pointer");
+  EMP_OP_PREC(prec, "op_gate_mul");
+  if (prec == EMP_OP_F32) return launch_gate_mul_f32((float*)d_x, x_ld, (const float*)d_g, g_ld, rows, C, (hipStream_t)stream);
+  return launch_gate_mul_f16((const half_t*)d_x, x_ld, (half_t*)d_g, g_ld, rows, C, (hipStream_t)stream);
+}
+
+int emp_op_dwconv_nhwc_f32(const float* d_in, int N, int H, int W, int C, int in_ld, const float* d_w, int K, float* d_out, int out_ld,
+                           void* stream) {
+  EMP_REQUIRE(d_in && d_w && d_out && ((uintptr_t)d_in % 16) == 0 && ((uintptr_t)d_w % 16) == 0 && ((uintptr_t)d_out % 16) == 0,
+              "op_dwconv_nhwc_f32: null or misaligned pointer");
+  return launch_dwconv_f32(d_in, N, H, W, C, in_ld, d_w, K, d_out, out_ld, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -140,8 +140,9 @@ int launch_dwconv(const half_t* in, int N, int H, int W, int C, int in_ld, const
 //   out_lo != nullptr: the result as an fp16 hi + lo pair (hi -> out, lo -> out_lo), rows out_ld apart (0: C)
 int launch_fuse_combine(const half_t* a, const half_t* b, const half_t* c, float ca, float cb, float cc, int mode,
                         int N, int H, int W, int C, half_t* out, hipStream_t s, half_t* out_lo = nullptr, int out_ld = 0);
+// variant 0: automatic (EMP_BILINEAR_NO_UP4=1 disables the four-pixel kernel), 1: one-pixel kernel, 2: four-pixel kernel or an error
 int launch_bilinear_ac(const half_t* in, int N, int h, int w, int C, int in_ld, half_t* out, int H, int W,
-                       int out_ld, hipStream_t s);
+                       int out_ld, hipStream_t s, int variant = 0);
 int launch_avgpool(const half_t* in, int N, int HW, int C, int in_ld, float* out /*N x C*/, float* part,
                    hipStream_t s);
 int avgpool_scratch_floats(int N, int C);

@@ -662,6 +662,7 @@ __global__ void __launch_bounds__(256) gate_mul_f16_kernel(const half_t* __restr
 int launch_stem7x7(const void* img, int dtype, float sub, float mul, int N, int H, int W, int vh, int vw,
                    const float* w, const float* b, half_t* out, hipStream_t s) {
   EMP_REQUIRE(H % 2 == 0 && W % 2 == 0, "stem: H, W must be even");
+  EMP_REQUIRE(N > 0 && H > 0 && W > 0 && vh >= 1 && vw >= 1 && vh <= H && vw <= W, "stem: valid size %dx%d must be non-empty and fit %dx%d", vh, vw, H, W);
   const int Ho = H / 2, Wo = W / 2;
   const int grid = N * cdiv(Ho, 16) * cdiv(Wo, 16);
   switch (dtype) {
@@ -687,6 +688,7 @@ int launch_stem7x7(const void* img, int dtype, float sub, float mul, int N, int 
 int launch_stem7x7_f32(const void* img, int dtype, float sub, float mul, int N, int H, int W, int vh, int vw,
                        const float* w, const float* b, float* out, hipStream_t s) {
   EMP_REQUIRE(H % 2 == 0 && W % 2 == 0, "stem: H, W must be even");
+  EMP_REQUIRE(N > 0 && H > 0 && W > 0 && vh >= 1 && vw >= 1 && vh <= H && vw <= W, "stem: valid size %dx%d must be non-empty and fit %dx%d", vh, vw, H, W);
   const int Ho = H / 2, Wo = W / 2;
   const int grid = N * cdiv(Ho, 16) * cdiv(Wo, 16);
   switch (dtype) {
@@ -712,6 +714,7 @@ int launch_stem7x7_f32(const void* img, int dtype, float sub, float mul, int N, 
 int launch_stem3x3s2_f16(const void* img, int dtype, float sub, float mul, int N, int H, int W, int vh, int vw, const float* w,
                          const float* b, int C, half_t* out, int out_ld, hipStream_t s) {
   EMP_REQUIRE(H % 2 == 0 && W % 2 == 0 && C % 8 == 0 && out_ld % 8 == 0 && out_ld >= C, "stem3x3 (fp16): bad shape");
+  EMP_REQUIRE(N > 0 && H > 0 && W > 0 && vh >= 1 && vw >= 1 && vh <= H && vw <= W, "stem3x3 (fp16): valid size %dx%d must be non-empty and fit %dx%d", vh, vw, H, W);
   const int64_t total = (int64_t)N * (H / 2) * (W / 2) * (C / 8);
   const dim3 grid(grid_for(total));
   switch (dtype) {
@@ -736,6 +739,7 @@ int launch_stem3x3s2_f16(const void* img, int dtype, float sub, float mul, int N
 
 int launch_gate_mul_f16(const half_t* x, int x_ld, half_t* g, int g_ld, int64_t rows, int C, hipStream_t s) {
   EMP_REQUIRE(C % 8 == 0 && x_ld % 8 == 0 && g_ld % 8 == 0 && x_ld >= C && g_ld >= C, "gate_mul (fp16): bad shape");
+  EMP_REQUIRE(x && g && rows > 0 && C > 0, "gate_mul (fp16): bad arguments");
   const int64_t total = rows * (C / 8);
   hipLaunchKernelGGL(gate_mul_f16_kernel, dim3(grid_for(total)), dim3(256), 0, s, x, x_ld, g, g_ld, C, total);
   EMP_LAUNCH_CHECK();
@@ -743,7 +747,7 @@ int launch_gate_mul_f16(const half_t* x, int x_ld, half_t* g, int g_ld, int64_t 
 }
 
 int launch_maxpool3x3s2(const half_t* in, int N, int H, int W, int C, half_t* out, hipStream_t s) {
-  EMP_REQUIRE(C % 8 == 0 && H % 2 == 0 && W % 2 == 0, "maxpool: bad shape");
+  EMP_REQUIRE(in && out && N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && H % 2 == 0 && W % 2 == 0, "maxpool: bad shape");
   int64_t total = (int64_t)N * (H / 2) * (W / 2) * (C / 8);
   hipLaunchKernelGGL(maxpool3x3s2_kernel, dim3(grid_for(total)), dim3(256), 0, s, in, N, H, W, C, out, total);
   EMP_LAUNCH_CHECK();
@@ -770,6 +774,7 @@ int launch_dwconv(const half_t* in, int N, int H, int W, int C, int in_ld, const
 int launch_fuse_combine(const half_t* a, const half_t* b, const half_t* c, float ca, float cb, float cc, int mode, int N,
                         int H, int W, int C, half_t* out, hipStream_t s, half_t* out_lo, int out_ld) {
   EMP_REQUIRE(C % 8 == 0 && (mode == 0 || mode == 1), "fuse_combine: bad arguments");
+  EMP_REQUIRE(a && b && out && N > 0 && H > 0 && W > 0 && C > 0, "fuse_combine: bad geometry");
   if (out_ld == 0) out_ld = C;
   EMP_REQUIRE(out_ld % 8 == 0 && out_ld >= C, "fuse_combine: bad output stride %d", out_ld);
   EMP_REQUIRE(mode == 1 || (H % 2 == 0 && W % 2 == 0), "fuse_combine: up-sampled operand needs even H, W");
@@ -780,9 +785,13 @@ int launch_fuse_combine(const half_t* a, const half_t* b, const half_t* c, float
   return EMP_OK;
 }
 
+// variant 0: the dispatch below (with the EMP_BILINEAR_NO_UP4 switch); 1: the one-pixel kernel; 2: the four-pixel kernel, an error
+// where its preconditions do not hold (the operator-level tests A/B both in one process)
 int launch_bilinear_ac(const half_t* in, int N, int h, int w, int C, int in_ld, half_t* out, int H, int W, int out_ld,
-                       hipStream_t s) {
+                       hipStream_t s, int variant) {
   EMP_REQUIRE(C % 8 == 0 && in_ld % 8 == 0 && out_ld % 8 == 0, "bilinear: channels must be multiples of 8");
+  EMP_REQUIRE(N > 0 && h > 0 && w > 0 && H > 0 && W > 0 && in_ld >= C && out_ld >= C, "bilinear: bad geometry");
+  EMP_REQUIRE(variant >= 0 && variant <= 2, "bilinear: unknown variant %d", variant);
   // area_pixel_compute_scale(align_corners=True): (in-1)/(out-1), 0 when out == 1
   float sy = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f;
   float sx = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
@@ -790,7 +799,9 @@ int launch_bilinear_ac(const half_t* in, int N, int h, int w, int C, int in_ld, 
   EMP_REQUIRE(CG >= 1 && CG <= 256, "bilinear: at most 2048 channels");
   const int ppb = 256 / CG;                         // pixels (up4: 4-pixel groups) per block iteration
   static const bool no_up4 = [] { const char* e = getenv("EMP_BILINEAR_NO_UP4"); return e && e[0] == '1'; }();   // A/B runs
-  if (!no_up4 && W % 4 == 0 && 3.f * sx < 1.f && W >= 4 * ppb) {
+  const bool up4_ok = W % 4 == 0 && 3.f * sx < 1.f && W >= 4 * ppb;
+  EMP_REQUIRE(variant != 2 || up4_ok, "bilinear: the four-pixel kernel needs W %% 4 == 0, 3 * sx < 1 and W >= %d (W=%d w=%d)", 4 * ppb, W, w);
+  if (variant == 2 || (variant == 0 && !no_up4 && up4_ok)) {
     const int segs = cdiv(W / 4, ppb);
     const int64_t total = (int64_t)N * H * segs;
     EMP_REQUIRE(total < (1ll << 31), "bilinear: too many row segments");
@@ -811,6 +822,8 @@ int launch_bilinear_ac(const half_t* in, int N, int h, int w, int C, int in_ld, 
 }
 
 int launch_bilinear_ac_f32_nchw(const float* in, int NC, int h, int w, float* out, int scale, hipStream_t s) {
+  EMP_REQUIRE(in && out && NC > 0 && h > 0 && w > 0 && scale >= 1 && (int64_t)h * scale < (1ll << 31) / ((int64_t)w * scale),
+              "bilinear (fp32 planes): bad arguments");
   const int H = h * scale, W = w * scale;
   float sy = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f;
   float sx = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
@@ -824,6 +837,8 @@ int launch_bilinear_ac_f32_nchw(const float* in, int NC, int h, int w, float* ou
 // part: scratch of N*AVG_SEG*C floats
 int launch_avgpool(const half_t* in, int N, int HW, int C, int in_ld, float* out, float* part, hipStream_t s) {
   EMP_REQUIRE(C % 8 == 0, "avgpool: C must be a multiple of 8");
+  EMP_REQUIRE(in && out && part && N > 0 && HW > 0 && C > 0 && in_ld % 8 == 0 && in_ld >= C &&
+                  (int64_t)N * AVG_SEG * C < (1ll << 31), "avgpool: bad arguments");
   hipLaunchKernelGGL(avgpool_partial_kernel, dim3(N, cdiv(C, 256), AVG_SEG), dim3(256), 0, s, in, HW, C, in_ld, part);
   EMP_LAUNCH_CHECK();
   const int total = N * C;
@@ -836,6 +851,7 @@ int avgpool_scratch_floats(int N, int C) { return N * AVG_SEG * C; }
 
 int launch_gemv(const float* in, int N, int K, const float* w, const float* b, int Cout, int relu, float* out,
                 hipStream_t s) {
+  EMP_REQUIRE(in && w && out && N > 0 && K > 0 && Cout > 0 && (int64_t)N * Cout < (1ll << 29), "gemv: bad arguments");
   const int waves = N * Cout;
   hipLaunchKernelGGL(gemv_kernel, dim3(cdiv(waves, 4)), dim3(256), 0, s, in, N, K, w, b, Cout, relu, out);
   EMP_LAUNCH_CHECK();

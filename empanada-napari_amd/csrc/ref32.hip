@@ -532,6 +532,7 @@ __global__ void __launch_bounds__(256) gate_mul32_kernel(float* __restrict__ x, 
 int launch_stem3x3s2_f32(const void* img, int dtype, float sub, float mul, int N, int H, int W, int vh, int vw, const float* w,
                          const float* b, int C, float* out, int out_ld, hipStream_t s) {
   EMP_REQUIRE(H % 2 == 0 && W % 2 == 0 && C % 4 == 0 && out_ld % 4 == 0 && out_ld >= C, "stem3x3: bad shape");
+  EMP_REQUIRE(N > 0 && H > 0 && W > 0 && vh >= 1 && vw >= 1 && vh <= H && vw <= W, "stem3x3: valid size %dx%d must be non-empty and fit %dx%d", vh, vw, H, W);
   const int64_t total = (int64_t)N * (H / 2) * (W / 2) * (C / 4);
   const dim3 grid(grid_for(total));
   switch (dtype) {
@@ -556,6 +557,7 @@ int launch_stem3x3s2_f32(const void* img, int dtype, float sub, float mul, int N
 
 int launch_gate_mul_f32(float* x, int x_ld, const float* g, int g_ld, int64_t rows, int C, hipStream_t s) {
   EMP_REQUIRE(C % 4 == 0 && x_ld % 4 == 0 && g_ld % 4 == 0 && x_ld >= C && g_ld >= C, "gate_mul32: bad shape");
+  EMP_REQUIRE(x && g && rows > 0 && C > 0, "gate_mul32: bad arguments");
   const int64_t total = rows * (C / 4);
   hipLaunchKernelGGL(gate_mul32_kernel, dim3(grid_for(total)), dim3(256), 0, s, x, x_ld, g, g_ld, C, total);
   EMP_LAUNCH_CHECK();
@@ -587,7 +589,7 @@ int launch_conv32(const Conv32& p, hipStream_t s) {
 }
 
 int launch_maxpool3x3s2_f32(const float* in, int N, int H, int W, int C, float* out, hipStream_t s) {
-  EMP_REQUIRE(C % 4 == 0 && H % 2 == 0 && W % 2 == 0, "maxpool32: bad shape");
+  EMP_REQUIRE(in && out && N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 && H % 2 == 0 && W % 2 == 0, "maxpool32: bad shape");
   const int64_t total = (int64_t)N * (H / 2) * (W / 2) * (C / 4);
   hipLaunchKernelGGL(maxpool32_kernel, dim3(grid_for(total)), dim3(256), 0, s, in, N, H, W, C, out, total);
   EMP_LAUNCH_CHECK();
@@ -597,6 +599,7 @@ int launch_maxpool3x3s2_f32(const float* in, int N, int H, int W, int C, float* 
 int launch_dwconv_f32(const float* in, int N, int H, int W, int C, int in_ld, const float* w, int K, float* out, int out_ld,
                       hipStream_t s) {
   EMP_REQUIRE(C % 4 == 0 && in_ld % 4 == 0 && out_ld % 4 == 0 && (K == 3 || K == 5), "dwconv32: bad shape");
+  EMP_REQUIRE(in && w && out && N > 0 && H > 0 && W > 0 && C > 0 && in_ld >= C && out_ld >= C, "dwconv32: bad geometry");
   const char* strip_env = getenv("EMP_DW32_STRIP");      // =0: the one-output-per-thread kernel everywhere (read per call: tests A/B both in one process)
   if (W % 8 == 0 && !(strip_env && strip_env[0] == '0')) {
     const int64_t strips = (int64_t)N * H * (W / 8) * (C / 4);
@@ -614,6 +617,7 @@ int launch_dwconv_f32(const float* in, int N, int H, int W, int C, int in_ld, co
 int launch_bilinear_ac_f32_nhwc(const float* in, int N, int h, int w, int C, int in_ld, float* out, int H, int W, int out_ld,
                                 hipStream_t s) {
   EMP_REQUIRE(C % 4 == 0 && in_ld % 4 == 0 && out_ld % 4 == 0, "bilinear32: channels must be multiples of 4");
+  EMP_REQUIRE(in && out && N > 0 && h > 0 && w > 0 && H > 0 && W > 0 && C > 0 && in_ld >= C && out_ld >= C, "bilinear32: bad geometry");
   const float sy = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f;
   const float sx = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
   const int64_t total = (int64_t)N * H * W * (C / 4);
@@ -631,6 +635,7 @@ int launch_bilinear_ac_f32_nhwc(const float* in, int N, int h, int w, int C, int
 }
 
 int launch_avgpool_f32(const float* in, int N, int HW, int C, int in_ld, float* out, hipStream_t s) {
+  EMP_REQUIRE(in && out && N > 0 && HW > 0 && C > 0 && in_ld >= C && (int64_t)N * cdiv(C, 64) < (1ll << 31), "avgpool32: bad arguments");
   hipLaunchKernelGGL(avgpool32_kernel, dim3(N * cdiv(C, 64)), dim3(1024), 0, s, in, N, HW, C, in_ld, out);
   EMP_LAUNCH_CHECK();
   return EMP_OK;
@@ -639,6 +644,8 @@ int launch_avgpool_f32(const float* in, int N, int HW, int C, int in_ld, float* 
 int launch_fuse_combine_f32(const float* a, const float* b, const float* c, float ca, float cb, float cc, int mode, int N,
                             int H, int W, int C, float* out, hipStream_t s) {
   EMP_REQUIRE(mode == 0 || mode == 1, "fuse_combine32: bad mode");
+  EMP_REQUIRE(a && b && out && N > 0 && H > 0 && W > 0 && C > 0, "fuse_combine32: bad geometry");
+  EMP_REQUIRE(mode == 1 || (H % 2 == 0 && W % 2 == 0), "fuse_combine32: up-sampled operand needs even H, W");
   const int64_t total = (int64_t)N * H * W * C;
   hipLaunchKernelGGL(fuse_combine32_kernel, dim3(grid_for(total)), dim3(256), 0, s, a, b, c, ca, cb, cc, mode, N, H, W, C, out,
                      total);

@@ -294,6 +294,7 @@ __global__ void __launch_bounds__(256) stem_pool32_kernel(const T* __restrict__ 
 int launch_stem_pool(const void* img, int dtype, float sub, float mul, int N, int H, int W, int vh, int vw,
                      const float* w, const float* b, half_t* out, hipStream_t s) {
   EMP_REQUIRE(H % 4 == 0 && W % 4 == 0, "stem: H, W must be multiples of 4");
+  EMP_REQUIRE(N > 0 && H > 0 && W > 0 && vh >= 1 && vw >= 1 && vh <= H && vw <= W, "stem: valid size %dx%d must be non-empty and fit %dx%d", vh, vw, H, W);
   const int Hp = H / 4, Wp = W / 4;
   const int64_t tiles = (int64_t)N * cdiv(Hp, PT) * cdiv(Wp, PT);
   EMP_REQUIRE(tiles < (1ll << 31), "stem: too many tiles");
@@ -322,6 +323,7 @@ int launch_stem_pool(const void* img, int dtype, float sub, float mul, int N, in
 int launch_stem_pool_f32(const void* img, int dtype, float sub, float mul, int N, int H, int W, int vh, int vw,
                          const float* w, const float* b, float* out, hipStream_t s) {
   EMP_REQUIRE(H % 4 == 0 && W % 4 == 0, "stem: H, W must be multiples of 4");
+  EMP_REQUIRE(N > 0 && H > 0 && W > 0 && vh >= 1 && vw >= 1 && vh <= H && vw <= W, "stem: valid size %dx%d must be non-empty and fit %dx%d", vh, vw, H, W);
   const int Hp = H / 4, Wp = W / 4;
   const int64_t tiles = (int64_t)N * cdiv(Hp, PT) * cdiv(Wp, PT);
   EMP_REQUIRE(tiles < (1ll << 31), "stem: too many tiles");

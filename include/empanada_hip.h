@@ -441,6 +441,68 @@ EMP_API int emp_head1x1_scatter_f16(const void* d_in, int N, int P, int K, int i
 EMP_API int emp_head1x1_scatter_f32(const float* d_in, int N, int P, int K, int in_ld, const float* d_w, const float* d_b, int C,
                                     float* d_out, int64_t plane, const int32_t* d_scatter_idx, void* stream);
 
+/* The network's glue layers, operator by operator (csrc/layers.hip, csrc/stem.hip, their fp32 twins in csrc/ref32.hip and the
+ * plane region's average pool in csrc/conv16x3p.hip: every launch of emp_pdl_forward that is not a convolution).  Exported so that
+ * each kernel is tested against a plain float64 reference at shapes the network does not produce
+ * (tests/test_gpu_layer_kernels.py; references and error bounds in tests/layers_case.py).  Thin wrappers: no new kernel, nothing
+ * synchronises, nothing allocates.  A bad argument returns EMP_ERR_INVALID and launches nothing.
+ *
+ * prec selects the kernel: EMP_OP_F16 the fp16 engine's (fp16 NHWC maps), EMP_OP_F32 the fp32 / fp16x3 graph's (fp32 NHWC maps),
+ * EMP_OP_HL32 (emp_op_avgpool only) the plane region's hl32 map.  Maps are dense NHWC unless a row stride (`*_ld`, in elements)
+ * is given; fp16 kernels move 8 channels per lane (C, strides % 8 == 0), fp32 kernels 4 (% 4 == 0); pointers 16-byte aligned.
+ *
+ * emp_op_stem7x7: d_img (N,vh,vw) of image_dtype -> d_out (N,H/2,W/2,64): 7x7 stride-2 pad-3 conv + bias + ReLU of the image
+ *   normalised as (v - sub) * mul (EMP_IMG_U8 / U16; EMP_IMG_F32 is taken as it is) and THEN zero-padded from vh x vw to H x W
+ *   and by the convolution.  d_w (49,64) fp32 tap-major, d_b 64.  H, W even, 1 <= vh <= H, 1 <= vw <= W.  F16: stem7x7_kernel
+ *   storing fp16; F32: the same kernel storing its fp32 sums.
+ * emp_op_stem_pool: the same followed by the 3x3 stride-2 pad-1 max-pool, in one launch on the matrix pipe -> d_out
+ *   (N,H/4,W/4,64); H, W % 4 == 0.  F16: stem_pool_kernel (conv tile rounded to fp16 before the pool); F32: stem_pool32_kernel.
+ * emp_op_stem3x3s2: 3x3 stride-2 pad-1 conv + bias + ReLU, same normalisation and padding -> d_out (N,H/2,W/2,out_ld), C
+ *   channels written; d_w (9,C) fp32.  F16: stem3x3s2_f16_kernel (C % 8); F32: stem3x3s2_32_kernel (C % 4).
+ * emp_op_maxpool3x3s2: 3x3 stride-2 pad-1 max-pool, -inf padding, (N,H,W,C) -> (N,H/2,W/2,C); H, W even.  Exact.
+ * emp_op_fuse_combine: out = ca * r(a) + cb * b (+ cc * c when d_c is not NULL), b, c, out (N,H,W,C).  mode 0: a is (N,H/2,W/2,C)
+ *   and r the nearest x2 up-sampling (H, W even); mode 1: a is (N,2H,2W,C) and r the 3x3 stride-2 pad-1 max-pool.  F16: rows of
+ *   d_out out_ld apart (0: C); d_out_lo not NULL: the fp32 sum leaves as an fp16 pair, hi = fp16(v) to d_out and lo = fp16(v - hi)
+ *   to d_out_lo (same stride).  F32: fuse_combine32_kernel, dense, d_out_lo NULL and out_ld 0 or C.
+ * emp_op_bilinear_ac_nhwc: F.interpolate(bilinear, align_corners=True) of C channels of (N,h,w,in_ld) into C channels of
+ *   (N,H,W,out_ld); h == H and w == W copies bit for bit.  F16, variant 0: what the network launches (bilinear_ac_up4_kernel
+ *   when W % 4 == 0, 3 (w-1)/(W-1) < 1 and W >= 4 * (256 / (C/8)), unless EMP_BILINEAR_NO_UP4=1 was set when the process made
+ *   its first call; else bilinear_ac_kernel); variant 1: bilinear_ac_kernel; variant 2: bilinear_ac_up4_kernel, EMP_ERR_INVALID
+ *   where those conditions fail.  Both kernels give the same bits.  F32: variant must be 0; bilinear32x4_kernel when W % 4 == 0
+ *   and W >= 4 w, unless EMP_BILINEAR32_X4=0 (read per call), else bilinear32_kernel; same bits.
+ * emp_op_bilinear_ac_nchw_f32: NC planes (h,w) fp32 -> (h*scale, w*scale), align_corners=True (bilinear_ac_f32_kernel).
+ * emp_op_avgpool: mean over the HW pixels of each of C channels of (N,HW,in_ld) -> d_out (N,C) fp32.  F16:
+ *   avgpool_partial_kernel + avgpool_final_kernel (C % 8) with d_work of emp_op_avgpool_work_bytes bytes, which needs no
+ *   initialisation; F32: avgpool32_kernel, no scratch (d_work may be NULL); HL32: avgpool_hl32_kernel on a map made by
+ *   emp_hl32_from_f32 (C, in_ld % 32; rows of 2 * in_ld halfs), no scratch.
+ * emp_op_gemv: out[n][co] = act(sum_k in[n][k] * w[co][k] (+ b[co] when d_b is not NULL)), fp32, act = ReLU when relu != 0
+ *   (gemv_kernel: one wave per output).
+ * emp_op_gate_mul: x * sigmoid(g) per element of `rows` rows of C channels.  F16 (gate_mul_f16_kernel): the result replaces g,
+ *   x is left alone; F32 (gate_mul32_kernel): the result replaces x, g is left alone.
+ * emp_op_dwconv_nhwc_f32: KxK (3 | 5) depthwise conv, stride 1, pad K/2, no bias, taps (K*K, C) fp32: dwconv32_strip_kernel
+ *   when W % 8 == 0 unless EMP_DW32_STRIP=0 (read per call), else dwconv32_kernel; same bits. */
+typedef enum { EMP_OP_F16 = 0, EMP_OP_F32 = 1, EMP_OP_HL32 = 2 } emp_op_prec;
+EMP_API int emp_op_stem7x7(const void* d_img, int image_dtype, float sub, float mul, int N, int H, int W, int vh, int vw,
+                           const float* d_w, const float* d_b, void* d_out, int prec, void* stream);
+EMP_API int emp_op_stem_pool(const void* d_img, int image_dtype, float sub, float mul, int N, int H, int W, int vh, int vw,
+                             const float* d_w, const float* d_b, void* d_out, int prec, void* stream);
+EMP_API int emp_op_stem3x3s2(const void* d_img, int image_dtype, float sub, float mul, int N, int H, int W, int vh, int vw,
+                             const float* d_w, const float* d_b, int C, void* d_out, int out_ld, int prec, void* stream);
+EMP_API int emp_op_maxpool3x3s2(const void* d_in, int N, int H, int W, int C, void* d_out, int prec, void* stream);
+EMP_API int emp_op_fuse_combine(const void* d_a, const void* d_b, const void* d_c, float ca, float cb, float cc, int mode, int N,
+                                int H, int W, int C, void* d_out, void* d_out_lo, int out_ld, int prec, void* stream);
+EMP_API int emp_op_bilinear_ac_nhwc(const void* d_in, int N, int h, int w, int C, int in_ld, void* d_out, int H, int W, int out_ld,
+                                    int prec, int variant, void* stream);
+EMP_API int emp_op_bilinear_ac_nchw_f32(const float* d_in, int NC, int h, int w, float* d_out, int scale, void* stream);
+EMP_API int emp_op_avgpool_work_bytes(int N, int C, int prec, size_t* h_bytes);
+EMP_API int emp_op_avgpool(const void* d_in, int N, int HW, int C, int in_ld, float* d_out, void* d_work, size_t work_bytes,
+                           int prec, void* stream);
+EMP_API int emp_op_gemv(const float* d_in, int N, int K, const float* d_w, const float* d_b, int Cout, int relu, float* d_out,
+                        void* stream);
+EMP_API int emp_op_gate_mul(void* d_x, int x_ld, void* d_g, int g_ld, int64_t rows, int C, int prec, void* stream);
+EMP_API int emp_op_dwconv_nhwc_f32(const float* d_in, int N, int H, int W, int C, int in_ld, const float* d_w, int K, float* d_out,
+                                   int out_ld, void* stream);
+
 /* ------------------------------------------------------------------------
  * 3. Instance post-processing (hot loop 2), one launch group per batch
  * ---------------------------------------------------------------------- */
