@@ -187,6 +187,13 @@ PROTOTYPES = {
     'emp_fill_holes_tile_shape': (c_int, [c_int, C.POINTER(c_int), C.POINTER(c_int), C.POINTER(c_int)]),
     'emp_fill_holes_labels': (c_int, [vp, c_int, c_int, c_int, c_int, c_int, c_int, c_i64, vp, vp, vp, c_i64, vp, vp, c_int, vp, vp, c_i64,
                                       vp, C.POINTER(c_int)]),
+    'emp_split_edt_work_bytes': (sz, [c_i64]),
+    'emp_split_edt': (c_int, [vp, c_int, c_int, c_int, c_int, vp, c_int, vp, vp, c_i64, vp, vp]),
+    'emp_split_peaks_work_bytes': (sz, [c_i64, c_int]),
+    'emp_split_peaks': (c_int, [vp, c_int, vp, c_int, c_int, c_int, vp, c_i64, c_int, vp, c_i64, vp, vp, vp]),
+    'emp_split_flood_work_bytes': (sz, [c_i64, c_i64]),
+    'emp_split_flood': (c_int, [vp, c_int, vp, c_int, c_int, c_int, vp, c_i64, c_int, vp, c_i64, vp, vp, vp, C.POINTER(c_i64)]),
+    'emp_split_write': (c_int, [vp, c_int, c_int, c_int, c_int, vp, c_int, vp, vp, c_i64, vp, vp]),
 }
 
 

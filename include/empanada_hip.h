@@ -907,6 +907,76 @@ EMP_API int emp_fill_holes_labels(void* d_vol, int elem_bytes, int D, int H, int
                                   int64_t n_turns, const int32_t* d_tiles, const int64_t* h_level_offsets, int n_levels,
                                   int32_t* d_parent, int32_t* d_size, int64_t scratch_entries, void* stream, int* h_launches);
 
+/* ------------------------------------------------------------------------
+ * 9. Split Labels (csrc/split.hip): the device side of the plugin's Split
+ *    Labels (empanada_napari/_merge_split_widget.py:422-634) -- distance
+ *    transform, peak candidates, the marker flood and the write-back, batched
+ *    over the boxes of all turns of a call.  The greedy spacing of the peaks,
+ *    ndi.label of the survivors and the id bookkeeping (:527-545) are the
+ *    host's (labels.py, split_labels).
+ *
+ *    A box is 8 int64 {z0, y0, x0, nz, ny, nx, offset, label}: the label's
+ *    TIGHT box (regionprops' bbox, :519; an image is D = 1, nz = 1) and the
+ *    box's first entry in every per-voxel array; a voxel's entry is offset +
+ *    its raster position in the box, and the boxes follow each other without
+ *    gaps.  Every entry takes the boxes from the HOST (h_boxes), checks them
+ *    -- inside the array, nz^2 + ny^2 + nx^2 < 2^30, at most 65535 boxes,
+ *    n_entries < 2^31 - 1 -- and uploads them to d_boxes (8 n_boxes int64).
+ *
+ *    Pinned against scipy, exactly: the distance transform and the maximum
+ *    filter.  Restated from memory and NOT pinned (skimage is not available
+ *    where this library is built): peak_local_max's predicate, and the
+ *    flood's order, which is the level-synchronous form below and not
+ *    skimage's sequential queue.
+ * ---------------------------------------------------------------------- */
+/* what a voxel carries whose row / plane / box holds no background */
+#define EMP_SPLIT_INF (1 << 30)
+/* d_work of emp_split_edt: three int32 arrays of n_entries */
+EMP_API size_t emp_split_edt_work_bytes(int64_t n_entries);
+/* `ndi.distance_transform_edt(crop == label)` (_merge_split_widget.py:429), SQUARED and exact: d_d2[entry] = the squared
+ * Euclidean distance (int32) to the nearest voxel of the CROP that is not the label; voxels outside the crop are not
+ * background.  A row scan, then per remaining axis the lower envelope of parabolas.  A box without any background is
+ * EMP_SPLIT_INF everywhere (scipy returns an artefact there; the caller treats such a label as "nothing to split").
+ * d_vol (D, H, W; elem_bytes as in section 7) is only read.  Does not synchronise. */
+EMP_API int emp_split_edt(const void* d_vol, int elem_bytes, int D, int H, int W, const int64_t* h_boxes, int n_boxes, int64_t* d_boxes,
+                          int32_t* d_d2, int64_t n_entries, void* d_work, void* stream);
+EMP_API size_t emp_split_peaks_work_bytes(int64_t n_entries, int n_boxes);
+/* The candidates of `peak_local_max(distance, min_distance=d)` (_merge_split_widget.py:435,442) before its spacing rule, from
+ * any int32 image per box (d_d2): a voxel with value == the maximum of the (2d + 1)^n window around it clamped to the box
+ * (ndi.maximum_filter(size=2d + 1, mode='nearest')), value > the box's minimum (threshold_abs = image.min()), and not within d
+ * voxels of either end of an axis (exclude_border=True); axes of length 1 take no part (the squeeze of :434-440).  A constant
+ * box has no candidate.  d = min_distance in 1..100 (the widget's slider, :461).
+ *   d_cand[3 i]      {box, raster position in the box, value} in raster order, box after box; only the first cand_capacity
+ *                    are written
+ *   d_box_counts[b]  the number of candidates of box b, written or not: their sum says whether the capacity was enough
+ * Does not synchronise the results (it synchronises once on its own upload). */
+EMP_API int emp_split_peaks(const int64_t* h_boxes, int n_boxes, int64_t* d_boxes, int D, int H, int W, const int32_t* d_d2,
+                            int64_t n_entries, int min_distance, int32_t* d_cand, int64_t cand_capacity, int32_t* d_box_counts,
+                            void* d_work, void* stream);
+EMP_API size_t emp_split_flood_work_bytes(int64_t n_entries, int64_t n_markers);
+/* `watershed(energy, markers, mask=binary)` (_merge_split_widget.py:530) in its level-synchronous form.  The mask is d_d2 > 0;
+ * the energy is -d_d2 (plateau == 0, distance mode, :430) or constant (plateau != 0, points mode, :455).
+ *   every mask voxel gets a time (L, g) and a label; a marker voxel has time (e, 0) and its marker's id; any other voxel q takes
+ *   the label of the face neighbour p in the mask (4 in an image, 6 in a volume) with the lexicographically smallest
+ *   (L_p, g_p, label_p), and the time (L_p, g_p + 1) if e(q) <= L_p, else (e(q), 0).
+ * Times strictly increase along a claim chain, so the solution is unique; it is found by recomputing every voxel from its
+ * neighbours' values of the sweep before until a sweep changes nothing (no atomic minimum: a stale label with an equal time would
+ * stick).  skimage's flood is a sequential priority queue over (value, age): on one plateau (points mode) the two agree on
+ * every voxel; in distance mode a few per cent of a label's voxels, next to the border between two regions, can differ.
+ *   h_markers[3 i]  {box, raster position in the box, id}, id in 1..2^30 - 1 (host memory); one on a voxel outside the mask is ignored
+ *   d_out[entry]    the id that claimed the voxel; 0 outside the mask and in a part of the mask no marker reaches
+ *   *h_sweeps       the number of sweeps, the last one, which changed nothing, included
+ * Synchronises: the change flags come back every 8 sweeps. */
+EMP_API int emp_split_flood(const int64_t* h_boxes, int n_boxes, int64_t* d_boxes, int D, int H, int W, const int32_t* d_d2,
+                            int64_t n_entries, int plateau, const int32_t* h_markers, int64_t n_markers, int32_t* d_out, void* d_work,
+                            void* stream, int64_t* h_sweeps);
+/* `labels[slices][binary] = new_labels[binary] + max_label` (_merge_split_widget.py:544), IN PLACE on d_vol: every voxel of box b
+ * that holds the box's label becomes d_bases[b] + d_markers[entry] (so a voxel that no marker reached becomes d_bases[b], as in
+ * the reference).  d_bases[b] < 0: the turn writes nothing ("nothing to split", or the ids are in use, :540-542).  The new ids
+ * must not occur in the array and must fit the element type: the host's bookkeeping sees to both.  Does not synchronise. */
+EMP_API int emp_split_write(void* d_vol, int elem_bytes, int D, int H, int W, const int64_t* h_boxes, int n_boxes, int64_t* d_boxes,
+                            const int32_t* d_markers, int64_t n_entries, const int64_t* d_bases, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,14 +1,17 @@
 """Clean up a label volume on the device and print one JSON object: the plugin's Filter Small Labels, Delete Labels, Merge Labels,
-Count Labels and Morph Labels on a file.
+Count Labels, Morph Labels and Split Labels on a file.
 Usage: python tools/clean_labels.py IN [OUT] [--min-area N | --boundary [--whole-labels] | --delete IDS | --merge IDS [--into ID] |
                                              --count --label-divisor D | --morph OP [--radius R] [--3d] |
-                                             --fill-holes [HOLE_SIZE] [--radius R] [--3d]] [--per-slice]
+                                             --fill-holes [HOLE_SIZE] [--radius R] [--3d] |
+                                             --split IDS [--min-distance D] [--3d]] [--per-slice]
 IN / OUT: .npy files (IN is memory-mapped and streamed in slabs, OUT is created) or zarr array directories (OUT is created with
 IN's shape, dtype and chunks).  IDS: comma-separated label ids.  --count needs no OUT.  --morph OP: Dilate, Erode, Close or Open
 of every label with a disk of radius R (a 2-D IN) or, with --3d, a ball (a 3-D IN); IN must be a .npy file (the whole array goes
 to the device); labels_affected is the number of labels that had a turn.  --fill-holes [HOLE_SIZE]: Morph Labels' 'Fill holes' on
 every label: the holes of fewer than HOLE_SIZE voxels (default 64) inside the label's box padded by R; same rules and the same JSON
-line as --morph."""
+line as --morph.  --split IDS: Split Labels in distance mode on the labels named: each is cut into the basins of a watershed from
+the peaks of its distance transform that are at least D apart (default 10) and the pieces get fresh ids above the array's maximum;
+IN must be a .npy file; labels_affected is the number of labels that were split, and `new_ids` lists their pieces."""
 import argparse
 import json
 import os
@@ -57,8 +60,10 @@ def main(argv=None):
     op.add_argument('--count', action='store_true')
     op.add_argument('--morph', choices=list(L.MORPH_OPS), metavar='OP')
     op.add_argument('--fill-holes', type=int, nargs='?', const=64, default=None, metavar='HOLE_SIZE')
+    op.add_argument('--split', type=_ids, metavar='IDS')
+    ap.add_argument('--min-distance', type=int, default=10, help='--split: the least distance between two peaks, 1..100')
     ap.add_argument('--radius', type=int, default=1, help='--morph: radius of the disk / ball, 1..7; --fill-holes: the padding of the box')
-    ap.add_argument('--3d', dest='apply3d', action='store_true', help='--morph / --fill-holes: the ball / the volume\'s components on a 3-D array')
+    ap.add_argument('--3d', dest='apply3d', action='store_true', help='--morph / --fill-holes / --split: the ball / the volume\'s components / the volume\'s watershed on a 3-D array')
     ap.add_argument('--whole-labels', action='store_true')
     ap.add_argument('--into', type=int, default=None, help='--merge: the id the others become (default: the smallest)')
     ap.add_argument('--label-divisor', type=int, default=0)
@@ -85,7 +90,15 @@ def main(argv=None):
             res = fn(src, *a, out=dst, **k)
         return res[1] if isinstance(res, tuple) else None
 
-    if args.morph is not None or args.fill_holes is not None:
+    extra = {}
+    if args.split is not None:
+        if not isinstance(src, np.ndarray):
+            ap.error('--split needs a .npy input: the whole array goes to the device')
+        res, report = L.split_labels(np.asarray(src), ids=args.split, min_distance=args.min_distance, apply3d=args.apply3d, report=True)
+        dst[...] = res
+        extra['new_ids'] = {str(label): [int(v) for v in new] for label, new in report if not isinstance(new, str)}
+        n = len(extra['new_ids'])
+    elif args.morph is not None or args.fill_holes is not None:
         n = len(np.unique(src)) - int((np.asarray(src) == 0).any())
         if args.morph is not None:
             run(L.morph_labels, args.morph, radius=args.radius, apply3d=args.apply3d)
@@ -104,7 +117,7 @@ def main(argv=None):
             run(L.merge_labels, ids, new_label_id=args.into)
     if hasattr(dst, 'flush'):
         dst.flush()
-    out = {'shape': list(src.shape), 'labels_affected': int(n), 'out': args.dst}
+    out = {'shape': list(src.shape), 'labels_affected': int(n), 'out': args.dst, **extra}
     print(json.dumps(out))
     return out
 
