@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string>
 
 #include "../../include/empanada_hip.h"
@@ -46,6 +47,11 @@ int ensure_dyn_lds(const void* kernel, int bytes);
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// Environment switches, read where they are called (no process-wide cache).  env_on: on unless the value starts with '0'
+static inline bool env_on(const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); }
+static inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+static inline int64_t env_i64(const char* name, int64_t dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; }
 
 // ---------------------------------------------------------------------------
 // implicit-GEMM convolution (conv_igemm.hip)

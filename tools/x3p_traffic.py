@@ -22,7 +22,7 @@ def per_dispatch(d, counter):
 
 
 def algorithmic_bytes(B):
-    """the plane region of PanopticDeepLabPR / resnet50 at 1024^2 (pdl_net.hip run32): per launch input map + packed weights +
+    """the plane region of PanopticDeepLabPR / resnet50 at 1024^2 (pdl_net32.hip run32): per launch input map + packed weights +
     output (+ residual), 4 B per element (hl32 or fp32), one pass each"""
     M = B * 64 * 64
     L = []      # (M_in, Cin, K, Cout, res)
