@@ -95,7 +95,7 @@ __global__ void __launch_bounds__(256) median_kernel(MedianPtrs ptrs, int ks, fl
 
 // recursive median over a run of consecutive slices in ONE launch (the z recursion is per pixel, so
 // a thread walks its pixel through the slices, carrying the filtered history in registers):
-//   hist: (mid, count) filtered maps preceding the run (only if n_hist == mid), raw: (n_raw, count) raw maps
+//   hist: (mid, count) filtered maps preceding the run (all mid are always read: the entry requires the pointer), raw: (n_raw, count) raw maps
 //   out[j] = median(hist/out[j-mid..j-1], raw[j..j+mid]) for j in [0, n_out); needs n_raw >= n_out + mid
 // out MAY BE raw (in place: map j is in registers before out[j] is stored, maps beyond j + mid are read later), so
 // neither pointer is __restrict__: a whole slab is filtered without a second slab-sized buffer (multigpu.py)

@@ -2,6 +2,7 @@
 
     python oracle/gen_golden.py            # needs /root/reference, CPU only
     python oracle/gen_golden.py exports    # the TorchScript export fixtures of tests/test_load_export.py
+    python oracle/gen_golden.py postprocess_edges    # the post-processing edge cases of tests/postprocess_case.py
 
 The reference cannot travel to the GPU box, so its outputs on seeded inputs are
 committed as small fixtures; the inputs are either stored next to them or are
@@ -585,3 +586,44 @@ def gen_exports():
 
 if __name__ == '__main__' and 'exports' in sys.argv[1:]:
     gen_exports()
+
+
+# ----------------------------------------------------------------------------
+# post-processing edge cases: the reference's own centres, groups, cells and panoptic maps on the inputs of
+# tests/postprocess_case.py (EDGE_CASES) -- void_label 255, thing lists [2] and [1, 2] of four classes, stuff_area on both sides
+# of a class count, nms_kernel 1 and 5, 20 and 21 centres, upsampling 2
+# ----------------------------------------------------------------------------
+def gen_postprocess_edges():
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import postprocess_case as PP
+    from empanada.inference import postprocess as pp
+    from empanada.inference.engines import PanopticDeepLabRenderEngine, logits_to_prob
+
+    class Fake(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.p = torch.nn.Parameter(torch.zeros(1))
+
+    out = {}
+    for name in sorted(PP.EDGE_CASES):
+        e = PP.edge_inputs(name)
+        tctr, toff = torch.from_numpy(e['ctr']), torch.from_numpy(e['off'])
+        eng = PanopticDeepLabRenderEngine(Fake(), thing_list=e['things'], label_divisor=PP.EDGE_DIVISOR, stuff_area=e['stuff_area'],
+                                          void_label=e['void_label'], nms_threshold=PP.EDGE_THR, nms_kernel=e['k'],
+                                          confidence_thr=PP.MERGE_THR, padding_factor=16, coarse_boundaries=e['coarse'])
+        centers = pp.find_instance_center(tctr.clone(), PP.EDGE_THR, e['k'])
+        out[f'{name}_centers'] = centers.numpy()
+        if centers.size(0) > 0:
+            out[f'{name}_groups'] = pp.group_pixels(centers, toff, step=e['step']).numpy()
+        cells = eng.get_instance_cells(tctr.clone(), toff, e['upsampling'])
+        if e['upsampling'] * e['step'] > 1:      # (otherwise the cells are the groups)
+            out[f'{name}_cells'] = cells.numpy().astype(np.int32)
+        if name.startswith('stuff_'):
+            out[f'{name}_stuff_area'] = np.int64(e['stuff_area'])
+        if e['upsampling'] == 1:
+            out[f'{name}_pan'] = eng.postprocess(logits_to_prob(torch.from_numpy(e['sem_logits'])), cells).numpy()
+    save('postprocess_edges', **out)
+
+
+if __name__ == '__main__' and 'postprocess_edges' in sys.argv[1:]:
+    gen_postprocess_edges()

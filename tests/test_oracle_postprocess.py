@@ -10,6 +10,7 @@ from empanada_napari_amd import synth
 from oracle import postprocess as opp
 
 NSPEC = 9
+GOLDEN_EDGES = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'postprocess_edges.npz')
 
 
 def _case(g, i):
@@ -87,3 +88,39 @@ def test_recursive_median_scalar(golden_dir):
     out += [float(o['sem']) for o in list(q.median_queue)[q.mid_idx + 1:]]
     np.testing.assert_array_equal(np.array(out, np.float32), g['scalar_out'])
     assert list(g['scalar_out']) == [5, 5, 5, 5, 5, 2]  # recursive, not sliding
+
+
+def _edge_names():
+    import postprocess_case as PP
+    return sorted(PP.EDGE_CASES)
+
+
+@pytest.mark.parametrize('name', _edge_names())
+def test_oracle_reproduces_the_edge_fixture(golden_dir, name):
+    """tests/golden/postprocess_edges.npz: the reference project's centres, groups, cells and panoptic maps on the inputs of
+    tests/postprocess_case.py -- void_label 255, thing lists [2] and [1, 2] of four classes, stuff_area at and above a class
+    count, nms_kernel 1 and 5, 20 and 21 centres, upsampling 2 on both boundary modes"""
+    import postprocess_case as PP
+    g = np.load(os.path.join(golden_dir, 'postprocess_edges.npz'))
+    got = PP.edge_oracle(name)
+    e = PP.edge_inputs(name)
+    keys = {k[len(name) + 1:] for k in g.files if k.startswith(name + '_')} - {'stuff_area'}
+    assert keys == set(got) and ('cells' in keys) == (e['upsampling'] * e['step'] > 1)
+    for k in keys:
+        assert got[k].shape == g[f'{name}_{k}'].shape
+        np.testing.assert_array_equal(got[k], g[f'{name}_{k}'], err_msg=k)
+    if name.startswith('stuff_'):
+        assert int(g[f'{name}_stuff_area']) == e['stuff_area']
+    if 'pan' in keys:
+        assert e['void_label'] == 0 or name == 'stuff_at' or (got['pan'] == e['void_label']).any()
+    if name in ('k20', 'k21'):
+        assert got['centers'].shape[0] == int(name[1:])
+
+
+def test_edge_fixture_stuff_area_decides():
+    import postprocess_case as PP
+    g = np.load(os.path.join(GOLDEN_EDGES))
+    assert int(g['stuff_above_stuff_area']) == int(g['stuff_at_stuff_area']) + 1
+    flipped = g['stuff_at_pan'] != g['stuff_above_pan']
+    assert flipped.sum() == int(g['stuff_at_stuff_area']) and (g['stuff_above_pan'][flipped] == 255).all()
+    assert os.path.getsize(GOLDEN_EDGES) < 24 * 1024
