@@ -1,5 +1,6 @@
-// What the streaming kernels over label arrays share (overlap.hip, labels.hip): the hash of their open-addressing tables
-// and the load of E consecutive elements of 1, 2, 4 or 8 bytes as raw unsigned values.
+// What the streaming kernels over label arrays share (overlap.hip, labels.hip, measure.hip): the hash of their open-addressing
+// tables, the load of E consecutive elements of 1, 2, 4 or 8 bytes as raw unsigned values, and the division that turns a raster
+// offset into coordinates.
 #pragma once
 #include "common.h"
 
@@ -73,6 +74,21 @@ __device__ __forceinline__ void ov_store(void* base, int64_t i0, int nv, int vec
     for (int j = 0; j < E; ++j)
       if (j < nv) p[j] = (T)v[j];
   }
+}
+
+// x / d for x < d + 2^13 (d < 2^31 - 2^13) from the float reciprocal of d: the estimate is off by one at most
+__device__ __forceinline__ uint32_t ov_div(uint32_t x, uint32_t d, float inv, uint32_t& rem) {
+  uint32_t q = (uint32_t)((float)x * inv);
+  int32_t r = (int32_t)(x - q * d);
+  if (r < 0) {
+    --q;
+    r += (int32_t)d;
+  } else if ((uint32_t)r >= d) {
+    ++q;
+    r -= (int32_t)d;
+  }
+  rem = (uint32_t)r;
+  return q;
 }
 
 }  // namespace emp

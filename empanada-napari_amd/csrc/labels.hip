@@ -137,29 +137,14 @@ __device__ __forceinline__ void lt_lds_add(const LtCtx& c, uint64_t key, uint64_
   lt_global_add(c.t, key, c.negate ? 0ull - w : w, r, !c.negate);
 }
 
-// x / d for x < d + 2^13 (d < 2^31 - 2^13) from the float reciprocal of d: the estimate is off by one at most
-__device__ __forceinline__ uint32_t lt_div(uint32_t x, uint32_t d, float inv, uint32_t& rem) {
-  uint32_t q = (uint32_t)((float)x * inv);
-  int32_t r = (int32_t)(x - q * d);
-  if (r < 0) {
-    --q;
-    r += (int32_t)d;
-  } else if ((uint32_t)r >= d) {
-    ++q;
-    r -= (int32_t)d;
-  }
-  rem = (uint32_t)r;
-  return q;
-}
-
 // offset o (<= 2^12) from the voxel (bz, by, bx) in raster order
 __device__ __forceinline__ void lt_coord(const LtCtx& c, uint32_t bx, uint32_t by, uint32_t bz, uint32_t o, uint32_t& x, uint32_t& y, uint32_t& z) {
   x = bx + o;
   y = by;
   z = bz;
   if (x >= c.W) {
-    y += lt_div(x, c.W, c.invW, x);
-    if (y >= c.H) z += lt_div(y, c.H, c.invH, y);
+    y += ov_div(x, c.W, c.invW, x);
+    if (y >= c.H) z += ov_div(y, c.H, c.invH, y);
   }
 }
 

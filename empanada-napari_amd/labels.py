@@ -34,6 +34,10 @@ against them.  ``count_labels`` is pure numpy in the reference and is pinned (te
 The one deliberate difference: on an image without labels the reference's ``filter_out_small_label_areas`` dies with an
 ``IndexError`` (``.iloc[0]`` of an empty frame, _filter_small_labels.py:20); here that case returns the image unchanged and 0.
 
+``measure_labels`` (csrc/measure.hip) measures the objects of a label array in one pass: per label its voxel count, box, the raw
+first and second moments of its voxel coordinates and its exposed voxel faces per axis, all integers; ``LabelMeasures`` derives
+centroids, volumes, face surfaces, covariances and principal axes from them as pure numpy.
+
 There is no numpy fallback: without the HIP library or a device the device entries raise like every other entry of the package.
 """
 import ctypes as C
@@ -45,7 +49,7 @@ import torch
 from . import _abi
 from ._labelstream import GrowableTable, RawSource, ebytes, hp, initial_capacity, need_device, pick_device, slab_plan, source, stream_slabs
 
-__all__ = ['LabelTable', 'label_table', 'table_from_arrays', 'small_labels', 'boundary_labels', 'count_labels', 'class_label_lists',
+__all__ = ['LabelTable', 'label_table', 'table_from_arrays', 'LabelMeasures', 'measure_labels', 'measures_from_arrays', 'small_labels', 'boundary_labels', 'count_labels', 'class_label_lists',
            'next_available_labels', 'next_available_label', 'label_bbox', 'delete_labels', 'merge_labels',
            'filter_out_small_label_areas', 'remove_boundary_labels', 'morph_labels', 'fill_label_holes', 'morph_schedule',
            'morph_footprint_rows', 'morph_footprint_offsets', 'split_labels', 'split_spacing', 'split_marker_ids']
@@ -137,6 +141,220 @@ def label_table(labels, per_slice=False, device=None, slab=None, capacity=None):
     with torch.cuda.device(device):
         src = source(labels, device)
         return _table_of_source(src, src.shape, bool(per_slice), device, slab, capacity)
+
+
+# ----------------------------------------------------------------------------
+# device: the measures
+# ----------------------------------------------------------------------------
+_PAIRS = {3: ((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)), 2: ((0, 0), (1, 1), (0, 1))}      # the columns of sum2
+
+
+@dataclass
+class LabelMeasures:
+    """What ``measure_labels`` counts, per label that occurs (background 0 left out), and what follows from it.
+
+    The raw columns are integers and exact.  ``labels`` ascending, ``areas`` the voxel counts, ``boxes`` as ``LabelTable``'s;
+    ``sum1`` (k, ndim) the sums of the voxels' index coordinates; ``sum2`` (k, 6) the sums of zz, yy, xx, zy, zx, yx, or (k, 3) of
+    yy, xx, yx; ``faces`` (k, ndim) the exposed voxel faces perpendicular to each axis.  ndim is 3 for a volume and 2 for an image
+    or, per slice, for the images of a stack: there is no z column then, columns read (y, x), ``slices`` holds the leading-axis
+    index and rows are sorted by slice, then label.  ``spacing``: the voxel size per column; ``doublings``: how often the device
+    table had to grow.
+
+    Everything derived is pure numpy on these columns.  Coordinates are index coordinates (a voxel is the point at its index,
+    ``regionprops``' convention), ``*_physical`` and everything with a unit is scaled by ``spacing``."""
+    labels: np.ndarray
+    areas: np.ndarray
+    boxes: np.ndarray
+    sum1: np.ndarray
+    sum2: np.ndarray
+    faces: np.ndarray
+    slices: object = None
+    shape: tuple = ()
+    spacing: tuple = ()
+    doublings: int = 0
+
+    @property
+    def per_slice(self):
+        return self.slices is not None
+
+    @property
+    def ndim(self):
+        return self.sum1.shape[1]
+
+    @property
+    def centroid(self):
+        """(k, ndim) mean index coordinate, ``regionprops``' ``centroid``: one division of two exact integers"""
+        return self.sum1 / self.areas[:, None]
+
+    @property
+    def centroid_physical(self):
+        return self.centroid * np.asarray(self.spacing, dtype=np.float64)
+
+    @property
+    def volume(self):
+        """voxel count times the voxel's volume (its area for ndim 2)"""
+        return self.areas * float(np.prod(self.spacing))
+
+    @property
+    def surface_area(self):
+        """The voxel-face surface: every exposed face with the area the spacing gives it.  It is the surface of the voxel
+        model, not of a smooth object: for a smooth surface it overestimates by the ratio of the L1 to the L2 norm of the
+        normal, up to 1.5 for a sphere (sqrt(3) on a diagonal plane).  For ndim 2 it is the pixel-edge perimeter
+        (``perimeter_faces``)."""
+        sp = np.asarray(self.spacing, dtype=np.float64)
+        face = np.array([np.prod(np.delete(sp, a)) for a in range(self.ndim)])
+        return (self.faces * face).sum(axis=1)
+
+    @property
+    def perimeter_faces(self):
+        if self.ndim != 2:
+            raise ValueError('perimeter_faces: for images; a volume has a surface_area')
+        return self.surface_area
+
+    @property
+    def equivalent_diameter(self):
+        """the diameter of the ball (the disk for ndim 2) of the same volume"""
+        v = self.volume
+        return np.cbrt(6.0 * v / np.pi) if self.ndim == 3 else np.sqrt(4.0 * v / np.pi)
+
+    @property
+    def sphericity(self):
+        """pi^(1/3) (6 V)^(2/3) / A with the voxel-face surface A (for ndim 2 the circularity 4 pi A / P^2 with the pixel-edge
+        perimeter).  A is the face surface, so no voxel object reaches 1: a cube has (pi / 6)^(1/3) = 0.806, a large digital
+        ball about 2 / 3"""
+        v, a = self.volume, self.surface_area
+        with np.errstate(divide='ignore', invalid='ignore'):
+            return np.cbrt(np.pi) * np.cbrt(6.0 * v) ** 2 / a if self.ndim == 3 else 4.0 * np.pi * v / a ** 2
+
+    def central_moments_exact(self):
+        """(k, ndim, ndim) Python integers n sum(ab) - sum(a) sum(b): n^2 times the central second moments of the index
+        coordinates.  The raw sums reach 2^60, so the subtraction is done before anything is rounded."""
+        n = self.areas.astype(object)
+        s1, s2 = self.sum1.astype(object), self.sum2.astype(object)
+        m = np.empty((len(n), self.ndim, self.ndim), dtype=object)
+        for j, (a, b) in enumerate(_PAIRS[self.ndim]):
+            m[:, a, b] = m[:, b, a] = n * s2[:, j] - s1[:, a] * s1[:, b]
+        return m
+
+    @property
+    def covariance(self):
+        """(k, ndim, ndim) covariance of the voxel positions in physical units (voxels as points; one division of exact integers)"""
+        n = self.areas.astype(object)
+        cov = (self.central_moments_exact() / (n * n)[:, None, None]).astype(np.float64)
+        sp = np.asarray(self.spacing, dtype=np.float64)
+        return cov * sp[:, None] * sp[None, :]
+
+    @property
+    def principal_variances(self):
+        """(k, ndim) eigenvalues of ``covariance``, largest first"""
+        return np.linalg.eigvalsh(self.covariance)[:, ::-1] if len(self.labels) else np.zeros((0, self.ndim))
+
+    @property
+    def principal_axes(self):
+        """(k, ndim, ndim): ``[i, j]`` is the unit vector (in the columns' axis order) of label i's j-th principal variance"""
+        if not len(self.labels):
+            return np.zeros((0, self.ndim, self.ndim))
+        return np.linalg.eigh(self.covariance)[1][:, :, ::-1].transpose(0, 2, 1)
+
+    def to_table(self):
+        """dict of columns, ``regionprops_table``'s naming where it has one (``bbox-0``, ``centroid-1``, ...)"""
+        nd = self.ndim
+        out = {'slice': self.slices} if self.per_slice else {}
+        out.update({'label': self.labels, 'area': self.areas})
+        out.update({f'bbox-{i}': self.boxes[:, i] for i in range(2 * nd)})
+        c, pv = self.centroid_physical, self.principal_variances
+        out.update({f'centroid-{i}': c[:, i] for i in range(nd)})
+        out.update({'volume': self.volume, 'surface_area': self.surface_area, 'equivalent_diameter': self.equivalent_diameter,
+                    'sphericity': self.sphericity})
+        out.update({f'principal_variance-{i}': pv[:, i] for i in range(nd)})
+        return out
+
+    def to_csv(self, path):
+        import csv
+        table = self.to_table()
+        with open(path, 'w', newline='') as f:
+            w = csv.writer(f)
+            w.writerow(table)
+            w.writerows(zip(*(col.tolist() for col in table.values())))
+
+
+def _spacing(spacing, nd, per_slice):
+    if spacing is None:
+        return (1.0,) * nd
+    sp = tuple(float(v) for v in np.asarray(spacing, dtype=np.float64).reshape(-1))
+    if per_slice and len(sp) == 3:      # a stack's (z, y, x): the images have (y, x)
+        sp = sp[1:]
+    if len(sp) != nd or not all(v > 0 for v in sp):
+        raise ValueError(f'measure_labels: spacing needs {nd} positive values, got {spacing}')
+    return sp
+
+
+def measures_from_arrays(labels, areas, boxes, sum1, sum2, faces, shape, spacing=None, slices=None, doublings=0):
+    """LabelMeasures from host arrays (rows in any order, each key once)."""
+    shape = tuple(int(s) for s in shape)
+    nd = 2 if slices is not None else len(shape)
+    cols = [np.asarray(labels, dtype=np.int64).reshape(-1), np.asarray(areas, dtype=np.int64).reshape(-1),
+            np.asarray(boxes, dtype=np.int64).reshape(-1, 2 * nd), np.asarray(sum1, dtype=np.int64).reshape(-1, nd),
+            np.asarray(sum2, dtype=np.int64).reshape(-1, len(_PAIRS[nd])), np.asarray(faces, dtype=np.int64).reshape(-1, nd)]
+    if len({len(c) for c in cols}) != 1:
+        raise ValueError('measures_from_arrays: the columns differ in length')
+    if slices is not None:
+        slices = np.asarray(slices, dtype=np.int64).reshape(-1)
+        order = np.lexsort((cols[0], slices))
+        slices = slices[order]
+    else:
+        order = np.argsort(cols[0], kind='stable')
+    return LabelMeasures(*(c[order] for c in cols), slices, shape, _spacing(spacing, nd, slices is not None), int(doublings))
+
+
+MEASURE_MAX_CAPACITY = 1 << 20      # first size of the table at most: a slot is 136 bytes
+
+
+def _measures_of_source(src, shape, spacing, per_slice, border_faces, device, slab, capacity):
+    rows, H, W = _geometry(shape, per_slice, 'measure_labels')
+    nd = 2 if per_slice else len(shape)
+    spacing = _spacing(spacing, nd, per_slice)
+    if max(rows, H, W) ** 2 * rows * H * W >= 1 << 63:      # the entry's own rule, before anything is allocated
+        raise ValueError(f'measure_labels: a raw second moment could wrap: max(D, H, W)^2 * D * H * W must stay below 2^63, got shape {shape}')
+    table = GrowableTable('emp_label_measure', 'measure_labels', capacity or min(initial_capacity(rows * H * W), MEASURE_MAX_CAPACITY), device)
+    # The slice below a slab's first one.  A device source has it in front of the slab.  A host source's previous slab lies in
+    # the staging slot that the stream refills while this slab is counted, so its last slice is kept in a buffer of its own
+    host_halo = src.is_host and not per_slice
+    halo = torch.empty(max(1, src.row_bytes), dtype=torch.uint8, device=device) if host_halo else None
+    stream = torch.cuda.current_stream(device)
+    for _, z0, z1, (address,) in stream_slabs([src], slab, device):
+        below = None if per_slice or z0 == 0 else (halo.data_ptr() if host_halo else address - src.row_bytes)
+        table.add(address, src.ebytes, z0, z1 - z0, H, W, rows, below, int(per_slice), int(bool(border_faces)))
+        if host_halo and z1 < rows:
+            # `add` has synchronised before this copy is queued: wait for it too, or the refill of this slot could overtake it
+            _abi.check(table.lib.emp_copy_d2d(_abi.ptr(halo), address + (z1 - z0 - 1) * src.row_bytes, src.row_bytes, _abi.stream_ptr(device)),
+                       'emp_copy_d2d')
+            stream.synchronize()
+    keys, cnt, box, sums, faces = (t.cpu().numpy() for t in table.finalize(extra=[(6, torch.int32), (9, torch.int64), (3, torch.int64)]))
+    box = box.astype(np.int64)
+    box[:, 3:] += 1      # exclusive upper ends
+    s1, s2 = sums[:, :3], sums[:, 3:]
+    if per_slice:      # the images' (y, x); the kernel's z is the slice
+        return LabelMeasures(keys & 0xffffffff, cnt, box[:, [1, 2, 4, 5]], s1[:, [1, 2]], s2[:, [1, 2, 5]], faces[:, [1, 2]], keys >> 32,
+                             tuple(shape), spacing, table.doublings)
+    if len(shape) == 2:      # kernel (z, y, x) = image (y, 0, x): zz, xx, zx are the image's yy, xx, yx
+        return LabelMeasures(keys, cnt, box[:, [0, 2, 3, 5]], s1[:, [0, 2]], s2[:, [0, 2, 4]], faces[:, [0, 2]], None, tuple(shape), spacing,
+                             table.doublings)
+    return LabelMeasures(keys, cnt, box, s1, s2, faces, None, tuple(shape), spacing, table.doublings)
+
+
+@torch.no_grad()
+def measure_labels(labels, spacing=None, per_slice=False, border_faces=True, device=None, slab=None, capacity=None):
+    """The ``LabelMeasures`` of a 2-D or 3-D label array: sources, dtypes, value domain, ``per_slice``, ``slab`` and ``capacity``
+    as ``label_table``; label 0 is background and is not measured.  ``spacing``: the voxel size per axis (default 1).
+    ``border_faces``: a voxel on a face of the array exposes a face to the outside (default); False counts only faces between
+    voxels of the array.  The raw columns are exact, do not depend on ``slab`` and are bit-reproducible.  Shapes with
+    max(D, H, W)^2 * D * H * W >= 2^63 raise ``ValueError``: a raw second moment could wrap."""
+    need_device()
+    device = pick_device(device, labels)
+    with torch.cuda.device(device):
+        src = source(labels, device)
+        return _measures_of_source(src, src.shape, spacing, bool(per_slice), border_faces, device, slab, capacity)
 
 
 # ----------------------------------------------------------------------------

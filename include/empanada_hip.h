@@ -840,6 +840,52 @@ EMP_API int emp_label_apply_map(const void* d_key, int key_bytes, const void* d_
                                  int64_t map_capacity, void* stream);
 
 /* ------------------------------------------------------------------------
+ * 7b. Measure Labels (csrc/measure.hip): per label that occurs, background 0
+ *    excepted, what regionprops_table is asked for after a segmentation:
+ *    `area` (the voxel count), `bbox`, and the raw sums behind `centroid`
+ *    (sum of each coordinate / area), `moments` (sum z^a y^b x^c up to order 2)
+ *    and `inertia_tensor` (from the central second moments); plus the number
+ *    of exposed voxel faces per axis, this library's statement of a surface
+ *    (regionprops' `perimeter` is a weighted boundary-pixel count and is not
+ *    reproduced).  As in section 7 skimage is not available where this
+ *    library is built: everything is restated from documented behaviour and
+ *    is NOT pinned against it; the tests state it in numpy / scipy.
+ *
+ *    The table has the life cycle and the overflow contract of sections 6 and
+ *    7.  All sums are uint64 and exact.
+ * ---------------------------------------------------------------------- */
+/* 0 if the capacity is not a power of two in [64, 2^32] */
+EMP_API size_t emp_label_measure_work_bytes(int64_t capacity);
+EMP_API int emp_label_measure_reset(void* d_table, int64_t capacity, void* stream);
+/* Adds the slab d_labels (depth, H, W), slices [z0, z0 + depth) of a volume of total_depth slices, to the table.  in_bytes, the
+ * keys (per_slice 0: the label in [0, 2^63); 1: slice << 32 | label, labels in [0, 2^32)) and the error for values outside the
+ * domain are those of emp_label_table_accumulate, except that label 0 is background and is never entered.  Per key:
+ *   count          the voxels (regionprops_table's `area`)
+ *   box            min / max of z, y, x in global coordinates (`bbox`)
+ *   S1             sum z, sum y, sum x (`centroid` = S1 / count; `moments` of order 1)
+ *   S2             sum zz, yy, xx, zy, zx, yx (`moments` of order 2; n S2 - S1 S1 are n^2 times the central moments behind
+ *                  `inertia_tensor`)
+ *   F              faces perpendicular to z, y, x: one per voxel of the label and direction in which the neighbour has another
+ *                  value, 0 included; with border_faces != 0 also where the neighbour lies outside the array (the first and
+ *                  last index of each axis; for z: slices 0 and total_depth - 1)
+ * d_halo: slice z0 - 1 (H * W elements of the same type) on the device, so that z-faces across the slab's lower border are
+ * counted; NULL for z0 == 0.  With per_slice 1 no z-faces are counted and d_halo is not read.  Shapes with
+ * max(D, H, W)^2 * D * H * W >= 2^63 are EMP_ERR_INVALID: a raw second moment could wrap.  Synchronises the stream.
+ * *h_overflow = 1: the table is too small for this slab; the call has removed what it had added (box fields are idempotent and
+ * stay): move the table to a larger one with emp_label_measure_grow and call again. */
+EMP_API int emp_label_measure_accumulate(const void* d_labels, int in_bytes, int64_t z0, int depth, int H, int W, int64_t total_depth,
+                                 const void* d_halo, int per_slice, int border_faces, void* d_table, int64_t capacity, void* stream,
+                                 int* h_overflow);
+/* Re-inserts the counted cells of d_from into the reset, larger table d_to.  Synchronises.  *h_overflow = 1: d_to is too small too. */
+EMP_API int emp_label_measure_grow(const void* d_from, int64_t from_capacity, void* d_to, int64_t to_capacity, void* stream,
+                                 int* h_overflow);
+/* *h_num = the number of keys, of which min(*h_num, max_out) are written, in no particular order: d_keys[i], d_counts[i],
+ * d_boxes[6 i ..] as emp_label_table_finalize writes them (maxima INCLUSIVE), d_sums[9 i ..] = S1 then S2 in the order above,
+ * d_faces[3 i ..] = F.  Synchronises.  The table stays valid and can be fed further. */
+EMP_API int emp_label_measure_finalize(void* d_table, int64_t capacity, uint64_t* d_keys, uint64_t* d_counts, uint32_t* d_boxes,
+                                 uint64_t* d_sums, uint64_t* d_faces, int64_t max_out, int64_t* h_num, void* stream);
+
+/* ------------------------------------------------------------------------
  * 8. Morph Labels (csrc/morph.hip): binary dilation, erosion, closing and
  *    opening of single labels with a disk / ball of radius 1..7, every label
  *    inside its own padded box -- the plugin's Morph Labels
