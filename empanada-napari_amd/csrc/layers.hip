@@ -383,6 +383,7 @@ __global__ void __launch_bounds__(256) bilinear_ac_kernel(const half_t* __restri
   }
 }
 
+// The four-pixel kernel, first form (EMP_BILINEAR_UP4_LEGACY=1; the network runs bilinear_ac_up4x4_kernel below).
 // Up-scaling by >= 3 (the decoder's 64^2 -> 256^2): a thread owns FOUR consecutive output pixels of a row.  Their
 // source columns are x0a .. x0a + 2 (3 * sx < 1), so 6 loads feed 4 stores instead of 16 -- the one-pixel kernel moved
 // 5x the output bytes through the CU's 64 B/clk vector-memory path [0.74 ms for 2.1 GB written].  Per output the
@@ -445,6 +446,84 @@ __global__ void __launch_bounds__(256) bilinear_ac_up4_kernel(const half_t* __re
         }
         if (ok[u] && ox < W) *reinterpret_cast<f16x8*>(out + obase[u] + (size_t)j * out_ld) = o;
       }
+    }
+  }
+}
+
+// The four-pixel kernel, second form: a thread owns a 4 x 4 output block of one channel group.  With 3 * sy < 1 as well as
+// 3 * sx < 1 its sources are the 3 x 3 vectors at rows ya .. ya + 2, columns xa .. xa + 2 (clamped into the map, so that
+// "x0 + 1 at the edge" is the clamped load itself): 9 loads feed 16 stores.  A workgroup writes one band of four output rows
+// x 4 ppb columns and exits.  Per output column the horizontal lerps of the three source rows are computed once and shared
+// by the four output rows; the row pair of an output row is the same for the whole workgroup (a scalar branch).  Every output
+// is bilerp's expression on the same source values as in bilinear_ac_kernel: bit-identical results.
+__device__ __forceinline__ void up4x4_store_row(half_t* __restrict__ o, const float (&t0)[8], const float (&t1)[8], float hy, float ly) {
+#pragma clang fp contract(off)
+  float v[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) v[c] = __builtin_fmaf(ly, t1[c], hy * t0[c]);
+  // the fp32 sample must exist before it is rounded to fp16, as in the other two kernels: left alone, the compiler folds the
+  // fma and the conversion of some channels into v_fma_mixlo/hi_f16, which rounds once and differs in double-rounding cases
+  asm("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]));
+  f16x8 r;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) r[c] = (half_t)v[c];
+  *reinterpret_cast<f16x8*>(o) = r;
+}
+
+__global__ void __launch_bounds__(256) bilinear_ac_up4x4_kernel(const half_t* __restrict__ in, int h, int w, int C, int in_ld,
+                                                                half_t* __restrict__ out, int H, int W, int out_ld,
+                                                                float sy, float sx, int segs_per_row, int ppb) {
+#pragma clang fp contract(off)      // coordinates and weights round like the oracle's; the sample itself is bilerp's explicit fmas
+  const int CG = C >> 3;
+  const int cg = threadIdx.x % CG, pl = threadIdx.x / CG;      // channel group, 4 x 4 block within the segment
+  const int seg = blockIdx.x % segs_per_row, band = blockIdx.x / segs_per_row;
+  const int bands = H >> 2;
+  const int oy0 = (band % bands) * 4, n = band / bands;
+  const int ox0 = (seg * ppb + pl) * 4;
+  if (pl >= ppb || ox0 >= W) return;
+  const int ya = (int)(sy * (float)oy0), xa = (int)(sx * (float)ox0);
+  f16x8 s[3][3];
+  const half_t* base = in + (size_t)n * h * w * in_ld + cg * 8;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const int yc = ya + r < h - 1 ? ya + r : h - 1;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const int xc = xa + k < w - 1 ? xa + k : w - 1;
+      s[r][k] = *reinterpret_cast<const f16x8*>(base + ((size_t)yc * w + xc) * in_ld);
+    }
+  }
+  // the rows' weights and source pairs: the same for every thread of the workgroup
+  float ly[4], hy[4];
+  bool dy[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float fy = sy * (float)(oy0 + i);
+    const int y0 = (int)fy;
+    ly[i] = fy - (float)y0;
+    hy[i] = 1.f - ly[i];
+    dy[i] = __builtin_amdgcn_readfirstlane(y0 != ya);          // y0 - ya in {0, 1}
+  }
+  half_t* obase = out + (((size_t)n * H + oy0) * W + ox0) * out_ld + cg * 8;
+  const int orow = W * out_ld;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float fx = sx * (float)(ox0 + j);
+    const int x0 = (int)fx;
+    const float lx = fx - (float)x0, hx = 1.f - lx;
+    const bool d = x0 != xa;                                   // x0 - xa in {0, 1}
+    float t[3][8];                                             // hx * v[x0] + lx * v[x1] of the three source rows
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      const f16x8 a = d ? s[r][1] : s[r][0], b = d ? s[r][2] : s[r][1];
+#pragma unroll
+      for (int c = 0; c < 8; ++c) t[r][c] = __builtin_fmaf(lx, (float)b[c], hx * (float)a[c]);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      half_t* o = obase + i * orow + j * out_ld;
+      if (dy[i]) up4x4_store_row(o, t[1], t[2], hy[i], ly[i]);
+      else up4x4_store_row(o, t[0], t[1], hy[i], ly[i]);
     }
   }
 }
@@ -786,7 +865,8 @@ int launch_fuse_combine(const half_t* a, const half_t* b, const half_t* c, float
 }
 
 // variant 0: the dispatch below (with the EMP_BILINEAR_NO_UP4 switch); 1: the one-pixel kernel; 2: the four-pixel kernel, an error
-// where its preconditions do not hold (the operator-level tests A/B both in one process)
+// where its preconditions do not hold (the operator-level tests A/B both in one process).  The four-pixel kernel is the 4 x 4
+// form, or with EMP_BILINEAR_UP4_LEGACY=1 the 1 x 4 form.
 int launch_bilinear_ac(const half_t* in, int N, int h, int w, int C, int in_ld, half_t* out, int H, int W, int out_ld,
                        hipStream_t s, int variant) {
   EMP_REQUIRE(C % 8 == 0 && in_ld % 8 == 0 && out_ld % 8 == 0, "bilinear: channels must be multiples of 8");
@@ -799,10 +879,22 @@ int launch_bilinear_ac(const half_t* in, int N, int h, int w, int C, int in_ld, 
   EMP_REQUIRE(CG >= 1 && CG <= 256, "bilinear: at most 2048 channels");
   const int ppb = 256 / CG;                         // pixels (up4: 4-pixel groups) per block iteration
   static const bool no_up4 = [] { const char* e = getenv("EMP_BILINEAR_NO_UP4"); return e && e[0] == '1'; }();   // A/B runs
-  const bool up4_ok = W % 4 == 0 && 3.f * sx < 1.f && W >= 4 * ppb;
-  EMP_REQUIRE(variant != 2 || up4_ok, "bilinear: the four-pixel kernel needs W %% 4 == 0, 3 * sx < 1 and W >= %d (W=%d w=%d)", 4 * ppb, W, w);
+  const char* legacy_env = getenv("EMP_BILINEAR_UP4_LEGACY");  // =1: the 1 x 4 form of the four-pixel kernel (read per call: A/B; identical output)
+  const bool legacy = legacy_env && legacy_env[0] == '1';
+  // the 4 x 4 form owns whole blocks of four rows whose sources span three: H % 4 == 0 and 3 * sy < 1 besides the 1 x 4 form's conditions
+  const bool up4_ok = W % 4 == 0 && 3.f * sx < 1.f && W >= 4 * ppb && (legacy || (H % 4 == 0 && 3.f * sy < 1.f));
+  EMP_REQUIRE(variant != 2 || up4_ok, "bilinear: the four-pixel kernel needs W %% 4 == 0, 3 * sx < 1 and W >= %d%s (W=%d w=%d H=%d h=%d)", 4 * ppb,
+              legacy ? "" : ", H % 4 == 0 and 3 * sy < 1", W, w, H, h);
   if (variant == 2 || (variant == 0 && !no_up4 && up4_ok)) {
     const int segs = cdiv(W / 4, ppb);
+    if (!legacy) {
+      const int64_t total = (int64_t)N * (H / 4) * segs;
+      EMP_REQUIRE(total < (1ll << 31) && (int64_t)H * W * out_ld < (1ll << 31), "bilinear: too many row segments");
+      hipLaunchKernelGGL(bilinear_ac_up4x4_kernel, dim3((unsigned)total), dim3(256), 0, s, in, h, w, C, in_ld, out, H, W, out_ld, sy, sx,
+                         segs, ppb);
+      EMP_LAUNCH_CHECK();
+      return EMP_OK;
+    }
     const int64_t total = (int64_t)N * H * segs;
     EMP_REQUIRE(total < (1ll << 31), "bilinear: too many row segments");
     const int grid = (int)(total < 256 * 16 ? total : 256 * 16);

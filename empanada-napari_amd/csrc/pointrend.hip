@@ -42,19 +42,35 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* sh /*[
   return base + inc - v;
 }
 
+// One x2 sample (align_corners=False) in the operation order the compiler's contraction gave the first form of this kernel
+// (read from its gfx950 code): t0 = fma(lx, v01, hx * v00), t1 = fma(hx, v10, lx * v11), v = hy * t0 + ly * t1 with a plain
+// add.  Written out under fp contract(off) so that the one-output and the four-output kernel agree by construction.
+__device__ __forceinline__ float up2x_sample(float v00, float v01, float v10, float v11, float hx, float lx, float hy, float ly) {
+#pragma clang fp contract(off)
+  const float t0 = __builtin_fmaf(lx, v01, hx * v00);
+  const float t1 = __builtin_fmaf(hx, v10, lx * v11);
+  const float a = hy * t0, b = ly * t1;
+  return a + b;
+}
+// source coordinate of output o: 0.5 * (o + 0.5) - 0.5 clamped at 0 (the product by 0.5 is exact: fused or not, the same bits)
+__device__ __forceinline__ float up2x_coord(int o) {
+#pragma clang fp contract(off)
+  const float f = 0.5f * ((float)o + 0.5f) - 0.5f;
+  return f < 0.f ? 0.f : f;
+}
+
+// EMP_PR_UP2X_LEGACY=1: one output per thread, grid-stride
 __global__ void __launch_bounds__(256) upsample2x_keys_kernel(const float* __restrict__ in, int N, int C, int h, int w,
                                                               float* __restrict__ out, uint32_t* __restrict__ keys,
                                                               int64_t total) {
+#pragma clang fp contract(off)
   const int H = 2 * h, W = 2 * w;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     int ox = (int)(i % W);
     int64_t p = i / W;
     int oy = (int)(p % H);
     int n = (int)(p / H);
-    float fy = 0.5f * ((float)oy + 0.5f) - 0.5f;
-    float fx = 0.5f * ((float)ox + 0.5f) - 0.5f;
-    fy = fy < 0.f ? 0.f : fy;
-    fx = fx < 0.f ? 0.f : fx;
+    const float fy = up2x_coord(oy), fx = up2x_coord(ox);
     int y0 = (int)fy, x0 = (int)fx;
     int y1 = y0 + (y0 < h - 1 ? 1 : 0), x1 = x0 + (x0 < w - 1 ? 1 : 0);
     float ly = fy - (float)y0, lx = fx - (float)x0;
@@ -62,13 +78,92 @@ __global__ void __launch_bounds__(256) upsample2x_keys_kernel(const float* __res
     float top1 = -INFINITY, top2 = -INFINITY, v0 = 0.f;
     for (int c = 0; c < C; ++c) {
       const float* b = in + ((size_t)n * C + c) * h * w;
-      float v = hy * (hx * b[y0 * w + x0] + lx * b[y0 * w + x1]) + ly * (hx * b[y1 * w + x0] + lx * b[y1 * w + x1]);
+      float v = up2x_sample(b[y0 * w + x0], b[y0 * w + x1], b[y1 * w + x0], b[y1 * w + x1], hx, lx, hy, ly);
       out[(((size_t)n * C + c) * H + oy) * W + ox] = v;
       if (c == 0) v0 = v;
       if (v > top1) { top2 = top1; top1 = v; } else if (v > top2) { top2 = v; }
     }
     float key = (C == 1) ? fabsf(v0) : (top1 - top2);
     keys[i] = __float_as_uint(key);
+  }
+}
+
+// A thread produces outputs 4q .. 4q + 3 of one row: their source columns are 2q - 1 .. 2q + 2 (clamped into the row), so eight
+// loads per class feed one 16-byte store of logits and, after the last class, one of keys; 32-bit indices (the entry bounds
+// N * 4hw below 2^31), one row group per thread, no loop over the grid.  VEC 4: 16-byte stores (W % 4 == 0, both bases on a
+// 16-byte boundary); VEC 2: 8-byte stores (W is even; odd w ends each row in a pair); VEC 1: guarded 4-byte stores.
+template <int VEC>
+__global__ void __launch_bounds__(256) upsample2x_keys4_kernel(const float* __restrict__ in, int C, int h, int w,
+                                                               float* __restrict__ out, uint32_t* __restrict__ keys,
+                                                               int Wq, int total) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int H = 2 * h, W = 2 * w;
+  const int q = i % Wq, row = i / Wq;
+  const int oy = row % H, n = row / H;
+  const float fy = up2x_coord(oy);
+  const int y0 = (int)fy, y1 = y0 + (y0 < h - 1 ? 1 : 0);
+  const float ly = fy - (float)y0, hy = 1.f - ly;
+  int xc[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int x = 2 * q - 1 + k;
+    xc[k] = x < 0 ? 0 : (x < w - 1 ? x : w - 1);
+  }
+  float lx[4], hx[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float fx = up2x_coord(4 * q + j);
+    lx[j] = fx - (float)(int)fx;
+    hx[j] = 1.f - lx[j];
+  }
+  const bool first = q == 0;                       // output 0: x0 = 0, x1 = min(1, w - 1) are columns 1 and 2 of the four
+  const int valid = W - 4 * q < 4 ? W - 4 * q : 4; // 2 in the last group of a row with odd w
+  float top1[4], top2[4], v0[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { top1[j] = -INFINITY; top2[j] = -INFINITY; v0[j] = 0.f; }
+  const int plane = h * w, oplane = H * W;
+  const float* b = in + (size_t)n * C * plane;
+  float* o = out + (size_t)n * C * oplane + oy * W + 4 * q;
+  for (int c = 0; c < C; ++c, b += plane, o += oplane) {
+    float r0[4], r1[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { r0[k] = b[y0 * w + xc[k]]; r1[k] = b[y1 * w + xc[k]]; }
+    float v[4];
+    v[0] = up2x_sample(first ? r0[1] : r0[0], first ? r0[2] : r0[1], first ? r1[1] : r1[0], first ? r1[2] : r1[1], hx[0], lx[0], hy, ly);
+    v[1] = up2x_sample(r0[1], r0[2], r1[1], r1[2], hx[1], lx[1], hy, ly);
+    v[2] = up2x_sample(r0[1], r0[2], r1[1], r1[2], hx[2], lx[2], hy, ly);
+    v[3] = up2x_sample(r0[2], r0[3], r1[2], r1[3], hx[3], lx[3], hy, ly);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (c == 0) v0[j] = v[j];
+      if (v[j] > top1[j]) { top2[j] = top1[j]; top1[j] = v[j]; } else if (v[j] > top2[j]) { top2[j] = v[j]; }
+    }
+    if (VEC == 4) {
+      *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
+    } else if (VEC == 2) {
+      *reinterpret_cast<float2*>(o) = make_float2(v[0], v[1]);
+      if (valid == 4) *reinterpret_cast<float2*>(o + 2) = make_float2(v[2], v[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < valid) o[j] = v[j];
+    }
+  }
+  uint32_t key[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) key[j] = __float_as_uint((C == 1) ? fabsf(v0[j]) : (top1[j] - top2[j]));
+  uint32_t* kp = keys + (size_t)row * W + 4 * q;
+  if (VEC == 4) {
+    *reinterpret_cast<uint4*>(kp) = make_uint4(key[0], key[1], key[2], key[3]);
+  } else if (VEC == 2) {
+    *reinterpret_cast<uint2*>(kp) = make_uint2(key[0], key[1]);
+    if (valid == 4) *reinterpret_cast<uint2*>(kp + 2) = make_uint2(key[2], key[3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (j < valid) kp[j] = key[j];
   }
 }
 
@@ -832,7 +927,18 @@ inline int grid_for(int64_t total, int per_block = 256, int cap = 256 * 16) {
 
 int launch_upsample2x_keys(const float* in, int N, int C, int h, int w, float* out, uint32_t* keys, hipStream_t s) {
   int64_t total = (int64_t)N * 4 * h * w;
-  hipLaunchKernelGGL(upsample2x_keys_kernel, dim3(grid_for(total)), dim3(256), 0, s, in, N, C, h, w, out, keys, total);
+  const char* legacy_env = getenv("EMP_PR_UP2X_LEGACY");      // =1: one output per thread (read per call: A/B; identical output)
+  if ((legacy_env && legacy_env[0] == '1') || total >= (1ll << 31)) {
+    hipLaunchKernelGGL(upsample2x_keys_kernel, dim3(grid_for(total)), dim3(256), 0, s, in, N, C, h, w, out, keys, total);
+    EMP_LAUNCH_CHECK();
+    return EMP_OK;
+  }
+  const int W = 2 * w, Wq = (W + 3) / 4;
+  const int groups = N * 2 * h * Wq;                          // <= total
+  const uintptr_t bases = (uintptr_t)out | (uintptr_t)keys;
+  const int vec = (W % 4 == 0 && bases % 16 == 0) ? 4 : (bases % 8 == 0 ? 2 : 1);
+  auto kern = vec == 4 ? upsample2x_keys4_kernel<4> : vec == 2 ? upsample2x_keys4_kernel<2> : upsample2x_keys4_kernel<1>;
+  hipLaunchKernelGGL(kern, dim3(cdiv(groups, 256)), dim3(256), 0, s, in, C, h, w, out, keys, Wq, groups);
   EMP_LAUNCH_CHECK();
   return EMP_OK;
 }

@@ -11,7 +11,8 @@
 //
 // One workgroup = one 8 x 8 tile of POOLED outputs: the 17 x 17 conv outputs it needs (stored fp16 in LDS, -inf
 // outside the conv map so that the pool's padding never wins) from a 40 x 40 input patch; the conv map itself is
-// never written to HBM.
+// never written to HBM.  Two forms with the same bits: stem_pool_kernel_v2 (what the network runs) and stem_pool_kernel
+// (EMP_STEM_POOL_LEGACY=1), which differ in their schedule only.
 #include "common.h"
 
 namespace emp {
@@ -166,6 +167,190 @@ __global__ void __launch_bounds__(256) stem_pool_kernel(const T* __restrict__ im
 }
 
 
+// ---- stem_pool_kernel, second form (EMP_STEM_POOL_LEGACY=1 runs the one above) ------------------------------------------------------
+// The same tile, the same MFMA order per accumulator (wl.xh, wh.xl, wh.xh; ks = 0 then 1), the same epilogue arithmetic and the
+// same LDS layouts, so the same bits.  What differs is the schedule: (1) everything that does not depend on the tile -- the patch
+// element of each of a thread's seven loads, the LDS offsets of the fragments of a wave's five pixel tiles -- is computed once
+// per workgroup; (2) the raw patch of the NEXT tile is fetched into registers right after the barrier that publishes this
+// tile's patch, so that its latency lies under the MFMA and pooling phases instead of at the head of the next tile; (3) the
+// pixel-tile loop is unrolled and the fragment of pixel tile j + 1 is read before the MFMAs of pixel tile j issue; (4) the pool
+// takes its maxima on the packed fp16 vectors (the max of fp16 values is exact in fp16: 36 packed ops per item instead of 72
+// conversions, 72 fp32 maxima and 8 conversions back); (5) the barrier after the pool is gone: the next tile's patch write
+// touches ph / pl only, which no thread reads after the barrier behind the MFMA phase, and the next tile's first write to st
+// lies behind the next patch barrier, which a thread reaches only after its own pooling reads.
+template <typename T>
+__global__ void __launch_bounds__(256) stem_pool_kernel_v2(const T* __restrict__ img, float sub, float mul, int N, int H,
+                                                             int W, int vh, int vw, const float* __restrict__ wgt,
+                                                             const float* __restrict__ bias, half_t* __restrict__ out,
+                                                             int normalise) {
+  __shared__ __attribute__((aligned(16))) half_t ph[IP][IP];          // patch, hi part
+  __shared__ __attribute__((aligned(16))) half_t pl[IP][IP];          // patch, lo part
+  __shared__ __attribute__((aligned(16))) half_t st[NMT * 16][64];    // conv tile, fp16 after bias + ReLU
+  constexpr int NK = (IP * IP + 255) / 256;      // patch loads per thread: 7
+  constexpr int NJ = (NMT + 3) / 4;              // pixel tiles per wave: 5 (4 for the last wave)
+  const int Hs = H >> 1, Ws = W >> 1;       // conv map
+  const int Hp = Hs >> 1, Wp = Ws >> 1;     // pooled map
+  const int tiles_x = (Wp + PT - 1) / PT, tiles_y = (Hp + PT - 1) / PT;
+  const int tid = threadIdx.x, wave = tid >> 6, l = tid & 63;
+  const int total_tiles = N * tiles_y * tiles_x;
+  const int fr = l & 15, fq = l >> 4;
+  f16x8 wh[4][2], wl[4][2];
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const int ky = fq + 4 * ks;
+#pragma unroll
+      for (int kx = 0; kx < 8; ++kx) {
+        const float w = (ky < 7 && kx < 7) ? wgt[(ky * 7 + kx) * 64 + ct * 16 + fr] : 0.f;
+        const half_t h = (half_t)w;
+        wh[ct][ks][kx] = h;
+        wl[ct][ks][kx] = (half_t)(w - (float)h);
+      }
+    }
+  float bv[4][4];
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) bv[ct][r] = bias[ct * 16 + fq * 4 + r];
+
+  // tile-invariant indices
+  int pr[NK], pc[NK];                       // patch element of load k
+#pragma unroll
+  for (int k = 0; k < NK; ++k) {
+    const int i = tid + 256 * k;
+    pr[k] = i / IP;
+    pc[k] = i - pr[k] * IP;
+  }
+  const bool last_load = tid < IP * IP - 256 * (NK - 1);      // load NK - 1 exists for the first 64 threads only
+  int foff[NJ][2];                          // this lane's fragment of pixel tile j: element offset into ph / pl
+  int sy_of[NJ], sx_of[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int q = (wave + 4 * j) * 16 + fr;
+    const int qq = q < NSP ? q : NSP - 1;
+    sy_of[j] = qq / ST;
+    sx_of[j] = qq - sy_of[j] * ST;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) foff[j][ks] = (2 * sy_of[j] + fq + 4 * ks) * IP + 2 * sx_of[j];      // row <= 39
+  }
+  const half_t* phf = &ph[0][0];
+  const half_t* plf = &pl[0][0];
+
+  T raw[NK];
+  uint32_t okm = 0;
+  // the clamped loads of a tile's patch; okm: bit k set where load k lies inside the valid image
+  auto fetch = [&](int tile) {
+    int b = tile;
+    const int tx = b % tiles_x; b /= tiles_x;
+    const int ty = b % tiles_y; b /= tiles_y;
+    const int iy0 = 4 * (ty * PT) - 5, ix0 = 4 * (tx * PT) - 5;      // 2 * (2 * py0 - 1) - 3
+    const T* src = img + (size_t)b * vh * vw;
+    okm = 0;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+      const int iy = iy0 + pr[k], ix = ix0 + pc[k];
+      const bool ok = (k < NK - 1 || last_load) && iy >= 0 && iy < vh && ix >= 0 && ix < vw;
+      const int cy = min(max(iy, 0), vh - 1), cx = min(max(ix, 0), vw - 1);
+      raw[k] = src[(size_t)cy * vw + cx];
+      okm |= (ok ? 1u : 0u) << k;
+    }
+  };
+
+  int tile = blockIdx.x;
+  if (tile < total_tiles) fetch(tile);
+  for (; tile < total_tiles; tile += gridDim.x) {
+    int b = tile;
+    const int tx = b % tiles_x; b /= tiles_x;
+    const int ty = b % tiles_y; b /= tiles_y;
+    const int n = b;
+    const int py0 = ty * PT, px0 = tx * PT;
+    const int sy0 = 2 * py0 - 1, sx0 = 2 * px0 - 1;        // conv tile origin (may be -1)
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+      float v = (float)raw[k];
+      if (normalise) { v -= sub; v *= mul; }
+      v = ((okm >> k) & 1u) ? v : 0.f;
+      const half_t h = (half_t)v;
+      if (k < NK - 1 || last_load) {
+        ph[pr[k]][pc[k]] = h;
+        pl[pr[k]][pc[k]] = (half_t)(v - (float)h);
+      }
+    }
+    __syncthreads();      // the patch is complete; every thread has left the previous tile's pool
+    if (tile + (int)gridDim.x < total_tiles) fetch(tile + gridDim.x);      // in flight under the MFMA and pooling phases
+
+    f16x8 xh[2][2], xl[2][2];      // [pixel tile parity][ks]
+    auto read_frag = [&](int j) {
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        const uint32_t* rh = reinterpret_cast<const uint32_t*>(phf + foff[j][ks]);
+        const uint32_t* rl = reinterpret_cast<const uint32_t*>(plf + foff[j][ks]);
+        union { uint32_t u[4]; f16x8 v; } a, c;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { a.u[i] = rh[i]; c.u[i] = rl[i]; }
+        xh[j & 1][ks] = a.v;
+        xl[j & 1][ks] = c.v;
+      }
+    };
+    read_frag(0);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      if (wave + 4 * j >= NMT) break;       // wave-uniform: the last wave has four pixel tiles
+      if (j + 1 < NJ && wave + 4 * (j + 1) < NMT) read_frag(j + 1);
+      const int q = (wave + 4 * j) * 16 + fr;
+      f32x4 acc[4];
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) {
+          acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[ct][ks], xh[j & 1][ks], acc[ct], 0, 0, 0);
+          acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[ct][ks], xl[j & 1][ks], acc[ct], 0, 0, 0);
+          acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[ct][ks], xh[j & 1][ks], acc[ct], 0, 0, 0);
+        }
+      }
+      const int gy = sy0 + sy_of[j], gx = sx0 + sx_of[j];
+      const bool inside = gy >= 0 && gy < Hs && gx >= 0 && gx < Ws;
+      const uint32_t keep = inside ? 0xFFFFFFFFu : 0u;
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) {
+        union { f16x2 h[2]; uint32_t u[2]; f16x4 v; } o;
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          const f32x2 s2 = f32x2{acc[ct][2 * r], acc[ct][2 * r + 1]} + f32x2{bv[ct][2 * r], bv[ct][2 * r + 1]};
+          const f16x2 h2 = __builtin_convertvector(s2, f16x2);
+          o.h[r] = __builtin_elementwise_max(h2, f16x2{(half_t)0.f, (half_t)0.f});
+          o.u[r] = (o.u[r] & keep) | (0xFC00FC00u & ~keep);      // outside the conv map: (-inf, -inf)
+        }
+        *reinterpret_cast<f16x4*>(&st[q][(((ct * 2 + (fq >> 1)) ^ (q & 7)) << 3) + (fq & 1) * 4]) = o.v;      // swizzle: see above
+      }
+    }
+    __syncthreads();      // the conv tile is complete; nobody reads ph / pl any more
+
+#pragma unroll
+    for (int it = 0; it < PT * PT * 8 / 256; ++it) {
+      const int i = tid + 256 * it;
+      const int cg = i & 7, pp = i >> 3;
+      const int py = pp / PT, px = pp - py * PT;
+      const int oy = py0 + py, ox = px0 + px;
+      if (oy >= Hp || ox >= Wp) continue;
+      const half_t ninf = (half_t)(-INFINITY);
+      f16x8 m = f16x8{ninf, ninf, ninf, ninf, ninf, ninf, ninf, ninf};
+#pragma unroll
+      for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) {
+          const int sq = (2 * py + dy) * ST + 2 * px + dx;
+          m = __builtin_elementwise_max(m, *reinterpret_cast<const f16x8*>(&st[sq][(cg ^ (sq & 7)) * 8]));
+        }
+      *reinterpret_cast<f16x8*>(out + (((size_t)n * Hp + oy) * Wp + ox) * 64 + cg * 8) = m;
+    }
+  }
+}
+
+
 // ---- the same launch for the fp32 graph (fp32 reference mode's schedule in the fp16x3 mode; round 6) ---------------------------------
 // conv1 + bn1 + relu + maxpool with an fp32 conv tile in LDS and an fp32 NHWC output: the products are the three-MFMA split above
 // (fp32 result to ~2^-21 relative, what every convolution of the fp16x3 mode delivers), bias / ReLU / max in fp32.  Replaces the
@@ -298,20 +483,22 @@ int launch_stem_pool(const void* img, int dtype, float sub, float mul, int N, in
   const int Hp = H / 4, Wp = W / 4;
   const int64_t tiles = (int64_t)N * cdiv(Hp, PT) * cdiv(Wp, PT);
   EMP_REQUIRE(tiles < (1ll << 31), "stem: too many tiles");
-  const int64_t grid = tiles < 256 * 12 ? tiles : 256 * 12;      // persistent: 3 workgroups per CU x 4 rounds of slack
+  int64_t grid = tiles < 256 * 12 ? tiles : 256 * 12;      // persistent: 3 workgroups per CU x 4 rounds of slack
+  // both switches are read per call (A/B in one process; identical output)
+  const char* legacy_env = getenv("EMP_STEM_POOL_LEGACY");      // =1: the first form of the kernel
+  const bool legacy = legacy_env && legacy_env[0] == '1';
+  if (const char* cap_env = getenv("EMP_STEM_POOL_GRID")) {     // =<n>: at most n workgroups (tests: the tile loop on small images)
+    const long cap = strtol(cap_env, nullptr, 10);
+    if (cap >= 1 && cap < grid) grid = cap;
+  }
+  auto go = [&](auto fast, auto slow, auto ptr, int norm) {
+    if (legacy) hipLaunchKernelGGL(slow, dim3((unsigned)grid), dim3(256), 0, s, ptr, sub, mul, N, H, W, vh, vw, w, b, out, norm);
+    else hipLaunchKernelGGL(fast, dim3((unsigned)grid), dim3(256), 0, s, ptr, sub, mul, N, H, W, vh, vw, w, b, out, norm);
+  };
   switch (dtype) {
-    case EMP_IMG_F32:
-      hipLaunchKernelGGL(stem_pool_kernel<float>, dim3((unsigned)grid), dim3(256), 0, s, (const float*)img, sub, mul, N, H, W,
-                         vh, vw, w, b, out, 0);
-      break;
-    case EMP_IMG_U8:
-      hipLaunchKernelGGL(stem_pool_kernel<uint8_t>, dim3((unsigned)grid), dim3(256), 0, s, (const uint8_t*)img, sub, mul, N,
-                         H, W, vh, vw, w, b, out, 1);
-      break;
-    case EMP_IMG_U16:
-      hipLaunchKernelGGL(stem_pool_kernel<uint16_t>, dim3((unsigned)grid), dim3(256), 0, s, (const uint16_t*)img, sub, mul,
-                         N, H, W, vh, vw, w, b, out, 1);
-      break;
+    case EMP_IMG_F32: go(&stem_pool_kernel_v2<float>, &stem_pool_kernel<float>, (const float*)img, 0); break;
+    case EMP_IMG_U8: go(&stem_pool_kernel_v2<uint8_t>, &stem_pool_kernel<uint8_t>, (const uint8_t*)img, 1); break;
+    case EMP_IMG_U16: go(&stem_pool_kernel_v2<uint16_t>, &stem_pool_kernel<uint16_t>, (const uint16_t*)img, 1); break;
     default:
       EMP_REQUIRE(false, "stem: unknown image dtype %d", dtype);
   }

@@ -397,7 +397,10 @@ EMP_API int emp_sepconvp_ws_nhwc_f16(const void* d_in, int N, int H, int W, int 
  *
  * emp_pr_upsample2x_keys: d_in (N,C,h,w) fp32 -> d_out (N,C,2h,2w) fp32, F.interpolate(scale_factor=2, bilinear,
  *   align_corners=False), and d_keys (N,2h*2w) uint32: the fp32 bit pattern of |v| (C == 1) or top1 - top2 over the classes
- *   (C > 1) of the up-sampled logits -- the negated uncertainty of point_rend.py:11-31, never negative.
+ *   (C > 1) of the up-sampled logits -- the negated uncertainty of point_rend.py:11-31, never negative.  One thread writes four
+ *   consecutive outputs of a row with 16-byte stores (W % 4 == 0 and both outputs on a 16-byte boundary), 8-byte stores (odd w)
+ *   or guarded 4-byte stores (any 4-byte-aligned pointers).  EMP_PR_UP2X_LEGACY=1 (read per call): the one-output kernel; the
+ *   same bits.
  * emp_pr_topk_smallest: per image the k cells with the smallest keys (fp32 bit patterns of non-negative values): every key
  *   below the k-th smallest value and, among the cells equal to it, those with the lowest index.  d_idx (N,k) int32: first
  *   the cells below the k-th value in ascending order, then the tied cells in ascending order.  k == plane returns every
@@ -456,7 +459,10 @@ EMP_API int emp_head1x1_scatter_f32(const float* d_in, int N, int P, int K, int 
  *   and by the convolution.  d_w (49,64) fp32 tap-major, d_b 64.  H, W even, 1 <= vh <= H, 1 <= vw <= W.  F16: stem7x7_kernel
  *   storing fp16; F32: the same kernel storing its fp32 sums.
  * emp_op_stem_pool: the same followed by the 3x3 stride-2 pad-1 max-pool, in one launch on the matrix pipe -> d_out
- *   (N,H/4,W/4,64); H, W % 4 == 0.  F16: stem_pool_kernel (conv tile rounded to fp16 before the pool); F32: stem_pool32_kernel.
+ *   (N,H/4,W/4,64); H, W % 4 == 0.  F16: stem_pool_kernel_v2 (conv tile rounded to fp16 before the pool; the next tile's patch is
+ *   fetched under the current tile's work), or with EMP_STEM_POOL_LEGACY=1 stem_pool_kernel, the same bits;
+ *   EMP_STEM_POOL_GRID=<n> caps the workgroups of either (a test hook: the tile loop on small images); both read per call.
+ *   F32: stem_pool32_kernel.
  * emp_op_stem3x3s2: 3x3 stride-2 pad-1 conv + bias + ReLU, same normalisation and padding -> d_out (N,H/2,W/2,out_ld), C
  *   channels written; d_w (9,C) fp32.  F16: stem3x3s2_f16_kernel (C % 8); F32: stem3x3s2_32_kernel (C % 4).
  * emp_op_maxpool3x3s2: 3x3 stride-2 pad-1 max-pool, -inf padding, (N,H,W,C) -> (N,H/2,W/2,C); H, W even.  Exact.
@@ -465,10 +471,12 @@ EMP_API int emp_head1x1_scatter_f32(const float* d_in, int N, int P, int K, int 
  *   d_out out_ld apart (0: C); d_out_lo not NULL: the fp32 sum leaves as an fp16 pair, hi = fp16(v) to d_out and lo = fp16(v - hi)
  *   to d_out_lo (same stride).  F32: fuse_combine32_kernel, dense, d_out_lo NULL and out_ld 0 or C.
  * emp_op_bilinear_ac_nhwc: F.interpolate(bilinear, align_corners=True) of C channels of (N,h,w,in_ld) into C channels of
- *   (N,H,W,out_ld); h == H and w == W copies bit for bit.  F16, variant 0: what the network launches (bilinear_ac_up4_kernel
- *   when W % 4 == 0, 3 (w-1)/(W-1) < 1 and W >= 4 * (256 / (C/8)), unless EMP_BILINEAR_NO_UP4=1 was set when the process made
- *   its first call; else bilinear_ac_kernel); variant 1: bilinear_ac_kernel; variant 2: bilinear_ac_up4_kernel, EMP_ERR_INVALID
- *   where those conditions fail.  Both kernels give the same bits.  F32: variant must be 0; bilinear32x4_kernel when W % 4 == 0
+ *   (N,H,W,out_ld); h == H and w == W copies bit for bit.  F16, variant 0: what the network launches (the four-pixel kernel
+ *   bilinear_ac_up4x4_kernel, a 4 x 4 output block per thread, when W % 4 == 0, 3 (w-1)/(W-1) < 1, W >= 4 * (256 / (C/8)),
+ *   H % 4 == 0 and 3 (h-1)/(H-1) < 1, unless EMP_BILINEAR_NO_UP4=1 was set when the process made its first call; else
+ *   bilinear_ac_kernel); variant 1: bilinear_ac_kernel; variant 2: the four-pixel kernel, EMP_ERR_INVALID where those
+ *   conditions fail.  EMP_BILINEAR_UP4_LEGACY=1 (read per call): the four-pixel kernel is bilinear_ac_up4_kernel (1 x 4 outputs
+ *   per thread) under the first three conditions alone.  All three kernels give the same bits.  F32: variant must be 0; bilinear32x4_kernel when W % 4 == 0
  *   and W >= 4 w, unless EMP_BILINEAR32_X4=0 (read per call), else bilinear32_kernel; same bits.
  * emp_op_bilinear_ac_nchw_f32: NC planes (h,w) fp32 -> (h*scale, w*scale), align_corners=True (bilinear_ac_f32_kernel).
  * emp_op_avgpool: mean over the HW pixels of each of C channels of (N,HW,in_ld) -> d_out (N,C) fp32.  F16:
