@@ -1,6 +1,7 @@
-// What the streaming kernels over label arrays share (overlap.hip, labels.hip, measure.hip): the hash of their open-addressing
-// tables, the load of E consecutive elements of 1, 2, 4 or 8 bytes as raw unsigned values, and the division that turns a raster
-// offset into coordinates.
+// What the streaming kernels over label arrays share in their hot loops (overlap.hip, labels.hip, measure.hip): the hash of
+// their open-addressing tables, the load of E consecutive elements of 1, 2, 4 or 8 bytes as raw unsigned values, the division
+// that turns a raster offset into coordinates, the domain check of a one-label key and the min / max update of a cell's box.
+// Everything here is inlined into the count kernels; what they share outside them -- the table itself -- is label_table.h.
 #pragma once
 #include "common.h"
 
@@ -89,6 +90,36 @@ __device__ __forceinline__ uint32_t ov_div(uint32_t x, uint32_t d, float inv, ui
   }
   rem = (uint32_t)r;
   return q;
+}
+
+// offset o (<= 2^12) from the voxel (bz, by, bx) in raster order; c: a kernel's context with H, W and their float reciprocals
+template <class Ctx>
+__device__ __forceinline__ void ov_coord(const Ctx& c, uint32_t bx, uint32_t by, uint32_t bz, uint32_t o, uint32_t& x, uint32_t& y, uint32_t& z) {
+  x = bx + o;
+  y = by;
+  z = bz;
+  if (x >= c.W) {
+    y += ov_div(x, c.W, c.invW, x);
+    if (y >= c.H) z += ov_div(y, c.H, c.invH, y);
+  }
+}
+
+// values outside the domain of a key that holds one label: [0, 2^63) for the whole volume, [0, 2^32) per slice
+template <int S>
+__device__ __forceinline__ bool ov_key_out_of_range(uint64_t v, int is_signed, int per_slice) {
+  if (S == 8) return per_slice ? (v >> 32) != 0 : (v >> 63) != 0;
+  return is_signed && ((v >> (8 * S - 1)) & 1);
+}
+
+// the box r (lo[3], hi[3]: z, y, x, inclusive) into the six fields b of a cell in global memory.  A field is read before it is
+// updated: a box converges after a few runs of its label
+template <class R>
+__device__ __forceinline__ void ov_box_update_global(uint32_t* b, const R& r) {
+#pragma unroll
+  for (int f = 0; f < 3; ++f) {
+    if (r.lo[f] < __hip_atomic_load(&b[f], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&b[f], r.lo[f]);
+    if (r.hi[f] > __hip_atomic_load(&b[3 + f], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&b[3 + f], r.hi[f]);
+  }
 }
 
 }  // namespace emp

@@ -24,10 +24,12 @@
 // Overflow: as in overlap.hip, slots are never released, so the same slab with negated weights takes out exactly the counts
 // a failed call added.  The min / max updates of a failed call are not undone: they are idempotent and are the right values
 // once the slab is counted again (cells whose count is 0 do not exist for grow / finalize).
+// The table around the count kernel -- layout, reset, rehash, compaction, the host side of accumulate / grow / finalize -- is
+// label_table.h's; LabelTableCells below tells it what a cell of this family is.
 #include <vector>
 
 #include "common.h"
-#include "label_stream.h"
+#include "label_table.h"
 
 namespace emp {
 namespace {
@@ -37,9 +39,7 @@ constexpr int LT_LDS_SLOTS = 512;        // 40 B per slot: 20 KiB of LDS per wor
 constexpr int LT_LDS_PROBES = 8;
 constexpr int LT_GLOBAL_PROBES = 128;
 constexpr int64_t LT_MAX_GRID = 8192;    // short stretches, as overlap.hip (finding 82)
-constexpr uint64_t LT_EMPTY = ~0ull;     // keys lie in [0, 2^63)
-constexpr size_t LT_HEADER = 64;         // bytes: [1] flags (u32 overflow, u32 range), [2] compaction cursor
-constexpr size_t LT_SLOT_BYTES = 40;     // key, count, 6 x u32 box (min z, y, x, max z, y, x; inclusive)
+constexpr uint64_t LT_EMPTY = CELL_EMPTY;      // keys lie in [0, 2^63)
 
 typedef unsigned long long ull_t;
 
@@ -51,27 +51,9 @@ struct LtTable {
   uint64_t mask;
 };
 
-inline LtTable lt_table(void* d_table, int64_t capacity) {
-  LtTable t;
-  t.hdr = (uint64_t*)d_table;
-  t.keys = (uint64_t*)((char*)d_table + LT_HEADER);
-  t.counts = t.keys + capacity;
-  t.box = (uint32_t*)(t.counts + capacity);
-  t.mask = (uint64_t)capacity - 1;
-  return t;
-}
-
 struct LtBox {
   uint32_t lo[3], hi[3];      // z, y, x
 };
-
-__device__ __forceinline__ void lt_box_update_global(uint32_t* b, const LtBox& r) {
-#pragma unroll
-  for (int f = 0; f < 3; ++f) {
-    if (r.lo[f] < __hip_atomic_load(&b[f], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&b[f], r.lo[f]);
-    if (r.hi[f] > __hip_atomic_load(&b[3 + f], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&b[3 + f], r.hi[f]);
-  }
-}
 
 // w: the (possibly negated) weight; with_box 0: the count only (the negated pass)
 __device__ __forceinline__ void lt_global_add(const LtTable& t, uint64_t key, uint64_t w, const LtBox& r, int with_box) {
@@ -85,7 +67,7 @@ __device__ __forceinline__ void lt_global_add(const LtTable& t, uint64_t key, ui
     }
     if (cur == key) {
       atomicAdd((ull_t*)&t.counts[s], (ull_t)w);
-      if (with_box) lt_box_update_global(&t.box[s * 6], r);
+      if (with_box) ov_box_update_global(&t.box[s * 6], r);
       return;
     }
     s = (s + 1) & t.mask;
@@ -137,23 +119,12 @@ __device__ __forceinline__ void lt_lds_add(const LtCtx& c, uint64_t key, uint64_
   lt_global_add(c.t, key, c.negate ? 0ull - w : w, r, !c.negate);
 }
 
-// offset o (<= 2^12) from the voxel (bz, by, bx) in raster order
-__device__ __forceinline__ void lt_coord(const LtCtx& c, uint32_t bx, uint32_t by, uint32_t bz, uint32_t o, uint32_t& x, uint32_t& y, uint32_t& z) {
-  x = bx + o;
-  y = by;
-  z = bz;
-  if (x >= c.W) {
-    y += ov_div(x, c.W, c.invW, x);
-    if (y >= c.H) z += ov_div(y, c.H, c.invH, y);
-  }
-}
-
 // a run of len voxels of one label from offset o of the tile whose first voxel is (bz, by, bx): one entry, or one per slice
 // in per-slice mode (at most len of them)
 __device__ __forceinline__ void lt_run(const LtCtx& c, uint64_t label, uint32_t bx, uint32_t by, uint32_t bz, uint32_t o, uint32_t len) {
   uint32_t x0, y0, z0, x1, y1, z1;
-  lt_coord(c, bx, by, bz, o, x0, y0, z0);
-  lt_coord(c, bx, by, bz, o + len - 1, x1, y1, z1);
+  ov_coord(c, bx, by, bz, o, x0, y0, z0);
+  ov_coord(c, bx, by, bz, o + len - 1, x1, y1, z1);
   for (uint32_t z = z0;; ++z) {
     const uint32_t ze = c.per_slice ? z : z1;      // the entry covers the slices z .. ze
     const bool first = z == z0, last = ze == z1, multi = ze != z;
@@ -172,13 +143,6 @@ __device__ __forceinline__ void lt_run(const LtCtx& c, uint64_t label, uint32_t 
     lt_lds_add(c, c.per_slice ? ((uint64_t)(c.zoff + z) << 32) | label : label, cnt, r);
     if (last) break;
   }
-}
-
-// values outside the key's domain: [0, 2^63) for the whole volume, [0, 2^32) per slice
-template <int S>
-__device__ __forceinline__ bool lt_out_of_range(uint64_t v, int is_signed, int per_slice) {
-  if (S == 8) return per_slice ? (v >> 32) != 0 : (v >> 63) != 0;
-  return is_signed && ((v >> (8 * S - 1)) & 1);
 }
 
 // elements per lane and tile: LT_VECS 16-byte vectors, 16 elements at most (the run walk of a lane is unrolled).  In a uniform
@@ -240,7 +204,7 @@ __global__ void __launch_bounds__(LT_THREADS) label_table_kernel(const void* __r
     bool uni = nv == E;
 #pragma unroll
     for (int j = 0; j < E; ++j) {
-      bad = bad || lt_out_of_range<S>(v[j], is_signed, per_slice);
+      bad = bad || ov_key_out_of_range<S>(v[j], is_signed, per_slice);
       uni &= v[j] == v[0];
     }
     // a uniform lane continues the run of a uniform predecessor with the same label
@@ -272,7 +236,7 @@ __global__ void __launch_bounds__(LT_THREADS) label_table_kernel(const void* __r
       }
       lt_run(c, cur, bx, by, bz, o0 + start, len);
     }
-    lt_coord(c, bx, by, bz, TILE, bx, by, bz);
+    ov_coord(c, bx, by, bz, TILE, bx, by, bz);
   }
   if (bad) atomicOr((unsigned int*)&t.hdr[1] + 1, 1u);
   __syncthreads();
@@ -290,74 +254,35 @@ __global__ void __launch_bounds__(LT_THREADS) label_table_kernel(const void* __r
   }
 }
 
-__global__ void __launch_bounds__(256) label_table_reset_kernel(LtTable t, int64_t capacity) {
-  const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i0 < (int64_t)(LT_HEADER / 8)) t.hdr[i0] = 0;
-  for (int64_t i = i0; i < capacity; i += (int64_t)gridDim.x * 256) {
-    t.keys[i] = LT_EMPTY;
-    t.counts[i] = 0;
+// a cell is a key, a count and 6 x u32 of box (min z, y, x, max z, y, x; inclusive)
+struct LabelTableCells {
+  typedef LtTable Table;
+  struct Out {
+    uint64_t* keys;
+    uint64_t* counts;
+    uint32_t* box;
+  };
+  static constexpr size_t SLOT_BYTES = 40;
+  static constexpr int HEADER_CELLS = 0;
+  static void layout(LtTable& t, int64_t capacity) { t.box = (uint32_t*)(t.counts + capacity); }
+  static __device__ void clear(const LtTable& t, int64_t i) {
     for (int f = 0; f < 3; ++f) {
       t.box[i * 6 + f] = 0xffffffffu;
       t.box[i * 6 + 3 + f] = 0u;
     }
   }
-}
-
-// every counted cell of `from` into `to` (a larger table); a cell whose count is 0 was claimed by a slab that has been undone
-__global__ void __launch_bounds__(256) label_table_rehash_kernel(LtTable from, int64_t capacity, LtTable to) {
-  const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  for (int64_t i = i0; i < capacity; i += (int64_t)gridDim.x * 256) {
-    const uint64_t k = from.keys[i], w = from.counts[i];
-    if (k != LT_EMPTY && w != 0) {
-      LtBox r;
-      for (int f = 0; f < 3; ++f) {
-        r.lo[f] = from.box[i * 6 + f];
-        r.hi[f] = from.box[i * 6 + 3 + f];
-      }
-      lt_global_add(to, k, w, r, 1);
+  static __device__ void move(const LtTable& from, int64_t i, uint64_t k, uint64_t w, const LtTable& to) {
+    LtBox r;
+    for (int f = 0; f < 3; ++f) {
+      r.lo[f] = from.box[i * 6 + f];
+      r.hi[f] = from.box[i * 6 + 3 + f];
     }
+    lt_global_add(to, k, w, r, 1);
   }
-}
-
-// counted cells -> (key, count, box) in arrival order (the caller sorts); hdr[2] is the cursor, one atomic per wave
-__global__ void __launch_bounds__(256) label_table_compact_kernel(LtTable t, int64_t capacity, uint64_t* __restrict__ out_keys,
-                                                                  uint64_t* __restrict__ out_counts, uint32_t* __restrict__ out_box,
-                                                                  int64_t max_out) {
-  const int lane = threadIdx.x & 63;
-  const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t step = (int64_t)gridDim.x * 256;
-  const int64_t rounds = (capacity + step - 1) / step;
-  for (int64_t r = 0; r < rounds; ++r) {
-    const int64_t i = i0 + r * step;
-    uint64_t k = LT_EMPTY, w = 0;
-    if (i < capacity) {
-      k = t.keys[i];
-      w = k != LT_EMPTY ? t.counts[i] : 0;
-    }
-    const bool keep = w != 0;
-    const uint64_t m = __ballot(keep);
-    if (m == 0) continue;
-    const int leader = __ffsll((ull_t)m) - 1;
-    ull_t base = 0;
-    if (lane == leader) base = atomicAdd((ull_t*)&t.hdr[2], (ull_t)__popcll(m));
-    base = __shfl(base, leader);
-    if (keep) {
-      const int64_t pos = (int64_t)base + __popcll(m & ((1ull << lane) - 1ull));
-      if (pos < max_out) {
-        out_keys[pos] = k;
-        out_counts[pos] = w;
-        for (int f = 0; f < 6; ++f) out_box[pos * 6 + f] = t.box[i * 6 + f];
-      }
-    }
+  static __device__ void write(const LtTable& t, int64_t i, const Out& out, int64_t pos) {
+    for (int f = 0; f < 6; ++f) out.box[pos * 6 + f] = t.box[i * 6 + f];
   }
-}
-
-inline int lt_grid(int64_t items) {
-  int64_t g = (items + 255) / 256;
-  return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
-}
-
-inline bool lt_pow2(int64_t c) { return c >= 64 && c <= (1ll << 32) && (c & (c - 1)) == 0; }
+};
 
 template <int S>
 int lt_launch(const void* a, int64_t n, int is_signed, const LtTable& t, int64_t z0, int H, int W, int per_slice, int negate, hipStream_t s) {
@@ -548,21 +473,19 @@ using namespace emp;
 extern "C" {
 
 size_t emp_label_table_work_bytes(int64_t capacity) {
-  return lt_pow2(capacity) ? LT_HEADER + (size_t)capacity * LT_SLOT_BYTES : 0;
+  return cells_capacity_ok(capacity) ? CELL_HEADER + (size_t)capacity * LabelTableCells::SLOT_BYTES : 0;
 }
 
 int emp_label_table_reset(void* d_table, int64_t capacity, void* stream) {
-  EMP_REQUIRE(d_table && lt_pow2(capacity), "label_table_reset: the capacity must be a power of two in [64, 2^32]");
-  hipLaunchKernelGGL(label_table_reset_kernel, dim3(lt_grid(capacity)), dim3(256), 0, (hipStream_t)stream, lt_table(d_table, capacity), capacity);
-  EMP_LAUNCH_CHECK();
-  return EMP_OK;
+  EMP_REQUIRE(d_table && cells_capacity_ok(capacity), "label_table_reset: the capacity must be a power of two in [64, 2^32]");
+  return cells_reset<LabelTableCells>(d_table, capacity, (hipStream_t)stream);
 }
 
 // Synchronises the stream (it reads the table's flags).  *h_overflow = 1: the table was too small for this slab; the counts
 // the call had added have been taken out again.
 int emp_label_table_accumulate(const void* d_labels, int in_bytes, int64_t z0, int depth, int H, int W, int per_slice, void* d_table,
                                int64_t capacity, void* stream, int* h_overflow) {
-  EMP_REQUIRE(d_table && lt_pow2(capacity) && h_overflow && depth >= 0 && H > 0 && W > 0 && (depth == 0 || d_labels),
+  EMP_REQUIRE(d_table && cells_capacity_ok(capacity) && h_overflow && depth >= 0 && H > 0 && W > 0 && (depth == 0 || d_labels),
               "label_table_accumulate: bad arguments");
   EMP_REQUIRE(z0 >= 0 && z0 + depth <= 0x7fffffffll && W < 0x7fffffff - 8192 && H < 0x7fffffff - 8192,
               "label_table_accumulate: slice index, height or width beyond 2^31 - 2^13");
@@ -570,62 +493,32 @@ int emp_label_table_accumulate(const void* d_labels, int in_bytes, int64_t z0, i
   *h_overflow = 0;
   const int64_t n = (int64_t)depth * H * W;
   if (n == 0) return EMP_OK;
-  const LtTable t = lt_table(d_table, capacity);
+  const LtTable t = cells_table<LabelTableCells>(d_table, capacity);
   per_slice = per_slice != 0;
-  int rc = lt_dispatch(d_labels, in_bytes, n, t, z0, H, W, per_slice, 0, s);
-  if (rc) return rc;
-  uint32_t flags[2] = {0, 0};
-  EMP_CHECK_HIP(hipMemcpyAsync(flags, &t.hdr[1], sizeof(flags), hipMemcpyDeviceToHost, s));
-  EMP_CHECK_HIP(hipStreamSynchronize(s));
-  EMP_REQUIRE(flags[1] == 0, "label_table_accumulate: a label outside the key's domain (negative, or beyond 2^63 / per slice 2^32)");
-  if (flags[0]) {
-    rc = lt_dispatch(d_labels, in_bytes, n, t, z0, H, W, per_slice, 1, s);      // the same slab with negated weights
-    if (rc) return rc;
-    EMP_CHECK_HIP(hipMemsetAsync(&t.hdr[1], 0, 8, s));
-    EMP_CHECK_HIP(hipStreamSynchronize(s));
-    *h_overflow = 1;
-  }
-  return EMP_OK;
+  return cells_accumulate(t.hdr, s, "label_table_accumulate", "the key's domain (negative, or beyond 2^63 / per slice 2^32)",
+                          [&](int negate) { return lt_dispatch(d_labels, in_bytes, n, t, z0, H, W, per_slice, negate, s); }, h_overflow);
 }
 
 // Moves the cells of a table into an empty (reset) larger one.  Synchronises; *h_overflow = 1: d_to is too small as well.
 int emp_label_table_grow(const void* d_from, int64_t from_capacity, void* d_to, int64_t to_capacity, void* stream, int* h_overflow) {
-  EMP_REQUIRE(d_from && d_to && lt_pow2(from_capacity) && lt_pow2(to_capacity) && to_capacity > from_capacity && h_overflow,
+  EMP_REQUIRE(d_from && d_to && cells_capacity_ok(from_capacity) && cells_capacity_ok(to_capacity) && to_capacity > from_capacity && h_overflow,
               "label_table_grow: bad arguments");
-  hipStream_t s = (hipStream_t)stream;
-  const LtTable to = lt_table(d_to, to_capacity);
-  hipLaunchKernelGGL(label_table_rehash_kernel, dim3(lt_grid(from_capacity)), dim3(256), 0, s, lt_table((void*)d_from, from_capacity),
-                     from_capacity, to);
-  EMP_LAUNCH_CHECK();
-  uint32_t flag = 0;
-  EMP_CHECK_HIP(hipMemcpyAsync(&flag, &to.hdr[1], sizeof(flag), hipMemcpyDeviceToHost, s));
-  EMP_CHECK_HIP(hipStreamSynchronize(s));
-  *h_overflow = flag != 0;
-  return EMP_OK;
+  return cells_grow<LabelTableCells>(d_from, from_capacity, d_to, to_capacity, (hipStream_t)stream, h_overflow);
 }
 
 // Synchronises.  *h_num = number of keys; the first min(*h_num, max_out) of them are written.
 int emp_label_table_finalize(void* d_table, int64_t capacity, uint64_t* d_keys, uint64_t* d_counts, uint32_t* d_boxes, int64_t max_out,
                              int64_t* h_num, void* stream) {
-  EMP_REQUIRE(d_table && lt_pow2(capacity) && h_num && max_out >= 0 && (max_out == 0 || (d_keys && d_counts && d_boxes)),
+  EMP_REQUIRE(d_table && cells_capacity_ok(capacity) && h_num && max_out >= 0 && (max_out == 0 || (d_keys && d_counts && d_boxes)),
               "label_table_finalize: bad arguments");
-  hipStream_t s = (hipStream_t)stream;
-  const LtTable t = lt_table(d_table, capacity);
-  EMP_CHECK_HIP(hipMemsetAsync(&t.hdr[2], 0, 8, s));
-  hipLaunchKernelGGL(label_table_compact_kernel, dim3(lt_grid(capacity)), dim3(256), 0, s, t, capacity, d_keys, d_counts, d_boxes, max_out);
-  EMP_LAUNCH_CHECK();
-  uint64_t num = 0;
-  EMP_CHECK_HIP(hipMemcpyAsync(&num, &t.hdr[2], 8, hipMemcpyDeviceToHost, s));
-  EMP_CHECK_HIP(hipStreamSynchronize(s));
-  *h_num = (int64_t)num;
-  return EMP_OK;
+  return cells_finalize<LabelTableCells>(d_table, capacity, {d_keys, d_counts, d_boxes}, max_out, h_num, (hipStream_t)stream);
 }
 
 // The map is built on the host (linear probing, the kernels' hash) and copied: n entries are a few megabytes at most.
 // Synchronises (the staging vectors live on this call's stack).
 int emp_label_map_build(const uint64_t* h_keys, const uint64_t* h_vals, int64_t n, uint64_t* d_map_keys, uint64_t* d_map_vals,
                         int64_t map_capacity, void* stream) {
-  EMP_REQUIRE(n >= 0 && (n == 0 || (h_keys && h_vals)) && d_map_keys && d_map_vals && lt_pow2(map_capacity) && map_capacity >= 2 * n,
+  EMP_REQUIRE(n >= 0 && (n == 0 || (h_keys && h_vals)) && d_map_keys && d_map_vals && cells_capacity_ok(map_capacity) && map_capacity >= 2 * n,
               "label_map_build: the capacity must be a power of two in [64, 2^32], at least twice the number of entries");
   std::vector<uint64_t> keys((size_t)map_capacity, LT_EMPTY), vals((size_t)map_capacity, 0);
   const uint64_t mask = (uint64_t)map_capacity - 1;
@@ -645,7 +538,7 @@ int emp_label_map_build(const uint64_t* h_keys, const uint64_t* h_vals, int64_t 
 
 int emp_label_apply_map(const void* d_key, int key_bytes, const void* d_src, int src_bytes, void* d_out, int64_t z0, int depth, int H, int W,
                         int per_slice, const uint64_t* d_map_keys, const uint64_t* d_map_vals, int64_t map_capacity, void* stream) {
-  EMP_REQUIRE(depth >= 0 && H > 0 && W > 0 && z0 >= 0 && z0 + depth <= 0x7fffffffll && d_map_keys && d_map_vals && lt_pow2(map_capacity),
+  EMP_REQUIRE(depth >= 0 && H > 0 && W > 0 && z0 >= 0 && z0 + depth <= 0x7fffffffll && d_map_keys && d_map_vals && cells_capacity_ok(map_capacity),
               "label_apply_map: bad arguments");
   const int64_t n = (int64_t)depth * H * W;
   if (n == 0) return EMP_OK;

@@ -27,8 +27,10 @@
 // Overflow: as in labels.hip, slots are never released; the same slab with negated weights takes out exactly what a failed call
 // added (every sum and face count is an add modulo 2^64); box fields are idempotent and are not undone.  A cell can hold face
 // credits from the slab above it before its own count arrives; cells whose count is 0 do not exist for grow / finalize.
+// The table around the count kernel -- layout, reset, rehash, compaction, the host side of accumulate / grow / finalize -- is
+// label_table.h's; MeasureCells below tells it what a cell of this family is.
 #include "common.h"
-#include "label_stream.h"
+#include "label_table.h"
 
 namespace emp {
 namespace {
@@ -38,11 +40,9 @@ constexpr int MZ_LDS_SLOTS = 256;
 constexpr int MZ_LDS_PROBES = 8;
 constexpr int MZ_GLOBAL_PROBES = 128;
 constexpr int64_t MZ_MAX_GRID = 2048;      // two rounds of the 1024 workgroups the chip holds
-constexpr uint64_t MZ_EMPTY = ~0ull;       // keys lie in [0, 2^63)
-constexpr size_t MZ_HEADER = 64;           // bytes: [1] flags (u32 overflow, u32 range), [2] compaction cursor
+constexpr uint64_t MZ_EMPTY = CELL_EMPTY;  // keys lie in [0, 2^63)
 constexpr int MZ_SUMS = 12;                // sum z, y, x; sum zz, yy, xx, zy, zx, yx; faces z, y, x
 constexpr int MZ_FACES = 9;                // index of the first face count
-constexpr size_t MZ_SLOT_BYTES = 16 + 8 * MZ_SUMS + 24;
 
 typedef unsigned long long ull_t;
 
@@ -54,17 +54,6 @@ struct MzTable {
   uint32_t* box;
   uint64_t mask;
 };
-
-inline MzTable mz_table(void* d_table, int64_t capacity) {
-  MzTable t;
-  t.hdr = (uint64_t*)d_table;
-  t.keys = (uint64_t*)((char*)d_table + MZ_HEADER);
-  t.counts = t.keys + capacity;
-  t.sums = t.counts + capacity;
-  t.box = (uint32_t*)(t.sums + capacity * MZ_SUMS);
-  t.mask = (uint64_t)capacity - 1;
-  return t;
-}
 
 // what a run, an LDS slot or a cell adds to a cell
 struct MzRec {
@@ -98,14 +87,7 @@ __device__ __forceinline__ void mz_global_add(const MzTable& t, uint64_t key, co
 #pragma unroll
   for (int f = 0; f < MZ_SUMS; ++f)
     if (r.s[f]) atomicAdd((ull_t*)&t.sums[s * MZ_SUMS + f], (ull_t)(negate ? 0ull - r.s[f] : r.s[f]));
-  if (!negate && r.cnt) {
-    uint32_t* b = &t.box[s * 6];
-#pragma unroll
-    for (int f = 0; f < 3; ++f) {
-      if (r.lo[f] < __hip_atomic_load(&b[f], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&b[f], r.lo[f]);
-      if (r.hi[f] > __hip_atomic_load(&b[3 + f], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&b[3 + f], r.hi[f]);
-    }
-  }
+  if (!negate && r.cnt) ov_box_update_global(&t.box[s * 6], r);
 }
 
 struct MzCtx {
@@ -220,23 +202,12 @@ __device__ __forceinline__ void mz_rows(MzRec& r, uint32_t z0, uint32_t z1, uint
   r.s[8] += sy * sx * nz;
 }
 
-// offset o (<= 2^12) from the voxel (bz, by, bx) in raster order
-__device__ __forceinline__ void mz_coord(const MzCtx& c, uint32_t bx, uint32_t by, uint32_t bz, uint32_t o, uint32_t& x, uint32_t& y, uint32_t& z) {
-  x = bx + o;
-  y = by;
-  z = bz;
-  if (x >= c.W) {
-    y += ov_div(x, c.W, c.invW, x);
-    if (y >= c.H) z += ov_div(y, c.H, c.invH, y);
-  }
-}
-
 // a run of len (<= 2^10) voxels of `label` that starts at the slab's voxel (zs, ys, xs), with the faces f[z, y, x] its lane
 // counted for it (they belong to voxels of the run's first slice): one entry, or one per slice in per-slice mode
 __device__ __forceinline__ void mz_run(const MzCtx& c, uint64_t label, uint32_t xs, uint32_t ys, uint32_t zs, uint32_t len, const uint32_t* f) {
   if (label == 0) return;
   uint32_t xe, ye, ze;
-  mz_coord(c, xs, ys, zs, len - 1, xe, ye, ze);
+  ov_coord(c, xs, ys, zs, len - 1, xe, ye, ze);
   const uint32_t W = c.W, H = c.H;
   for (uint32_t z = zs;; ++z) {
     const uint32_t zl = c.per_slice ? z : ze;      // the entry covers the slices z .. zl
@@ -274,13 +245,6 @@ __device__ __forceinline__ void mz_run(const MzCtx& c, uint64_t label, uint32_t 
     mz_add(c, c.per_slice ? ((uint64_t)g0 << 32) | label : label, r);
     if (last) break;
   }
-}
-
-// values outside the key's domain: [0, 2^63) for the whole volume, [0, 2^32) per slice
-template <int S>
-__device__ __forceinline__ bool mz_out_of_range(uint64_t v, int is_signed, int per_slice) {
-  if (S == 8) return per_slice ? (v >> 32) != 0 : (v >> 63) != 0;
-  return is_signed && ((v >> (8 * S - 1)) & 1);
 }
 
 // E elements from element i0 of `base` on, of which those with an index in [0, ..) and j < nv exist (the rest read as 0):
@@ -374,12 +338,12 @@ __global__ void __launch_bounds__(MZ_THREADS) label_measure_kernel(const void* _
     uint64_t before = (uint64_t)__shfl_up((ull_t)v[E - 1], 1);
     if (lane == 0) before = (i0 > 0 && nv > 0) ? (uint64_t)((const T*)a)[i0 - 1] : 0ull;
     uint32_t x, y, z;
-    mz_coord(c, bx, by, bz, o0, x, y, z);
+    ov_coord(c, bx, by, bz, o0, x, y, z);
     const uint32_t gz = zoff + z;
     bool uni = nv == E, same = before == v[0];
 #pragma unroll
     for (int j = 0; j < E; ++j) {
-      bad = bad || mz_out_of_range<S>(v[j], is_signed, per_slice);
+      bad = bad || ov_key_out_of_range<S>(v[j], is_signed, per_slice);
       uni &= v[j] == v[0];
       same &= up[j] == v[0] && (per_slice || below[j] == v[0]);
     }
@@ -447,7 +411,7 @@ __global__ void __launch_bounds__(MZ_THREADS) label_measure_kernel(const void* _
       if (ny.n) mz_credit(c, ny.key, 1, ny.n);
       if (nz.n) mz_credit(c, nz.key, 0, nz.n);
     }
-    mz_coord(c, bx, by, bz, TILE, bx, by, bz);
+    ov_coord(c, bx, by, bz, TILE, bx, by, bz);
   }
   if (bad) atomicOr((unsigned int*)&t.hdr[1] + 1, 1u);
   __syncthreads();
@@ -471,28 +435,32 @@ __global__ void __launch_bounds__(MZ_THREADS) label_measure_kernel(const void* _
   }
 }
 
-__global__ void __launch_bounds__(256) label_measure_reset_kernel(MzTable t, int64_t capacity) {
-  const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i0 < (int64_t)(MZ_HEADER / 8)) t.hdr[i0] = 0;
-  for (int64_t i = i0; i < capacity; i += (int64_t)gridDim.x * 256) {
-    t.keys[i] = MZ_EMPTY;
-    t.counts[i] = 0;
+// a cell is a key, a count, MZ_SUMS x u64 of sums and 6 x u32 of box; finalize gives the moments and the faces as two columns
+struct MeasureCells {
+  typedef MzTable Table;
+  struct Out {
+    uint64_t* keys;
+    uint64_t* counts;
+    uint32_t* box;
+    uint64_t* sums;
+    uint64_t* faces;
+  };
+  static constexpr size_t SLOT_BYTES = 16 + 8 * MZ_SUMS + 24;
+  static constexpr int HEADER_CELLS = 0;
+  static void layout(MzTable& t, int64_t capacity) {
+    t.sums = t.counts + capacity;
+    t.box = (uint32_t*)(t.sums + capacity * MZ_SUMS);
+  }
+  static __device__ void clear(const MzTable& t, int64_t i) {
     for (int f = 0; f < MZ_SUMS; ++f) t.sums[i * MZ_SUMS + f] = 0;
     for (int f = 0; f < 3; ++f) {
       t.box[i * 6 + f] = 0xffffffffu;
       t.box[i * 6 + 3 + f] = 0u;
     }
   }
-}
-
-// every counted cell of `from` into `to` (a larger table); a cell whose count is 0 was claimed by a slab that has been undone
-__global__ void __launch_bounds__(256) label_measure_rehash_kernel(MzTable from, int64_t capacity, MzTable to) {
-  const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  for (int64_t i = i0; i < capacity; i += (int64_t)gridDim.x * 256) {
-    const uint64_t k = from.keys[i];
-    if (k == MZ_EMPTY || from.counts[i] == 0) continue;
+  static __device__ void move(const MzTable& from, int64_t i, uint64_t k, uint64_t w, const MzTable& to) {
     MzRec r;
-    r.cnt = from.counts[i];
+    r.cnt = w;
     for (int f = 0; f < MZ_SUMS; ++f) r.s[f] = from.sums[i * MZ_SUMS + f];
     for (int f = 0; f < 3; ++f) {
       r.lo[f] = from.box[i * 6 + f];
@@ -500,50 +468,12 @@ __global__ void __launch_bounds__(256) label_measure_rehash_kernel(MzTable from,
     }
     mz_global_add(to, k, r, 0);
   }
-}
-
-// counted cells -> (key, count, box, sums, faces) in arrival order (the caller sorts); hdr[2] is the cursor, one atomic per wave
-__global__ void __launch_bounds__(256) label_measure_compact_kernel(MzTable t, int64_t capacity, uint64_t* __restrict__ out_keys,
-                                                                    uint64_t* __restrict__ out_counts, uint32_t* __restrict__ out_box,
-                                                                    uint64_t* __restrict__ out_sums, uint64_t* __restrict__ out_faces,
-                                                                    int64_t max_out) {
-  const int lane = threadIdx.x & 63;
-  const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t step = (int64_t)gridDim.x * 256;
-  const int64_t rounds = (capacity + step - 1) / step;
-  for (int64_t r = 0; r < rounds; ++r) {
-    const int64_t i = i0 + r * step;
-    uint64_t k = MZ_EMPTY, w = 0;
-    if (i < capacity) {
-      k = t.keys[i];
-      w = k != MZ_EMPTY ? t.counts[i] : 0;
-    }
-    const bool keep = w != 0;
-    const uint64_t m = __ballot(keep);
-    if (m == 0) continue;
-    const int leader = __ffsll((ull_t)m) - 1;
-    ull_t base = 0;
-    if (lane == leader) base = atomicAdd((ull_t*)&t.hdr[2], (ull_t)__popcll(m));
-    base = __shfl(base, leader);
-    if (keep) {
-      const int64_t pos = (int64_t)base + __popcll(m & ((1ull << lane) - 1ull));
-      if (pos < max_out) {
-        out_keys[pos] = k;
-        out_counts[pos] = w;
-        for (int f = 0; f < 6; ++f) out_box[pos * 6 + f] = t.box[i * 6 + f];
-        for (int f = 0; f < MZ_FACES; ++f) out_sums[pos * MZ_FACES + f] = t.sums[i * MZ_SUMS + f];
-        for (int f = 0; f < 3; ++f) out_faces[pos * 3 + f] = t.sums[i * MZ_SUMS + MZ_FACES + f];
-      }
-    }
+  static __device__ void write(const MzTable& t, int64_t i, const Out& out, int64_t pos) {
+    for (int f = 0; f < 6; ++f) out.box[pos * 6 + f] = t.box[i * 6 + f];
+    for (int f = 0; f < MZ_FACES; ++f) out.sums[pos * MZ_FACES + f] = t.sums[i * MZ_SUMS + f];
+    for (int f = 0; f < 3; ++f) out.faces[pos * 3 + f] = t.sums[i * MZ_SUMS + MZ_FACES + f];
   }
-}
-
-inline int mz_grid(int64_t items) {
-  int64_t g = (items + 255) / 256;
-  return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
-}
-
-inline bool mz_pow2(int64_t c) { return c >= 64 && c <= (1ll << 32) && (c & (c - 1)) == 0; }
+};
 
 struct MzSlab {
   const void* a;
@@ -582,14 +512,12 @@ using namespace emp;
 extern "C" {
 
 size_t emp_label_measure_work_bytes(int64_t capacity) {
-  return mz_pow2(capacity) ? MZ_HEADER + (size_t)capacity * MZ_SLOT_BYTES : 0;
+  return cells_capacity_ok(capacity) ? CELL_HEADER + (size_t)capacity * MeasureCells::SLOT_BYTES : 0;
 }
 
 int emp_label_measure_reset(void* d_table, int64_t capacity, void* stream) {
-  EMP_REQUIRE(d_table && mz_pow2(capacity), "label_measure_reset: the capacity must be a power of two in [64, 2^32]");
-  hipLaunchKernelGGL(label_measure_reset_kernel, dim3(mz_grid(capacity)), dim3(256), 0, (hipStream_t)stream, mz_table(d_table, capacity), capacity);
-  EMP_LAUNCH_CHECK();
-  return EMP_OK;
+  EMP_REQUIRE(d_table && cells_capacity_ok(capacity), "label_measure_reset: the capacity must be a power of two in [64, 2^32]");
+  return cells_reset<MeasureCells>(d_table, capacity, (hipStream_t)stream);
 }
 
 // Synchronises the stream (it reads the table's flags).  *h_overflow = 1: the table was too small for this slab; what the call
@@ -597,7 +525,7 @@ int emp_label_measure_reset(void* d_table, int64_t capacity, void* stream) {
 int emp_label_measure_accumulate(const void* d_labels, int in_bytes, int64_t z0, int depth, int H, int W, int64_t total_depth,
                                  const void* d_halo, int per_slice, int border_faces, void* d_table, int64_t capacity, void* stream,
                                  int* h_overflow) {
-  EMP_REQUIRE(d_table && mz_pow2(capacity) && h_overflow && depth >= 0 && H > 0 && W > 0 && (depth == 0 || d_labels),
+  EMP_REQUIRE(d_table && cells_capacity_ok(capacity) && h_overflow && depth >= 0 && H > 0 && W > 0 && (depth == 0 || d_labels),
               "label_measure_accumulate: bad arguments");
   EMP_REQUIRE(z0 >= 0 && total_depth >= z0 + depth, "label_measure_accumulate: the slab [%lld, %lld) does not lie in a volume of depth %lld",
               (long long)z0, (long long)(z0 + depth), (long long)total_depth);
@@ -621,55 +549,24 @@ int emp_label_measure_accumulate(const void* d_labels, int in_bytes, int64_t z0,
   g.per_slice = per_slice;
   g.border = border_faces != 0;
   if (g.n == 0) return EMP_OK;
-  const MzTable t = mz_table(d_table, capacity);
-  int rc = mz_dispatch(g, in_bytes, t, 0, s);
-  if (rc) return rc;
-  uint32_t flags[2] = {0, 0};
-  EMP_CHECK_HIP(hipMemcpyAsync(flags, &t.hdr[1], sizeof(flags), hipMemcpyDeviceToHost, s));
-  EMP_CHECK_HIP(hipStreamSynchronize(s));
-  EMP_REQUIRE(flags[1] == 0, "label_measure_accumulate: a label outside the key's domain (negative, or beyond 2^63 / per slice 2^32)");
-  if (flags[0]) {
-    rc = mz_dispatch(g, in_bytes, t, 1, s);      // the same slab with negated weights
-    if (rc) return rc;
-    EMP_CHECK_HIP(hipMemsetAsync(&t.hdr[1], 0, 8, s));
-    EMP_CHECK_HIP(hipStreamSynchronize(s));
-    *h_overflow = 1;
-  }
-  return EMP_OK;
+  const MzTable t = cells_table<MeasureCells>(d_table, capacity);
+  return cells_accumulate(t.hdr, s, "label_measure_accumulate", "the key's domain (negative, or beyond 2^63 / per slice 2^32)",
+                          [&](int negate) { return mz_dispatch(g, in_bytes, t, negate, s); }, h_overflow);
 }
 
 // Moves the cells of a table into an empty (reset) larger one.  Synchronises; *h_overflow = 1: d_to is too small as well.
 int emp_label_measure_grow(const void* d_from, int64_t from_capacity, void* d_to, int64_t to_capacity, void* stream, int* h_overflow) {
-  EMP_REQUIRE(d_from && d_to && mz_pow2(from_capacity) && mz_pow2(to_capacity) && to_capacity > from_capacity && h_overflow,
+  EMP_REQUIRE(d_from && d_to && cells_capacity_ok(from_capacity) && cells_capacity_ok(to_capacity) && to_capacity > from_capacity && h_overflow,
               "label_measure_grow: bad arguments");
-  hipStream_t s = (hipStream_t)stream;
-  const MzTable to = mz_table(d_to, to_capacity);
-  hipLaunchKernelGGL(label_measure_rehash_kernel, dim3(mz_grid(from_capacity)), dim3(256), 0, s, mz_table((void*)d_from, from_capacity),
-                     from_capacity, to);
-  EMP_LAUNCH_CHECK();
-  uint32_t flag = 0;
-  EMP_CHECK_HIP(hipMemcpyAsync(&flag, &to.hdr[1], sizeof(flag), hipMemcpyDeviceToHost, s));
-  EMP_CHECK_HIP(hipStreamSynchronize(s));
-  *h_overflow = flag != 0;
-  return EMP_OK;
+  return cells_grow<MeasureCells>(d_from, from_capacity, d_to, to_capacity, (hipStream_t)stream, h_overflow);
 }
 
 // Synchronises.  *h_num = number of keys; the first min(*h_num, max_out) of them are written.
 int emp_label_measure_finalize(void* d_table, int64_t capacity, uint64_t* d_keys, uint64_t* d_counts, uint32_t* d_boxes, uint64_t* d_sums,
                                uint64_t* d_faces, int64_t max_out, int64_t* h_num, void* stream) {
-  EMP_REQUIRE(d_table && mz_pow2(capacity) && h_num && max_out >= 0 && (max_out == 0 || (d_keys && d_counts && d_boxes && d_sums && d_faces)),
+  EMP_REQUIRE(d_table && cells_capacity_ok(capacity) && h_num && max_out >= 0 && (max_out == 0 || (d_keys && d_counts && d_boxes && d_sums && d_faces)),
               "label_measure_finalize: bad arguments");
-  hipStream_t s = (hipStream_t)stream;
-  const MzTable t = mz_table(d_table, capacity);
-  EMP_CHECK_HIP(hipMemsetAsync(&t.hdr[2], 0, 8, s));
-  hipLaunchKernelGGL(label_measure_compact_kernel, dim3(mz_grid(capacity)), dim3(256), 0, s, t, capacity, d_keys, d_counts, d_boxes, d_sums,
-                     d_faces, max_out);
-  EMP_LAUNCH_CHECK();
-  uint64_t num = 0;
-  EMP_CHECK_HIP(hipMemcpyAsync(&num, &t.hdr[2], 8, hipMemcpyDeviceToHost, s));
-  EMP_CHECK_HIP(hipStreamSynchronize(s));
-  *h_num = (int64_t)num;
-  return EMP_OK;
+  return cells_finalize<MeasureCells>(d_table, capacity, {d_keys, d_counts, d_boxes, d_sums, d_faces}, max_out, h_num, (hipStream_t)stream);
 }
 
 }  // extern "C"

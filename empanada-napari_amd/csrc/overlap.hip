@@ -28,11 +28,14 @@
 // every time: running the same slab again with negated weights removes exactly what the failed call added.  That is how
 // emp_label_overlap_accumulate leaves the table as it found it when it reports an overflow; the caller then moves the
 // table to a larger one (emp_label_overlap_grow) and counts the slab again.
+// This file has the count kernel, its probe loops and the argument checks of the entries.  The table around them -- layout,
+// reset, rehash, compaction, and the host side of accumulate / grow / finalize -- is label_table.h's, which labels.hip and
+// measure.hip use as well; OverlapCells below tells it what a cell of this family is.
 #include <algorithm>
 #include <vector>
 
 #include "common.h"
-#include "label_stream.h"
+#include "label_table.h"
 
 namespace emp {
 namespace {
@@ -46,8 +49,7 @@ constexpr int OV_GLOBAL_PROBES = 128;
 #ifndef OV_MAX_GRID
 #define OV_MAX_GRID 8192                 // 32 workgroups per CU, 8 of them resident: short stretches even out the objects' share of work
 #endif
-constexpr uint64_t OV_EMPTY = ~0ull;     // the pair (2^32 - 1, 2^32 - 1) is legal: it is counted in the header instead
-constexpr size_t OV_HEADER = 64;         // bytes: [0] count of the OV_EMPTY pair, [1] flags (u32 overflow, u32 range), [2] compaction cursor
+constexpr uint64_t OV_EMPTY = CELL_EMPTY;      // the pair (2^32 - 1, 2^32 - 1) is legal: it is counted in hdr[0] instead
 
 typedef unsigned long long ull_t;
 
@@ -57,15 +59,6 @@ struct OvTable {
   uint64_t* counts;
   uint64_t mask;
 };
-
-inline OvTable ov_table(void* d_table, int64_t capacity) {
-  OvTable t;
-  t.hdr = (uint64_t*)d_table;
-  t.keys = (uint64_t*)((char*)d_table + OV_HEADER);
-  t.counts = t.keys + capacity;
-  t.mask = (uint64_t)capacity - 1;
-  return t;
-}
 
 __device__ __forceinline__ void ov_global_add(const OvTable& t, uint64_t key, uint64_t w) {
   if (key == OV_EMPTY) {
@@ -198,66 +191,21 @@ __global__ void __launch_bounds__(OV_THREADS) overlap_count_kernel(const void* _
 #endif
 }
 #undef OV_ADD
-#undef OV_ADD
 
-__global__ void __launch_bounds__(256) overlap_reset_kernel(OvTable t, int64_t capacity) {
-  const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i0 < (int64_t)(OV_HEADER / 8)) t.hdr[i0] = 0;
-  for (int64_t i = i0; i < capacity; i += (int64_t)gridDim.x * 256) {
-    t.keys[i] = OV_EMPTY;
-    t.counts[i] = 0;
-  }
-}
-
-// every counted cell of `from` into `to` (a larger table); a cell whose count is 0 was claimed by a slab that has been undone
-__global__ void __launch_bounds__(256) overlap_rehash_kernel(OvTable from, int64_t capacity, OvTable to) {
-  const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i0 == 0 && from.hdr[0] != 0) ov_global_add(to, OV_EMPTY, from.hdr[0]);
-  for (int64_t i = i0; i < capacity; i += (int64_t)gridDim.x * 256) {
-    const uint64_t k = from.keys[i], c = from.counts[i];
-    if (k != OV_EMPTY && c != 0) ov_global_add(to, k, c);
-  }
-}
-
-// occupied cells -> (key, count) in arrival order (the caller sorts); hdr[2] is the cursor, one atomic per wave
-__global__ void __launch_bounds__(256) overlap_compact_kernel(OvTable t, int64_t capacity, uint64_t* __restrict__ out_keys,
-                                                              uint64_t* __restrict__ out_counts, int64_t max_out) {
-  const int lane = threadIdx.x & 63;
-  const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t step = (int64_t)gridDim.x * 256;
-  const int64_t rounds = (capacity + 1 + step - 1) / step;      // slot `capacity` stands for the header's pair
-  for (int64_t r = 0; r < rounds; ++r) {
-    const int64_t i = i0 + r * step;
-    uint64_t k = OV_EMPTY, c = 0;
-    if (i < capacity) {
-      k = t.keys[i];
-      c = k != OV_EMPTY ? t.counts[i] : 0;
-    } else if (i == capacity) {
-      c = t.hdr[0];
-    }
-    const bool keep = c != 0;
-    const uint64_t m = __ballot(keep);
-    if (m == 0) continue;
-    const int leader = __ffsll((ull_t)m) - 1;
-    ull_t base = 0;
-    if (lane == leader) base = atomicAdd((ull_t*)&t.hdr[2], (ull_t)__popcll(m));
-    base = __shfl(base, leader);
-    if (keep) {
-      const int64_t pos = (int64_t)base + __popcll(m & ((1ull << lane) - 1ull));
-      if (pos < max_out) {
-        out_keys[pos] = k;
-        out_counts[pos] = c;
-      }
-    }
-  }
-}
-
-inline int ov_grid(int64_t items) {
-  int64_t g = (items + 255) / 256;
-  return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
-}
-
-inline bool ov_pow2(int64_t c) { return c >= 64 && c <= (1ll << 32) && (c & (c - 1)) == 0; }
+// a cell is a key and a count and nothing else; the pair that equals OV_EMPTY is the one cell in the header
+struct OverlapCells {
+  typedef OvTable Table;
+  struct Out {
+    uint64_t* keys;
+    uint64_t* counts;
+  };
+  static constexpr size_t SLOT_BYTES = 16;
+  static constexpr int HEADER_CELLS = 1;
+  static void layout(OvTable&, int64_t) {}
+  static __device__ void clear(const OvTable&, int64_t) {}
+  static __device__ void move(const OvTable&, int64_t, uint64_t k, uint64_t c, const OvTable& to) { ov_global_add(to, k, c); }
+  static __device__ void write(const OvTable&, int64_t, const Out&, int64_t) {}
+};
 
 template <int SA, int SB>
 int ov_launch(const void* a, const void* b, int64_t n, int sa, int sb, const OvTable& t, int negate, hipStream_t s) {
@@ -292,72 +240,40 @@ using namespace emp;
 extern "C" {
 
 size_t emp_label_overlap_work_bytes(int64_t capacity) {
-  return ov_pow2(capacity) ? OV_HEADER + (size_t)capacity * 16 : 0;
+  return cells_capacity_ok(capacity) ? CELL_HEADER + (size_t)capacity * OverlapCells::SLOT_BYTES : 0;
 }
 
 int emp_label_overlap_reset(void* d_table, int64_t capacity, void* stream) {
-  EMP_REQUIRE(d_table && ov_pow2(capacity), "label_overlap_reset: the capacity must be a power of two in [64, 2^32]");
-  hipLaunchKernelGGL(overlap_reset_kernel, dim3(ov_grid(capacity)), dim3(256), 0, (hipStream_t)stream, ov_table(d_table, capacity), capacity);
-  EMP_LAUNCH_CHECK();
-  return EMP_OK;
+  EMP_REQUIRE(d_table && cells_capacity_ok(capacity), "label_overlap_reset: the capacity must be a power of two in [64, 2^32]");
+  return cells_reset<OverlapCells>(d_table, capacity, (hipStream_t)stream);
 }
 
 // Synchronises the stream (it reads the table's flags).  *h_overflow = 1: the table was too small for this slab; what the
 // call had added has been taken out again, the table is as before the call.
 int emp_label_overlap_accumulate(const void* d_a, int a_bytes, const void* d_b, int b_bytes, int64_t n, void* d_table,
                                  int64_t capacity, void* stream, int* h_overflow) {
-  EMP_REQUIRE(d_table && ov_pow2(capacity) && n >= 0 && h_overflow && (n == 0 || (d_a && d_b)), "label_overlap_accumulate: bad arguments");
+  EMP_REQUIRE(d_table && cells_capacity_ok(capacity) && n >= 0 && h_overflow && (n == 0 || (d_a && d_b)), "label_overlap_accumulate: bad arguments");
   hipStream_t s = (hipStream_t)stream;
   *h_overflow = 0;
   if (n == 0) return EMP_OK;
-  const OvTable t = ov_table(d_table, capacity);
-  int rc = ov_dispatch(d_a, a_bytes, d_b, b_bytes, n, t, 0, s);
-  if (rc) return rc;
-  uint32_t flags[2] = {0, 0};
-  EMP_CHECK_HIP(hipMemcpyAsync(flags, &t.hdr[1], sizeof(flags), hipMemcpyDeviceToHost, s));
-  EMP_CHECK_HIP(hipStreamSynchronize(s));
-  EMP_REQUIRE(flags[1] == 0, "label_overlap_accumulate: a label outside [0, 2^32) (negative, or too large for the 32-bit halves of a pair)");
-  if (flags[0]) {
-    rc = ov_dispatch(d_a, a_bytes, d_b, b_bytes, n, t, 1, s);      // the same slab with negated weights
-    if (rc) return rc;
-    EMP_CHECK_HIP(hipMemsetAsync(&t.hdr[1], 0, 8, s));
-    EMP_CHECK_HIP(hipStreamSynchronize(s));
-    *h_overflow = 1;
-  }
-  return EMP_OK;
+  const OvTable t = cells_table<OverlapCells>(d_table, capacity);
+  return cells_accumulate(t.hdr, s, "label_overlap_accumulate", "[0, 2^32) (negative, or too large for the 32-bit halves of a pair)",
+                          [&](int negate) { return ov_dispatch(d_a, a_bytes, d_b, b_bytes, n, t, negate, s); }, h_overflow);
 }
 
 // Moves the cells of a table into an empty (reset) larger one.  Synchronises; *h_overflow = 1: d_to is too small as well
 // (reset it, or a larger one, and call again: d_from is unchanged).
 int emp_label_overlap_grow(const void* d_from, int64_t from_capacity, void* d_to, int64_t to_capacity, void* stream, int* h_overflow) {
-  EMP_REQUIRE(d_from && d_to && ov_pow2(from_capacity) && ov_pow2(to_capacity) && to_capacity > from_capacity && h_overflow,
+  EMP_REQUIRE(d_from && d_to && cells_capacity_ok(from_capacity) && cells_capacity_ok(to_capacity) && to_capacity > from_capacity && h_overflow,
               "label_overlap_grow: bad arguments");
-  hipStream_t s = (hipStream_t)stream;
-  const OvTable to = ov_table(d_to, to_capacity);
-  hipLaunchKernelGGL(overlap_rehash_kernel, dim3(ov_grid(from_capacity)), dim3(256), 0, s, ov_table((void*)d_from, from_capacity),
-                     from_capacity, to);
-  EMP_LAUNCH_CHECK();
-  uint32_t flag = 0;
-  EMP_CHECK_HIP(hipMemcpyAsync(&flag, &to.hdr[1], sizeof(flag), hipMemcpyDeviceToHost, s));
-  EMP_CHECK_HIP(hipStreamSynchronize(s));
-  *h_overflow = flag != 0;
-  return EMP_OK;
+  return cells_grow<OverlapCells>(d_from, from_capacity, d_to, to_capacity, (hipStream_t)stream, h_overflow);
 }
 
 // Synchronises.  *h_num = number of distinct pairs; the first min(*h_num, max_out) of them are written.
 int emp_label_overlap_finalize(void* d_table, int64_t capacity, uint64_t* d_keys, uint64_t* d_counts, int64_t max_out,
                                int64_t* h_num, void* stream) {
-  EMP_REQUIRE(d_table && ov_pow2(capacity) && h_num && max_out >= 0 && (max_out == 0 || (d_keys && d_counts)), "label_overlap_finalize: bad arguments");
-  hipStream_t s = (hipStream_t)stream;
-  const OvTable t = ov_table(d_table, capacity);
-  EMP_CHECK_HIP(hipMemsetAsync(&t.hdr[2], 0, 8, s));
-  hipLaunchKernelGGL(overlap_compact_kernel, dim3(ov_grid(capacity + 1)), dim3(256), 0, s, t, capacity, d_keys, d_counts, max_out);
-  EMP_LAUNCH_CHECK();
-  uint64_t num = 0;
-  EMP_CHECK_HIP(hipMemcpyAsync(&num, &t.hdr[2], 8, hipMemcpyDeviceToHost, s));
-  EMP_CHECK_HIP(hipStreamSynchronize(s));
-  *h_num = (int64_t)num;
-  return EMP_OK;
+  EMP_REQUIRE(d_table && cells_capacity_ok(capacity) && h_num && max_out >= 0 && (max_out == 0 || (d_keys && d_counts)), "label_overlap_finalize: bad arguments");
+  return cells_finalize<OverlapCells>(d_table, capacity, {d_keys, d_counts}, max_out, h_num, (hipStream_t)stream);
 }
 
 // HOST.  k cells (h_a[i], h_b[i]) -> h_count[i], sorted by (a, b), each pair once (emp_label_overlap_finalize's output after the sort).
