@@ -25,68 +25,21 @@
 //
 // Summation order of the depthwise taps (ky-major, kx-minor, fp32 fma chain from 0) and of the GEMM
 // (ascending 32-channel K-steps) equals the unfused dwconv_kernel + conv_igemm_kernel pair.
-#include "common.h"
+#include "sepconv_common.h"
 
 namespace emp {
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+constexpr int SC_BT_BYTES = 128 * 128;                // B tile: 128 pixels x 64 channels fp16 = 16384
 
-constexpr int SC_TH = 8, SC_TW = 16;                  // output tile (rows x cols) = 128 pixels
-// halo tile of a KS x KS depthwise kernel: (8 + KS - 1) rows x 20 columns (KS = 5: 12 x 20 = 240 pixels = 30 LDS-DMA
-// instructions of 8 pixels; KS = 3: 10 x 20 = 200 pixels = 25 instructions, the two right-most columns unused)
-constexpr int SC_IW = SC_TW + 4;
-constexpr int sc_npix(int ks) { return (SC_TH + ks - 1) * SC_IW; }
-constexpr int sc_halo_bytes(int ks) { return sc_npix(ks) * 128; }
-constexpr int SC_BT_BYTES = 128 * 128;                // 16384
-
-struct SepParams {
-  const half_t* in;
-  int N, H, W, C, in_ld;
-  const half_t* dww;     // [25][C] fp16
-  const half_t* pww;     // pointwise weights in MFMA-fragment order (sepconv5_pack_pw)
-  const float* bias;     // [Cout]
-  half_t* out;           // (N,H,W,out_ld) or nullptr (head mode)
-  int out_ld, act;
-  const half_t* zero;    // >= 2 KiB of zeros
-  int tiles_x, tiles_y;
-  int tiles;
-  const float* hw;       // head mode: [hc][Cout] fp32
-  const float* hb;       // [hc]
-  int hc;
-  float* hout;           // (N,hc) planes of `plane` floats
-  int64_t plane;
-};
-
-template <int ACT>
-__device__ __forceinline__ float sc_act(float x) {
-  if (ACT == 1) return fmaxf(x, 0.f);
-  if (ACT == 2) return x / (1.f + __expf(-x));
-  return x;
-}
-
-__device__ __forceinline__ void tile_coords(const SepParams& p, int tile, int& n, int& y0, int& x0) {
-  const int tx = tile % p.tiles_x;
-  const int r = tile / p.tiles_x;
-  const int ty = r % p.tiles_y;
-  n = r / p.tiles_y;
-  y0 = ty * SC_TH;
-  x0 = tx * SC_TW;
-}
-
-// workgroup barrier that orders LDS traffic only: global loads / LDS-DMA stay in flight across it
-__device__ __forceinline__ void lds_barrier() {
-  // Raw barrier that orders LDS traffic only.  A fence (or __syncthreads) would also drain vmcnt: an in-flight
-  // LDS-DMA is a pending LDS write on the VM counter.  The "memory" clobber keeps the compiler from moving
-  // memory accesses across it; DMA completion is handled by the counted vmcnt waits of the issuing waves.
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
+// dww: [25][C] fp16; pww: sepconv5_pack_pw; bias may be null
+typedef SepParams<half_t, half_t> Sep5Params;
 
 // NDW = number of depthwise waves (4 or 8: one or two per SIMD), NMW = number of mma waves (4 or 8),
 // MT = 16-cout MFMA row tiles per mma wave: Cout = NMW * 16 * MT.
 template <int KS, int NDW, int NMW, int MT, bool HEAD, int ACT>
-__global__ void __launch_bounds__(64 * (NDW + NMW), 1) sepconv5_kernel(const SepParams p) {
+__global__ void __launch_bounds__(64 * (NDW + NMW), 1) sepconv5_kernel(const Sep5Params p) {
   constexpr int KK = KS * KS, PAD = KS / 2;
   constexpr int SC_NPIX = sc_npix(KS), SC_NST = SC_NPIX / 8, SC_HALO_BYTES = sc_halo_bytes(KS);
   constexpr int NT = 64 * (NDW + NMW);      // threads
@@ -204,7 +157,7 @@ __global__ void __launch_bounds__(64 * (NDW + NMW), 1) sepconv5_kernel(const Sep
         for (int k = 0; k < NDMA; ++k) sptr[k] = p.zero;
       } else if (ch == 0) {
         int n, y0, x0;
-        tile_coords(p, tile_of(tile_it), n, y0, x0);
+        tile_coords(p.tiles_x, p.tiles_y, tile_of(tile_it), n, y0, x0);
         const half_t* src = p.in + (size_t)n * p.H * p.W * p.in_ld + (lane & 7) * 8;
 #pragma unroll
         for (int k = 0; k < NDMA; ++k) {
@@ -246,16 +199,8 @@ __global__ void __launch_bounds__(64 * (NDW + NMW), 1) sepconv5_kernel(const Sep
     // step counters: c1 = (g-1) % NC with tile t1, c2 = (g+2) % NC with tile t2, ring2 = (g+2) % 3
     int c1 = NC - 1, t1 = -1, c2 = 2 % NC, t2 = 2 / NC, ring2 = 2;
     for (int g = 0; g <= LAST; ++g) {
-      if (HEAD && g >= 2 && c1 == 0 && fh < p.hc) {
-        // finish the head of tile t1 - 1 (its last chunk was multiplied in the previous step)
-        int n, y0, x0;
-        tile_coords(p, tile_of(t1 - 1), n, y0, x0);
-        const int oy = y0 + (fpx >> 4), ox = x0 + (fpx & 15);
-        float v = fhb;
-#pragma unroll
-        for (int wv = 0; wv < NMW; ++wv) v += red[(wv * 128 + fpx) * 2 + fh];
-        if (oy < p.H && ox < p.W) p.hout[((size_t)n * p.hc + fh) * p.plane + (size_t)oy * p.W + ox] = v;
-      }
+      // finish the head of tile t1 - 1 (its last chunk was multiplied in the previous step)
+      if (HEAD && g >= 2 && c1 == 0 && fh < p.hc) head_store<NMW>(p, red, tile_of(t1 - 1), fh, fpx, fpx >> 4, fpx & 15, fhb);
       const bool do_mma = g >= 1 && g - 1 < S;
       // VM issue order: [weights of this step, issued at the end of the previous step] [stores] [NDMA DMA loads of
       // stage(g+2)].  Loads retire in order, so vmcnt(NDMA) == "the weights AND the halo of step g+1 (DMA'd one
@@ -304,7 +249,7 @@ __global__ void __launch_bounds__(64 * (NDW + NMW), 1) sepconv5_kernel(const Sep
       load_a(c1 + 1 == NC ? 0 : c1 + 1);   // weights of chunk g % NC, multiplied in step g+1; `a` is dead until the next wait
       if (do_mma && c1 == NC - 1) {
         int n, y0, x0;
-        tile_coords(p, tile_of(t1), n, y0, x0);
+        tile_coords(p.tiles_x, p.tiles_y, tile_of(t1), n, y0, x0);
         const int ox = x0 + n16;
         if (!HEAD) {
 #pragma unroll
@@ -344,22 +289,7 @@ __global__ void __launch_bounds__(64 * (NDW + NMW), 1) sepconv5_kernel(const Sep
 #pragma unroll 1
           for (int h = 0; h < p.hc; ++h) {
             float sum[8];
-#pragma unroll
-            for (int nt = 0; nt < 8; ++nt) sum[nt] = 0.f;
-#pragma unroll
-            for (int blk = 0; blk < MT / 2; ++blk) {
-              const float* hp = hwl + h * COUT + wm * 16 * MT + blk * 32 + g16 * 8;
-              float hv[8];
-#pragma unroll
-              for (int e = 0; e < 8; ++e) hv[e] = hp[e];
-#pragma unroll
-              for (int nt = 0; nt < 8; ++nt)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                  sum[nt] = fmaf(acc[2 * blk][nt][e], hv[e], sum[nt]);
-                  sum[nt] = fmaf(acc[2 * blk + 1][nt][e], hv[4 + e], sum[nt]);
-                }
-            }
+            head_plane_sums<MT>(acc, hwl + h * COUT + wm * 16 * MT + g16 * 8, sum);
 #pragma unroll
             for (int nt = 0; nt < 8; ++nt) {
               float v = sum[nt];
@@ -399,32 +329,21 @@ __global__ void __launch_bounds__(256) sepconv5_pack_pw_kernel(const half_t* __r
   }
 }
 
-template <int KS, int NDW, int NMW, int MT, bool HEAD, int ACT>
-int launch_act(const SepParams& p, size_t lds_bytes, int grid, hipStream_t s) {
-  if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(&sepconv5_kernel<KS, NDW, NMW, MT, HEAD, ACT>), 160 * 1024)) return rc;
-  hipLaunchKernelGGL((sepconv5_kernel<KS, NDW, NMW, MT, HEAD, ACT>), dim3(grid), dim3(64 * (NDW + NMW)), lds_bytes, s, p);
-  EMP_LAUNCH_CHECK();
-  return EMP_OK;
-}
-
 template <int KS, int NDW, int NMW, int MT, bool HEAD>
-int launch_one(const SepParams& p, size_t lds_bytes, int grid, hipStream_t s) {
-  if (p.act == 1) return launch_act<KS, NDW, NMW, MT, HEAD, 1>(p, lds_bytes, grid, s);
-  if (p.act == 2) return launch_act<KS, NDW, NMW, MT, HEAD, 2>(p, lds_bytes, grid, s);
-  return launch_act<KS, NDW, NMW, MT, HEAD, 0>(p, lds_bytes, grid, s);
+int launch_sep5(const Sep5Params& p, size_t lds_bytes, hipStream_t s) {
+  return launch_by_act([](auto a) { return &sepconv5_kernel<KS, NDW, NMW, MT, HEAD, decltype(a)::value>; }, p, 64 * (NDW + NMW), lds_bytes, s);
 }
 
 }  // namespace
 
 static size_t sepconv5_lds_bytes(int C, int Cout, int head_c, int ks = 5) {
   const int nmw = Cout == 256 ? 8 : 4;
-  return 3 * sc_halo_bytes(ks) + 2 * SC_BT_BYTES + (size_t)C * ks * ks * 4 + (size_t)Cout * 4 +
-         (head_c ? (size_t)2 * Cout * 4 + (size_t)nmw * 128 * 2 * 4 : 0);
+  return sep_lds_bytes(ks, SC_BT_BYTES, Cout, head_c, nmw) + (size_t)C * ks * ks * 4 + (size_t)Cout * 4;      // + taps, bias
 }
 
 bool sepconv5_supported(int C, int Cout, int head_c) {
-  return C % 64 == 0 && C >= 128 && (Cout == 128 || Cout == 256) && head_c >= 0 && head_c <= 2 &&
-         sepconv5_lds_bytes(C, Cout, head_c) <= 160 * 1024;   // C <= 320 (features) / C <= 192 (heads)
+  return C % 64 == 0 && C >= 128 && sep_couts_supported(Cout, head_c) &&
+         sepconv5_lds_bytes(C, Cout, head_c) <= SC_MAX_LDS;   // C <= 320 (features) / C <= 192 (heads)
 }
 
 // out != nullptr: y = act(pw(dw(x)) + bias) -> (N,H,W,out_ld) fp16.
@@ -444,35 +363,20 @@ int launch_sepconv5(const half_t* in, int N, int H, int W, int C, int in_ld, con
                     int ks) {
   EMP_REQUIRE(ks == 5 || (ks == 3 && head_c == 0), "sepconv: depthwise kernel %d unsupported", ks);
   EMP_REQUIRE(sepconv5_supported(C, Cout, head_c), "sepconv5: unsupported shape C=%d Cout=%d head=%d", C, Cout, head_c);
-  EMP_REQUIRE(act >= 0 && act <= 2, "sepconv5: bad activation %d", act);
-  EMP_REQUIRE((head_c > 0) != (out != nullptr), "sepconv5: exactly one of the feature / head outputs");
-  EMP_REQUIRE(in_ld % 8 == 0 && (out == nullptr || out_ld % 8 == 0), "sepconv5: 16-byte row alignment");
-  SepParams p{};
-  p.in = in; p.N = N; p.H = H; p.W = W; p.C = C; p.in_ld = in_ld;
-  p.dww = dww; p.pww = pww; p.bias = bias;
-  p.out = out; p.out_ld = out_ld; p.act = act; p.zero = zero;
-  p.tiles_x = cdiv(W, SC_TW); p.tiles_y = cdiv(H, SC_TH);
-  const int64_t tiles = (int64_t)N * p.tiles_x * p.tiles_y;
-  EMP_REQUIRE(tiles < (1ll << 30), "sepconv5: too many tiles");
-  p.tiles = (int)tiles;
-  p.hw = head_w; p.hb = head_b; p.hc = head_c; p.hout = hout; p.plane = plane;
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    EMP_CHECK_HIP(hipGetDevice(&dev));
-    EMP_CHECK_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-    n_cu = n_cu >= 8 ? (n_cu / 8) * 8 : 8;
-  }
-  const int grid = n_cu;
+  Sep5Params p{};
+  if (int rc = sep_fill_params(p, "sepconv5", in, N, H, W, C, in_ld, act, out, out_ld, in_ld % 8 == 0 && (out == nullptr || out_ld % 8 == 0),
+                               head_w, head_b, head_c, hout, plane))
+    return rc;
+  p.dww = dww; p.pww = pww; p.bias = bias; p.zero = zero;
   const size_t lds_bytes = sepconv5_lds_bytes(C, Cout, head_c, ks);
   if (ks == 3) {     // BiFPN nodes (depthwise 3x3 -> pointwise -> BN -> SiLU); no head mode
-    if (Cout == 256) return launch_one<3, 4, 8, 2, false>(p, lds_bytes, grid, s);
-    return launch_one<3, 4, 4, 2, false>(p, lds_bytes, grid, s);
+    if (Cout == 256) return launch_sep5<3, 4, 8, 2, false>(p, lds_bytes, s);
+    return launch_sep5<3, 4, 4, 2, false>(p, lds_bytes, s);
   }
   // (two depthwise waves per SIMD, <8, 8, 2>, measured no faster: the mma role's vector-memory issue bounds the step)
   if (Cout == 256)
-    return head_c ? launch_one<5, 4, 8, 2, true>(p, lds_bytes, grid, s) : launch_one<5, 4, 8, 2, false>(p, lds_bytes, grid, s);
-  return head_c ? launch_one<5, 4, 4, 2, true>(p, lds_bytes, grid, s) : launch_one<5, 4, 4, 2, false>(p, lds_bytes, grid, s);
+    return head_c ? launch_sep5<5, 4, 8, 2, true>(p, lds_bytes, s) : launch_sep5<5, 4, 8, 2, false>(p, lds_bytes, s);
+  return head_c ? launch_sep5<5, 4, 4, 2, true>(p, lds_bytes, s) : launch_sep5<5, 4, 4, 2, false>(p, lds_bytes, s);
 }
 
 }  // namespace emp

@@ -47,75 +47,17 @@
 //
 // Summation order: depthwise taps ky-major, kx-minor, fp32 fma chain from 0; GEMM ascending 32-channel K-steps,
 // per step w*hi, w*lo (WS: then w_lo*hi), from the bias.  Fixed, so a batch of N equals N batch-1 calls bit for bit.
-#include "common.h"
+#include "sepconv_common.h"
 
 namespace emp {
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int SC_TH = 8, SC_TW = 16;                  // output tile (rows x cols) = 128 pixels
-// halo tile of a KS x KS depthwise kernel: (8 + KS - 1) rows x 20 columns (KS = 5: 12 x 20 = 240 pixels = 30 LDS-DMA
-// instructions of 8 pixels; KS = 3: 10 x 20 = 200 pixels = 25 instructions, the two right-most columns unused)
-constexpr int SC_IW = SC_TW + 4;
-constexpr int sc_npix(int ks) { return (SC_TH + ks - 1) * SC_IW; }
-constexpr int sc_halo_bytes(int ks) { return sc_npix(ks) * 128; }
 constexpr int SC_BT_HALF = 128 * 128;                 // 128 pixels x 64 channels fp16
 constexpr int SC_BT_BYTES = 2 * SC_BT_HALF;           // hi tile, lo tile
-constexpr int SC_NDW = 4, SC_NMW = 4;                 // depthwise / mma waves (one of each per SIMD)
 
-struct SepParams {
-  const half_t* in;
-  int N, H, W, C, in_ld;
-  const float* dww;      // [C/64][KS*KS][64] fp32 (sepconv5_pack_dw)
-  const half_t* pww;     // pointwise weights (fp16) in MFMA-fragment order (sepconvp_pack_pw)
-  const float* bias;     // [Cout] (never null: the launcher substitutes zeros)
-  half_t* out;           // (N,H,W,out_ld) or nullptr (head mode)
-  int out_ld, act;
-  const half_t* zero;    // >= 2 KiB of zeros
-  int tiles_x, tiles_y;
-  int tiles;
-  const float* hw;       // head mode: [hc][Cout] fp32
-  const float* hb;       // [hc]
-  int hc;
-  float* hout;           // (N,hc) planes of `plane` floats
-  int64_t plane;
-};
-
-template <int ACT>
-__device__ __forceinline__ float sc_act(float x) {
-  if (ACT == 1) return fmaxf(x, 0.f);
-  if (ACT == 2) return x / (1.f + __expf(-x));
-  return x;
-}
-
-__device__ __forceinline__ void tile_coords(const SepParams& p, int tile, int& n, int& y0, int& x0) {
-  const int tx = tile % p.tiles_x;
-  const int r = tile / p.tiles_x;
-  const int ty = r % p.tiles_y;
-  n = r / p.tiles_y;
-  y0 = ty * SC_TH;
-  x0 = tx * SC_TW;
-}
-
-// workgroup barrier that orders LDS traffic only: global loads / LDS-DMA stay in flight across it
-__device__ __forceinline__ void lds_barrier() {
-  // Raw barrier that orders LDS traffic only.  A fence (or __syncthreads) would also drain vmcnt: an in-flight
-  // LDS-DMA is a pending LDS write on the VM counter.  The "memory" clobber keeps the compiler from moving
-  // memory accesses across it; DMA completion is handled by the counted vmcnt waits of the issuing waves.
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-// fp32 pair -> fp16 hi pair + fp16 lo pair with x == hi + lo to 21 bits: hi = rtz(x), lo = rtz(x - hi) (the residual is
-// exact in fp32; v_cvt_pkrtz converts two values per instruction, the residual is one v_fma_mix / v_sub per value)
-__device__ __forceinline__ void split_hi_lo(const f32x2& x, f16x2& hi, f16x2& lo) {
-  typedef __fp16 h2 __attribute__((ext_vector_type(2)));
-  const h2 h = __builtin_amdgcn_cvt_pkrtz(x[0], x[1]);
-  const h2 l = __builtin_amdgcn_cvt_pkrtz(x[0] - (float)h[0], x[1] - (float)h[1]);
-  hi = __builtin_bit_cast(f16x2, h);
-  lo = __builtin_bit_cast(f16x2, l);
-}
+// dww: [C/64][KS*KS][64] fp32 (sepconvp_pack_dw); pww: sepconvp_pack_pw; bias never null (the launcher substitutes zeros)
+typedef SepParams<half_t, float> SeppParams;
 
 // MT = 16-cout MFMA row tiles per mma wave: Cout = 4 * 16 * MT (128 or 256).
 //
@@ -128,7 +70,7 @@ __device__ __forceinline__ void split_hi_lo(const f32x2& x, f16x2& hi, f16x2& lo
 // order instead: the depthwise wave consumes the taps of step g (requested a step earlier) BEFORE it issues the DMA
 // batch of step g+2, so the wait it gets covers only loads that are a whole step old; the mma waves issue no DMA.
 template <int KS, int MT, bool HEAD, int ACT, bool WS>
-__global__ void __launch_bounds__(64 * (SC_NDW + SC_NMW), 1) sepconvp_kernel(const SepParams p) {
+__global__ void __launch_bounds__(64 * (SC_NDW + SC_NMW), 1) sepconvp_kernel(const SeppParams p) {
   constexpr int NDW = SC_NDW, NMW = SC_NMW;
   constexpr int KK = KS * KS, PAD = KS / 2;
   constexpr int SC_NPIX = sc_npix(KS), SC_NST = SC_NPIX / 8, SC_HALO_BYTES = sc_halo_bytes(KS);
@@ -176,7 +118,7 @@ __global__ void __launch_bounds__(64 * (SC_NDW + SC_NMW), 1) sepconvp_kernel(con
         for (int k = 0; k < NDMA; ++k) sptr[k] = p.zero;
       } else if (ch == 0) {
         int n, y0, x0;
-        tile_coords(p, tile_of(tile_it), n, y0, x0);
+        tile_coords(p.tiles_x, p.tiles_y, tile_of(tile_it), n, y0, x0);
         const half_t* src = p.in + (size_t)n * p.H * p.W * p.in_ld + (lane & 7) * 8;
 #pragma unroll
         for (int k = 0; k < NDMA; ++k) {
@@ -317,16 +259,8 @@ __global__ void __launch_bounds__(64 * (SC_NDW + SC_NMW), 1) sepconvp_kernel(con
     // step counters: c1 = (g-1) % NC with tile t1
     int c1 = NC - 1, t1 = -1;
     for (int g = 0; g <= LAST; ++g) {
-      if (HEAD && g >= 2 && c1 == 0 && fh < p.hc) {
-        // finish the head of tile t1 - 1 (its last chunk was multiplied in the previous step)
-        int n, y0, x0;
-        tile_coords(p, tile_of(t1 - 1), n, y0, x0);
-        const int oy = y0 + (fpx >> 4), ox = x0 + (fpx & 15);
-        float v = fhb;
-#pragma unroll
-        for (int wv = 0; wv < NMW; ++wv) v += red[(wv * 128 + fpx) * 2 + fh];
-        if (oy < p.H && ox < p.W) p.hout[((size_t)n * p.hc + fh) * p.plane + (size_t)oy * p.W + ox] = v;
-      }
+      // finish the head of tile t1 - 1 (its last chunk was multiplied in the previous step)
+      if (HEAD && g >= 2 && c1 == 0 && fh < p.hc) head_store<NMW>(p, red, tile_of(t1 - 1), fh, fpx, fpx >> 4, fpx & 15, fhb);
       const bool do_mma = g >= 1 && g - 1 < S;
       const bool first = do_mma && c1 == 0;      // first chunk of a tile: the accumulators start from the bias
       if (first) {
@@ -382,7 +316,7 @@ __global__ void __launch_bounds__(64 * (SC_NDW + SC_NMW), 1) sepconvp_kernel(con
       __builtin_amdgcn_sched_barrier(0);
       if (do_mma && c1 == NC - 1) {
         int n, y0, x0;
-        tile_coords(p, tile_of(t1), n, y0, x0);
+        tile_coords(p.tiles_x, p.tiles_y, tile_of(t1), n, y0, x0);
         const int ox = x0 + n16;
         if (!HEAD) {
 #pragma unroll
@@ -411,22 +345,7 @@ __global__ void __launch_bounds__(64 * (SC_NDW + SC_NMW), 1) sepconvp_kernel(con
 #pragma unroll 1
           for (int h = 0; h < p.hc; ++h) {
             float sum[8];
-#pragma unroll
-            for (int nt = 0; nt < 8; ++nt) sum[nt] = 0.f;
-#pragma unroll
-            for (int blk = 0; blk < MT / 2; ++blk) {
-              const float* hp = hwl + h * COUT + wm * 16 * MT + blk * 32 + g16 * 8;
-              float hv[8];
-#pragma unroll
-              for (int e = 0; e < 8; ++e) hv[e] = hp[e];
-#pragma unroll
-              for (int nt = 0; nt < 8; ++nt)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                  sum[nt] = fmaf(acc[2 * blk][nt][e], hv[e], sum[nt]);
-                  sum[nt] = fmaf(acc[2 * blk + 1][nt][e], hv[4 + e], sum[nt]);
-                }
-            }
+            head_plane_sums<MT>(acc, hwl + h * COUT + wm * 16 * MT + g16 * 8, sum);
 #pragma unroll
             for (int nt = 0; nt < 8; ++nt) {
               float v = sum[nt];
@@ -478,31 +397,21 @@ __global__ void __launch_bounds__(256) sepconvp_pack_pw_kernel(const float* __re
   }
 }
 
-template <int KS, int MT, bool HEAD, int ACT, bool WS>
-int launch_act(const SepParams& p, size_t lds_bytes, int grid, hipStream_t s) {
-  if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(&sepconvp_kernel<KS, MT, HEAD, ACT, WS>), 160 * 1024)) return rc;
-  hipLaunchKernelGGL((sepconvp_kernel<KS, MT, HEAD, ACT, WS>), dim3(grid), dim3(64 * (SC_NDW + SC_NMW)), lds_bytes, s, p);
-  EMP_LAUNCH_CHECK();
-  return EMP_OK;
-}
-
 template <int KS, int MT, bool HEAD, bool WS = false>
-int launch_one(const SepParams& p, size_t lds_bytes, int grid, hipStream_t s) {
-  if (p.act == 1) return launch_act<KS, MT, HEAD, 1, WS>(p, lds_bytes, grid, s);
-  if (p.act == 2) return launch_act<KS, MT, HEAD, 2, WS>(p, lds_bytes, grid, s);
-  return launch_act<KS, MT, HEAD, 0, WS>(p, lds_bytes, grid, s);
+int launch_sepp(const SeppParams& p, size_t lds_bytes, hipStream_t s) {
+  return launch_by_act([](auto a) { return &sepconvp_kernel<KS, MT, HEAD, decltype(a)::value, WS>; }, p, 64 * (SC_NDW + SC_NMW), lds_bytes, s);
 }
 
 }  // namespace
 
 static size_t sepconvp_lds_bytes(int Cout, int head_c, int ks = 5) {
-  return 3 * sc_halo_bytes(ks) + 2 * SC_BT_BYTES + (head_c ? (size_t)2 * Cout * 4 + (size_t)SC_NMW * 128 * 2 * 4 : 0);
+  return sep_lds_bytes(ks, SC_BT_BYTES, Cout, head_c, SC_NMW);
 }
 
 bool sepconvp_supported(int C, int Cout, int head_c) {
   // C / 64 + 2 increments of 128 B must stay inside the 2 KiB zero page
-  return C % 64 == 0 && C >= 128 && C <= 512 && (Cout == 128 || Cout == 256) && head_c >= 0 && head_c <= 2 &&
-         sepconvp_lds_bytes(Cout, head_c) <= 160 * 1024;
+  return C % 64 == 0 && C >= 128 && C <= 512 && sep_couts_supported(Cout, head_c) &&
+         sepconvp_lds_bytes(Cout, head_c) <= SC_MAX_LDS;
 }
 
 bool sepconvp_wsplit_supported(int Cout) { return Cout == 128; }      // MT = 2: the lo fragments fit the registers
@@ -539,36 +448,21 @@ int launch_sepconvp(const half_t* in, int N, int H, int W, int C, int in_ld, con
   EMP_REQUIRE(ks == 5 || (ks == 3 && head_c == 0), "sepconv: depthwise kernel %d unsupported", ks);
   EMP_REQUIRE(!wsplit || sepconvp_wsplit_supported(Cout), "sepconvp: hi + lo pointwise weights need Cout == 128");
   EMP_REQUIRE(sepconvp_supported(C, Cout, head_c), "sepconvp: unsupported shape C=%d Cout=%d head=%d", C, Cout, head_c);
-  EMP_REQUIRE(act >= 0 && act <= 2, "sepconvp: bad activation %d", act);
-  EMP_REQUIRE((head_c > 0) != (out != nullptr), "sepconvp: exactly one of the feature / head outputs");
-  EMP_REQUIRE(in_ld % 8 == 0 && (out == nullptr || out_ld % 8 == 0), "sepconvp: 16-byte row alignment");
-  SepParams p{};
-  p.in = in; p.N = N; p.H = H; p.W = W; p.C = C; p.in_ld = in_ld;
-  p.dww = dww; p.pww = pww;
+  SeppParams p{};
+  if (int rc = sep_fill_params(p, "sepconvp", in, N, H, W, C, in_ld, act, out, out_ld, in_ld % 8 == 0 && (out == nullptr || out_ld % 8 == 0),
+                               head_w, head_b, head_c, hout, plane))
+    return rc;
+  p.dww = dww; p.pww = pww; p.zero = zero;
   p.bias = bias ? bias : reinterpret_cast<const float*>(zero);      // Cout * 4 <= 1 KiB of the 2 KiB zero page
-  p.out = out; p.out_ld = out_ld; p.act = act; p.zero = zero;
-  p.tiles_x = cdiv(W, SC_TW); p.tiles_y = cdiv(H, SC_TH);
-  const int64_t tiles = (int64_t)N * p.tiles_x * p.tiles_y;
-  EMP_REQUIRE(tiles < (1ll << 30), "sepconvp: too many tiles");
-  p.tiles = (int)tiles;
-  p.hw = head_w; p.hb = head_b; p.hc = head_c; p.hout = hout; p.plane = plane;
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    EMP_CHECK_HIP(hipGetDevice(&dev));
-    EMP_CHECK_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-    n_cu = n_cu >= 8 ? (n_cu / 8) * 8 : 8;
-  }
-  const int grid = n_cu;
   const size_t lds_bytes = sepconvp_lds_bytes(Cout, head_c, ks);
   if (ks == 3) {     // BiFPN nodes (depthwise 3x3 -> pointwise -> BN -> SiLU); no head mode
-    if (Cout == 256) return launch_one<3, 4, false>(p, lds_bytes, grid, s);
-    return wsplit ? launch_one<3, 2, false, true>(p, lds_bytes, grid, s) : launch_one<3, 2, false>(p, lds_bytes, grid, s);
+    if (Cout == 256) return launch_sepp<3, 4, false>(p, lds_bytes, s);
+    return wsplit ? launch_sepp<3, 2, false, true>(p, lds_bytes, s) : launch_sepp<3, 2, false>(p, lds_bytes, s);
   }
   if (Cout == 256)
-    return head_c ? launch_one<5, 4, true>(p, lds_bytes, grid, s) : launch_one<5, 4, false>(p, lds_bytes, grid, s);
-  if (wsplit) return head_c ? launch_one<5, 2, true, true>(p, lds_bytes, grid, s) : launch_one<5, 2, false, true>(p, lds_bytes, grid, s);
-  return head_c ? launch_one<5, 2, true>(p, lds_bytes, grid, s) : launch_one<5, 2, false>(p, lds_bytes, grid, s);
+    return head_c ? launch_sepp<5, 4, true>(p, lds_bytes, s) : launch_sepp<5, 4, false>(p, lds_bytes, s);
+  if (wsplit) return head_c ? launch_sepp<5, 2, true, true>(p, lds_bytes, s) : launch_sepp<5, 2, false, true>(p, lds_bytes, s);
+  return head_c ? launch_sepp<5, 2, true>(p, lds_bytes, s) : launch_sepp<5, 2, false>(p, lds_bytes, s);
 }
 
 }  // namespace emp

@@ -21,58 +21,18 @@
 // dwconv32 order), K ascending in steps of 32 from the bias: a batch of N equals N single calls bit for bit.
 // Not bit-identical to the unfused pair of launches (there the pointwise conv adds its bias at the end); both are the fp32
 // result to ~1e-6 relative (tests/test_gpu_sepconv_x3.py holds the kernel to an fp64 reference).
-#include "common.h"
+#include "sepconv_common.h"
 
 namespace emp {
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int SX_TH = 8, SX_TW = 16;                  // output tile (rows x cols) = 128 pixels
-constexpr int SX_IW = SX_TW + 4;
-constexpr int sx_npix(int ks) { return (SX_TH + ks - 1) * SX_IW; }
-constexpr int sx_halo_bytes(int ks) { return sx_npix(ks) * 128; }      // 32 fp32 channels per pixel
 constexpr int SX_BT_HALF = 128 * 64;                  // 128 pixels x 32 channels fp16
 constexpr int SX_BT_BYTES = 2 * SX_BT_HALF;           // hi tile, lo tile
-constexpr int SX_NDW = 4, SX_NMW = 4;
-constexpr int SX_CH = 32;                             // channels per chunk
+constexpr int SX_CH = 32;                             // channels per chunk: a pixel's chunk is 128 B of fp32
 
-struct SxParams {
-  const float* in;
-  int N, H, W, C, in_ld;
-  const float* dww;      // [C/32][KS*KS][32] fp32 (sepx3_pack_dw)
-  const half_t* pww;     // pointwise weights hi / lo in MFMA-fragment order (sepx3_pack_pw)
-  const float* bias;     // [Cout] (never null: the launcher substitutes zeros)
-  float* out;            // (N,H,W,out_ld) or nullptr (head mode)
-  int out_ld;
-  const float* zero;     // >= 2 KiB of zeros
-  int tiles_x, tiles_y;
-  int tiles;
-  const float* hw;       // head mode: [hc][Cout] fp32
-  const float* hb;       // [hc]
-  int hc;
-  float* hout;           // (N,hc) planes of `plane` floats
-  int64_t plane;
-};
-
-template <int ACT>
-__device__ __forceinline__ float sx_act(float x) {
-  if (ACT == 1) return fmaxf(x, 0.f);
-  if (ACT == 2) return x / (1.f + __expf(-x));
-  return x;
-}
-
-__device__ __forceinline__ void sx_tile_coords(const SxParams& p, int tile, int& n, int& y0, int& x0) {
-  const int tx = tile % p.tiles_x;
-  const int r = tile / p.tiles_x;
-  const int ty = r % p.tiles_y;
-  n = r / p.tiles_y;
-  y0 = ty * SX_TH;
-  x0 = tx * SX_TW;
-}
-
-__device__ __forceinline__ void sx_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// dww: [C/32][KS*KS][32] fp32 (sepx3_pack_dw); pww: hi / lo fragments (sepx3_pack_pw); bias never null (the launcher substitutes zeros)
+typedef SepParams<float, float> SxParams;
 
 // B tiles: 64-byte rows (32 halfs of one pixel), 16-byte chunk c of row r at chunk c ^ sx_swz(r): conflict-free ds_read_b128
 // fragments (lane -> row lane % 16, chunk lane / 16) -- conv16x3.hip's layout
@@ -80,10 +40,10 @@ __device__ __forceinline__ int sx_swz(int r) { return (-((r & 15) >> 2)) & 3; }
 
 // MT = 16-cout MFMA row tiles per mma wave: Cout = 4 * 16 * MT (128 or 256)
 template <int KS, int MT, bool HEAD, int ACT>
-__global__ void __launch_bounds__(64 * (SX_NDW + SX_NMW), 1) sepconv_x3_kernel(const SxParams p) {
-  constexpr int NDW = SX_NDW, NMW = SX_NMW;
+__global__ void __launch_bounds__(64 * (SC_NDW + SC_NMW), 1) sepconv_x3_kernel(const SxParams p) {
+  constexpr int NDW = SC_NDW, NMW = SC_NMW;
   constexpr int KK = KS * KS, PAD = KS / 2;
-  constexpr int NPIX = sx_npix(KS), NST = NPIX / 8, HALO_BYTES = sx_halo_bytes(KS);
+  constexpr int NPIX = sc_npix(KS), NST = NPIX / 8, HALO_BYTES = sc_halo_bytes(KS);
   constexpr int NT = 64 * (NDW + NMW);
   constexpr int R = 2;                      // output rows per depthwise thread (16 channel pairs x 4 column groups x 4 row groups)
   constexpr int COUT = NMW * 16 * MT;
@@ -111,7 +71,7 @@ __global__ void __launch_bounds__(64 * (SX_NDW + SX_NMW), 1) sepconv_x3_kernel(c
     // ------------------------------------------------------------------ dw role
     // thread = channel pair cp x columns 4cg..4cg+3 x rows R*rg..R*rg+R-1 of the 8 x 16 tile
     const int cp = lane & 15, combo = wave * 4 + (lane >> 4), cg = combo & 3, rg = combo >> 2;
-    const int hoff = ((R * rg) * SX_IW + 4 * cg) * 128 + cp * 8;
+    const int hoff = ((R * rg) * SC_IW + 4 * cg) * 128 + cp * 8;
     const float* sptr[NDMA];
 #pragma unroll
     for (int k = 0; k < NDMA; ++k) sptr[k] = p.zero;
@@ -121,13 +81,13 @@ __global__ void __launch_bounds__(64 * (SX_NDW + SX_NMW), 1) sepconv_x3_kernel(c
         for (int k = 0; k < NDMA; ++k) sptr[k] = p.zero;
       } else if (ch == 0) {
         int n, y0, x0;
-        sx_tile_coords(p, tile_of(tile_it), n, y0, x0);
+        tile_coords(p.tiles_x, p.tiles_y, tile_of(tile_it), n, y0, x0);
         const float* src = p.in + (size_t)n * p.H * p.W * p.in_ld + (lane & 7) * 4;
 #pragma unroll
         for (int k = 0; k < NDMA; ++k) {
           const int i = min(wave + NDW * k, NST - 1);
           const int q = i * 8 + (lane >> 3);
-          const int py = q / SX_IW, px = q - py * SX_IW;
+          const int py = q / SC_IW, px = q - py * SC_IW;
           const int iy = y0 + py - PAD, ix = x0 + px - PAD;
           const bool ok = (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
           sptr[k] = ok ? src + ((size_t)iy * p.W + ix) * p.in_ld : p.zero;
@@ -180,7 +140,7 @@ __global__ void __launch_bounds__(64 * (SX_NDW + SX_NMW), 1) sepconv_x3_kernel(c
           for (int c = 0; c < 4 + KS - 1; ++c) x[c] = nxt[c];
           if (r + 1 < R + KS - 1) {
 #pragma unroll
-            for (int c = 0; c < 4 + KS - 1; ++c) nxt[c] = *reinterpret_cast<const f32x2*>(hb + ((r + 1) * SX_IW + c) * 128);
+            for (int c = 0; c < 4 + KS - 1; ++c) nxt[c] = *reinterpret_cast<const f32x2*>(hb + ((r + 1) * SC_IW + c) * 128);
           }
 #pragma unroll
           for (int ky = 0; ky < KS; ++ky) {
@@ -198,7 +158,7 @@ __global__ void __launch_bounds__(64 * (SX_NDW + SX_NMW), 1) sepconv_x3_kernel(c
         for (int y = 0; y < R; ++y)
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            const int px = (R * rg + y) * SX_TW + 4 * cg + j;
+            const int px = (R * rg + y) * SC_TW + 4 * cg + j;
             f16x2 h, l;
             h[0] = (half_t)acc[y][j][0]; h[1] = (half_t)acc[y][j][1];
             l[0] = (half_t)(acc[y][j][0] - (float)h[0]); l[1] = (half_t)(acc[y][j][1] - (float)h[1]);
@@ -210,7 +170,7 @@ __global__ void __launch_bounds__(64 * (SX_NDW + SX_NMW), 1) sepconv_x3_kernel(c
       if (++c2 == NC) { c2 = 0; ++t2; }
       ring = ring == 2 ? 0 : ring + 1;
       ring2 = ring2 == 2 ? 0 : ring2 + 1;
-      sx_barrier();
+      lds_barrier();
     }
 #pragma unroll
     for (int t = 0; t < KK; ++t) asm volatile("" :: "v"(wn[t]));
@@ -239,15 +199,7 @@ __global__ void __launch_bounds__(64 * (SX_NDW + SX_NMW), 1) sepconv_x3_kernel(c
     __syncthreads();
     int c1 = NC - 1, t1 = -1;
     for (int g = 0; g <= LAST; ++g) {
-      if (HEAD && g >= 2 && c1 == 0 && fh < p.hc) {
-        int n, y0, x0;
-        sx_tile_coords(p, tile_of(t1 - 1), n, y0, x0);
-        const int oy = y0 + (fpx >> 4), ox = x0 + (fpx & 15);
-        float v = fhb;
-#pragma unroll
-        for (int wv = 0; wv < NMW; ++wv) v += red[(wv * 128 + fpx) * 2 + fh];
-        if (oy < p.H && ox < p.W) p.hout[((size_t)n * p.hc + fh) * p.plane + (size_t)oy * p.W + ox] = v;
-      }
+      if (HEAD && g >= 2 && c1 == 0 && fh < p.hc) head_store<NMW>(p, red, tile_of(t1 - 1), fh, fpx, fpx >> 4, fpx & 15, fhb);
       const bool do_mma = g >= 1 && g - 1 < S;
       const bool first = do_mma && c1 == 0;
       if (first) {
@@ -284,7 +236,7 @@ __global__ void __launch_bounds__(64 * (SX_NDW + SX_NMW), 1) sepconv_x3_kernel(c
       __builtin_amdgcn_sched_barrier(0);
       if (do_mma && c1 == NC - 1) {
         int n, y0, x0;
-        sx_tile_coords(p, tile_of(t1), n, y0, x0);
+        tile_coords(p.tiles_x, p.tiles_y, tile_of(t1), n, y0, x0);
         const int ox = x0 + n16;
         if (!HEAD) {
 #pragma unroll
@@ -295,10 +247,10 @@ __global__ void __launch_bounds__(64 * (SX_NDW + SX_NMW), 1) sepconv_x3_kernel(c
               const int oy = y0 + nt;
               if (oy < p.H && ox < p.W) {
                 float* op = p.out + (((size_t)n * p.H + oy) * p.W + ox) * p.out_ld + cb;
-                *reinterpret_cast<float4*>(op) = make_float4(sx_act<ACT>(acc[2 * blk][nt][0]), sx_act<ACT>(acc[2 * blk][nt][1]),
-                                                             sx_act<ACT>(acc[2 * blk][nt][2]), sx_act<ACT>(acc[2 * blk][nt][3]));
-                *reinterpret_cast<float4*>(op + 4) = make_float4(sx_act<ACT>(acc[2 * blk + 1][nt][0]), sx_act<ACT>(acc[2 * blk + 1][nt][1]),
-                                                                 sx_act<ACT>(acc[2 * blk + 1][nt][2]), sx_act<ACT>(acc[2 * blk + 1][nt][3]));
+                *reinterpret_cast<float4*>(op) = make_float4(sc_act<ACT>(acc[2 * blk][nt][0]), sc_act<ACT>(acc[2 * blk][nt][1]),
+                                                             sc_act<ACT>(acc[2 * blk][nt][2]), sc_act<ACT>(acc[2 * blk][nt][3]));
+                *reinterpret_cast<float4*>(op + 4) = make_float4(sc_act<ACT>(acc[2 * blk + 1][nt][0]), sc_act<ACT>(acc[2 * blk + 1][nt][1]),
+                                                                 sc_act<ACT>(acc[2 * blk + 1][nt][2]), sc_act<ACT>(acc[2 * blk + 1][nt][3]));
               }
             }
           }
@@ -308,26 +260,11 @@ __global__ void __launch_bounds__(64 * (SX_NDW + SX_NMW), 1) sepconv_x3_kernel(c
 #pragma unroll
             for (int nt = 0; nt < 8; ++nt)
 #pragma unroll
-              for (int e = 0; e < 4; ++e) acc[t][nt][e] = sx_act<ACT>(acc[t][nt][e]);
+              for (int e = 0; e < 4; ++e) acc[t][nt][e] = sc_act<ACT>(acc[t][nt][e]);
 #pragma unroll 1
           for (int h = 0; h < p.hc; ++h) {
             float sum[8];
-#pragma unroll
-            for (int nt = 0; nt < 8; ++nt) sum[nt] = 0.f;
-#pragma unroll
-            for (int blk = 0; blk < MT / 2; ++blk) {
-              const float* hp = hwl + h * COUT + wm * 16 * MT + blk * 32 + g16 * 8;
-              float hv[8];
-#pragma unroll
-              for (int e = 0; e < 8; ++e) hv[e] = hp[e];
-#pragma unroll
-              for (int nt = 0; nt < 8; ++nt)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                  sum[nt] = fmaf(acc[2 * blk][nt][e], hv[e], sum[nt]);
-                  sum[nt] = fmaf(acc[2 * blk + 1][nt][e], hv[4 + e], sum[nt]);
-                }
-            }
+            head_plane_sums<MT>(acc, hwl + h * COUT + wm * 16 * MT + g16 * 8, sum);
 #pragma unroll
             for (int nt = 0; nt < 8; ++nt) {
               float v = sum[nt];
@@ -340,7 +277,7 @@ __global__ void __launch_bounds__(64 * (SX_NDW + SX_NMW), 1) sepconv_x3_kernel(c
       }
       if (++c1 == NC) { c1 = 0; }
       if (c1 == 0) ++t1;
-      sx_barrier();
+      lds_barrier();
     }
   }
 }
@@ -362,8 +299,8 @@ __global__ void __launch_bounds__(256) sepx3_pack_pw_kernel(const float* __restr
     const int lane = r & 63; r >>= 6;
     const int part = r & 1; r >>= 1;
     const int t = r % MT; r /= MT;
-    const int wm = r % SX_NMW;
-    const int ch = r / SX_NMW;
+    const int wm = r % SC_NMW;
+    const int ch = r / SC_NMW;
     const int n16 = lane & 15, g16 = lane >> 4, tp = t & 1;
     const int co = wm * 16 * MT + (t >> 1) * 32 + ((n16 >> 2) << 3) + (tp << 2) + (n16 & 3);
     const float* src = w + (size_t)co * pw_ld + ch * SX_CH + g16 * 8;
@@ -378,27 +315,19 @@ __global__ void __launch_bounds__(256) sepx3_pack_pw_kernel(const float* __restr
 }
 
 template <int KS, int MT, bool HEAD>
-int sx_launch(const SxParams& p, int act, size_t lds_bytes, int grid, hipStream_t s) {
-  auto go = [&](auto kern) -> int {
-    if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024)) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * (SX_NDW + SX_NMW)), lds_bytes, s, p);
-    EMP_LAUNCH_CHECK();
-    return EMP_OK;
-  };
-  if (act == 1) return go(&sepconv_x3_kernel<KS, MT, HEAD, 1>);
-  if (act == 2) return go(&sepconv_x3_kernel<KS, MT, HEAD, 2>);
-  return go(&sepconv_x3_kernel<KS, MT, HEAD, 0>);
+int launch_sx(const SxParams& p, size_t lds_bytes, hipStream_t s) {
+  return launch_by_act([](auto a) { return &sepconv_x3_kernel<KS, MT, HEAD, decltype(a)::value>; }, p, 64 * (SC_NDW + SC_NMW), lds_bytes, s);
 }
 
 }  // namespace
 
 static size_t sepx3_lds_bytes(int Cout, int head_c, int ks) {
-  return 3 * sx_halo_bytes(ks) + 2 * SX_BT_BYTES + (head_c ? (size_t)2 * Cout * 4 + (size_t)SX_NMW * 128 * 2 * 4 : 0);
+  return sep_lds_bytes(ks, SX_BT_BYTES, Cout, head_c, SC_NMW);
 }
 
 bool sepconv_x3_supported(int C, int Cout, int head_c, int ks) {
   // C / 32 + 2 increments of 128 B must stay inside the 2 KiB zero page
-  return C % SX_CH == 0 && C >= 64 && C <= 448 && (Cout == 128 || Cout == 256) && head_c >= 0 && head_c <= 2 && (ks == 5 || (ks == 3 && head_c == 0));
+  return C % SX_CH == 0 && C >= 64 && C <= 448 && sep_couts_supported(Cout, head_c) && (ks == 5 || (ks == 3 && head_c == 0));
 }
 
 int64_t sepx3_pw_halfs(int C, int Cout) { return (int64_t)2 * C * Cout; }
@@ -424,30 +353,18 @@ int launch_sepconv_x3(const float* in, int N, int H, int W, int C, int in_ld, co
                       int Cout, int act, float* out, int out_ld, const float* head_w, const float* head_b, int head_c, float* hout,
                       int64_t plane, hipStream_t s, int ks) {
   EMP_REQUIRE(sepconv_x3_supported(C, Cout, head_c, ks), "sepconv_x3: unsupported shape C=%d Cout=%d head=%d k=%d", C, Cout, head_c, ks);
-  EMP_REQUIRE(act >= 0 && act <= 2, "sepconv_x3: bad activation %d", act);
-  EMP_REQUIRE((head_c > 0) != (out != nullptr), "sepconv_x3: exactly one of the feature / head outputs");
-  EMP_REQUIRE(in && dww && pww && in_ld % 4 == 0 && in_ld >= C && ((uintptr_t)in % 16) == 0 && (out == nullptr || (out_ld % 4 == 0 && ((uintptr_t)out % 16) == 0)) &&
-                  (!bias || ((uintptr_t)bias % 16) == 0), "sepconv_x3: 16-byte row alignment");
+  const bool aligned = in && dww && pww && in_ld % 4 == 0 && in_ld >= C && ((uintptr_t)in % 16) == 0 &&
+                       (out == nullptr || (out_ld % 4 == 0 && ((uintptr_t)out % 16) == 0)) && (!bias || ((uintptr_t)bias % 16) == 0);
   SxParams p{};
+  if (int rc = sep_fill_params(p, "sepconv_x3", in, N, H, W, C, in_ld, act, out, out_ld, aligned, head_w, head_b, head_c, hout, plane)) return rc;
   p.zero = reinterpret_cast<const float*>(zero_page());
   EMP_REQUIRE(p.zero != nullptr, "sepconv_x3: no zero page");
-  p.in = in; p.N = N; p.H = H; p.W = W; p.C = C; p.in_ld = in_ld;
   p.dww = dww; p.pww = pww;
   p.bias = bias ? bias : p.zero;      // Cout * 4 <= 1 KiB of the 2 KiB zero page
-  p.out = out; p.out_ld = out_ld;
-  p.tiles_x = cdiv(W, SX_TW); p.tiles_y = cdiv(H, SX_TH);
-  const int64_t tiles = (int64_t)N * p.tiles_x * p.tiles_y;
-  EMP_REQUIRE(tiles < (1ll << 30), "sepconv_x3: too many tiles");
-  p.tiles = (int)tiles;
-  p.hw = head_w; p.hb = head_b; p.hc = head_c; p.hout = hout; p.plane = plane;
-  int dev = 0, n_cu = 0;
-  EMP_CHECK_HIP(hipGetDevice(&dev));
-  EMP_CHECK_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-  const int grid = n_cu >= 8 ? (n_cu / 8) * 8 : 8;
   const size_t lds_bytes = sepx3_lds_bytes(Cout, head_c, ks);
-  if (ks == 3) return Cout == 256 ? sx_launch<3, 4, false>(p, act, lds_bytes, grid, s) : sx_launch<3, 2, false>(p, act, lds_bytes, grid, s);
-  if (Cout == 256) return head_c ? sx_launch<5, 4, true>(p, act, lds_bytes, grid, s) : sx_launch<5, 4, false>(p, act, lds_bytes, grid, s);
-  return head_c ? sx_launch<5, 2, true>(p, act, lds_bytes, grid, s) : sx_launch<5, 2, false>(p, act, lds_bytes, grid, s);
+  if (ks == 3) return Cout == 256 ? launch_sx<3, 4, false>(p, lds_bytes, s) : launch_sx<3, 2, false>(p, lds_bytes, s);
+  if (Cout == 256) return head_c ? launch_sx<5, 4, true>(p, lds_bytes, s) : launch_sx<5, 4, false>(p, lds_bytes, s);
+  return head_c ? launch_sx<5, 2, true>(p, lds_bytes, s) : launch_sx<5, 2, false>(p, lds_bytes, s);
 }
 
 }  // namespace emp
