@@ -20,29 +20,18 @@
 // Values must fit fp16's range (|x| <= 65504), as every map of the fp16 engine does.
 #include <type_traits>
 
-#include "common.h"
+#include "igemm_common.h"
 
 namespace emp {
 namespace {
 
 constexpr int X_BK = 32, X_LD = 32;      // LDS rows are the step's 32 halfs = 64 B, four 16-byte chunks
 
-template <int ACT>
-__device__ __forceinline__ float x_act(float x) {
-  if (ACT == 1) return fmaxf(x, 0.f);
-  if (ACT == 2) return x / (1.f + __expf(-x));
-  return x;
-}
-
 // 16-byte chunk c of tile row r lives at chunk position c ^ swz(r): with the fragment addressing below (lane -> row
 // lane % 16, chunk lane / 16) every one of gfx950's four non-contiguous ds_read_b128 lane groups touches 64 distinct
 // banks -- the image of conv_igemm256.hip.  (Round 5's first layout -- rows padded to 80 B -- measured 50 % of its LDS
 // cycles as bank conflicts: SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE, tools/conv16x3_pmc.sh.)
 __device__ __forceinline__ int swz(int r) { return (-((r & 15) >> 2)) & 3; }
-
-// workgroup barrier that orders LDS traffic only: a __syncthreads() would also drain vmcnt, i.e. wait for the global loads
-// that were issued precisely to stay in flight across it (the prefetch of the next steps)
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // 8 fp32 values -> 8 hi halfs + 8 lo halfs, one 16-byte LDS store each
 __device__ __forceinline__ void split_store(const float4 (&r)[2], half_t* hi, half_t* lo) {
@@ -100,7 +89,7 @@ __device__ __forceinline__ void pair_store4(const float4& r, half_t* hi, half_t*
 // into an hl32 row (the plane region's format, conv16x3p.hip: the consumer's operand split done here, once)
 template <int ACT>
 __device__ __forceinline__ void store4(const Conv32& p, int m, int co, const float4& t) {
-  const float v[4] = {x_act<ACT>(t.x), x_act<ACT>(t.y), x_act<ACT>(t.z), x_act<ACT>(t.w)};
+  const float v[4] = {conv_act<ACT>(t.x), conv_act<ACT>(t.y), conv_act<ACT>(t.z), conv_act<ACT>(t.w)};
   if (p.out2 && co >= p.split2) {      // second destination (two convolutions of one map as one launch: the decoders' low-level projections)
     *reinterpret_cast<float4*>(p.out2 + (size_t)m * p.out2_ld + (co - p.split2)) = make_float4(v[0], v[1], v[2], v[3]);
     return;
@@ -314,7 +303,7 @@ __global__ void __launch_bounds__(256, DB ? 2 : 3) conv16x3_kernel(const Conv32 
         const int col = n0 + wc + i * 16 + (lane >> 4) * 4;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float v = col + e < p.Cout ? x_act<ACT>(acc[i][j][e] + bi[i][e]) : 0.f;
+          const float v = col + e < p.Cout ? conv_act<ACT>(acc[i][j][e] + bi[i][e]) : 0.f;
           const int cw = col + e < p.Cout ? col + e : 0;
 #pragma unroll
           for (int h = 0; h < 4; ++h)
@@ -401,7 +390,7 @@ __global__ void __launch_bounds__(256, DB ? 2 : 3) conv16x3_kernel(const Conv32 
         float t = acc[i][j][e] + (p.bias ? p.bias[co] : 0.f);
         if (p.bias_n) t += p.bias_n[(size_t)n * p.Cout + co];
         if (p.res) t += p.res[(size_t)m * p.res_ld + co];
-        t = x_act<ACT>(t);
+        t = conv_act<ACT>(t);
         if (p.ps_cout == 0) {
           p.out[(size_t)m * p.out_ld + co] = t;
         } else {      // ConvTranspose2d(k=2, s=2) as four sub-pixel 1x1 convs: (n,y,x,q*C+c) -> (n, 2y+dy, 2x+dx, c)

@@ -32,7 +32,7 @@
 // groups of 128 channels (x3p_kgroup below): another summation order of the same terms.
 #include <type_traits>
 
-#include "common.h"
+#include "igemm_common.h"
 
 namespace emp {
 namespace {
@@ -59,21 +59,8 @@ struct X3P {
                // raw partial sums to out + s * M * Cout floats (>= 4 steps in every split)
 };
 
-__device__ __forceinline__ int perm32b(int x) {
-  const int t = x >> 4, i = x & 15;
-  return ((i >> 2) << 3) + (t << 2) + (i & 3);
-}
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-template <int ACT>
-__device__ __forceinline__ float act_p(float x) {
-  if (ACT == 1) return fmaxf(x, 0.f);
-  if (ACT == 2) return x / (1.f + __expf(-x));
-  return x;
-}
-
 // lane (fq, fr) owns couts co0 + P * 32 + fq * 8 + [0, 8) of pixel mrow0 + q * 16 + fr (the weight rows are permuted in the
-// image, perm32b): 32 contiguous bytes of an fp32 row, or 16 B of hi and 16 B of lo inside one 32-channel block of an hl32 row
+// image, perm32): 32 contiguous bytes of an fp32 row, or 16 B of hi and 16 B of lo inside one 32-channel block of an hl32 row
 template <int ACT, int OUTF, int RESF>      // RESF: 0 no residual, 1 fp32 rows, 2 hl32 rows
 __device__ __forceinline__ void x3p_epilogue(const X3P& p, void* out_base, f32x4 (&acc)[4][8], int mrow0, int co0, int fr, int fq, int HoWo) {
   // Two passes (couts P * 32 + fq * 8 + [0, 8) each).  The residual of FOUR pixel fragments at a time is requested up front --
@@ -143,7 +130,7 @@ __device__ __forceinline__ void x3p_epilogue(const X3P& p, void* out_base, f32x4
           v[4] += r1[u].x; v[5] += r1[u].y; v[6] += r1[u].z; v[7] += r1[u].w;
         }
 #pragma unroll
-        for (int r = 0; r < 8; ++r) v[r] = act_p<ACT>(v[r]);
+        for (int r = 0; r < 8; ++r) v[r] = conv_act<ACT>(v[r]);
         if (m >= p.M) continue;
         if (OUTF) {
           half_t* op = reinterpret_cast<half_t*>(obase) + (size_t)m * (2 * old_) + (oc >> 5) * 64 + (oc & 31);
@@ -264,12 +251,8 @@ __global__ void __launch_bounds__(512, 1) conv16x3p_kernel(const X3P p) {
       const int dy = x_ky * p.dil, dx = x_kx * p.dil;
       const int c0 = x_grp * KG * (2 * KS) + pchunk * 8;      // halfs into the hl32 row: the group's first 32-channel block
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int iy = a_iy0[i] + dy, ix = a_ix0[i] + dx;
-        const bool ok = (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
-        a_cur[i] = ok ? p.in + ((size_t)(a_pix[i] + iy * p.W + ix) * row_halfs + c0) : p.zero;
-        a_inc[i] = ok ? 2 * KS : 0;
-      }
+      for (int i = 0; i < 4; ++i)
+        tap_src_pix(p.in, a_pix[i], a_iy0[i], a_ix0[i], dy, dx, p.H, p.W, row_halfs, c0, p.zero, 2 * KS, a_cur[i], a_inc[i]);
     }
     if (++x_cb == KG) {
       x_cb = 0;
@@ -281,8 +264,7 @@ __global__ void __launch_bounds__(512, 1) conv16x3p_kernel(const X3P p) {
   };
   auto dma_x = [&](int i) {
     char* dst = lds + X_BASE + x_slot * XSLOT + (wave + 8 * i) * 1024;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)a_cur[i],
-                                     (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+    lds_dma16(a_cur[i], dst);
     a_cur[i] += a_inc[i];
   };
   auto x_next = [&]() { x_slot = (x_slot == 2) ? 0 : x_slot + 1; };
@@ -454,7 +436,7 @@ __global__ void __launch_bounds__(512, 1) conv16x3p_kernel(const X3P p) {
 }
 
 // [cout tile of 256][K step][part: 0 = lo, 1 = hi][piece of 16 rows][lane][8 halfs]: the bytes lane l of the wave that stages piece
-// pc writes to LDS, in LDS order -- conv_igemm256.hip's pack256_kernel with the split applied (rows permuted by perm32b, chunks
+// pc writes to LDS, in LDS order -- conv_igemm256.hip's pack256_kernel with the split applied (rows permuted by perm32, chunks
 // swizzled).  w: [Cout][K] fp32, K = KH * KW * Cin walked tap-major.
 __global__ void __launch_bounds__(256) x3p_pack_kernel(const float* __restrict__ w, half_t* __restrict__ out, int Cout, int K, int KT, int Cin,
                                                        int KG) {
@@ -465,8 +447,8 @@ __global__ void __launch_bounds__(256) x3p_pack_kernel(const float* __restrict__
     const int64_t tt = i >> 11;
     const int t = (int)(tt % KTOT), ntile = (int)(tt / KTOT);
     const int row = pc * 16 + (l >> 2);
-    const int co = ntile * 256 + (row & ~31) + perm32b(row & 31);
-    const int chunk = (l & 3) ^ ((-(l >> 4)) & 3);
+    const int co = ntile * 256 + (row & ~31) + perm32(row & 31);
+    const int chunk = stage_chunk64(l);
     // K step t of the walk [group][tap][step] -> its place in the row (tap-major there): tap * Cin + (g * KG + cb) * 32
     const int per = KT * KG, g = t / per, idx = t - g * per, tap = idx / KG, cb = idx - tap * KG;
     const float* src = w + (size_t)co * K + tap * Cin + (g * KG + cb) * KS + chunk * 8;
@@ -581,7 +563,7 @@ __global__ void __launch_bounds__(256) x3p_finish_kernel(const X3P p, const floa
       }
     }
 #pragma unroll
-    for (int r = 0; r < 8; ++r) v[r] = act_p<ACT>(v[r]);
+    for (int r = 0; r < 8; ++r) v[r] = conv_act<ACT>(v[r]);
     const bool second = p.out2 && co >= p.split;
     const int oc = second ? co - p.split : co;
     const int old_ = second ? p.out2_ld : p.out_ld;
@@ -619,11 +601,8 @@ int64_t x3p_image_halfs(int Cout, int K) { return (Cout % 256 == 0 && K % KS == 
 // whole 537 MB map nine times.  Whole fp16x3 step at batch 16, same box: tap-major 554 | 256-channel groups 552 | 128 563-566 |
 // 64 564-566 | 32 560 tiles/s.  EMP_X3P_KGROUP=n (A/B; n >= Cin / 32: tap-major)
 int x3p_kgroup(int KT, int Cin) {
-  const int CB = Cin / KS;
-  static const int env_kg = [] { const char* e = getenv("EMP_X3P_KGROUP"); return e ? atoi(e) : 0; }();
-  int kg = env_kg > 0 ? env_kg : 4;
-  if (KT == 1 || kg > CB || CB % kg != 0) kg = CB;
-  return kg;
+  static const int env_kg = env_int("EMP_X3P_KGROUP", 0);
+  return default_kgroup(KT, Cin / KS, env_kg > 0 ? env_kg : 0, 4);
 }
 
 // KT, Cin: the taps and channels of the main source (K == KT * Cin); kg: the walk group the kernel will be launched with (0: x3p_kgroup)
@@ -691,12 +670,9 @@ int launch_conv16x3p(const Conv32& c, hipStream_t s) {
   const int64_t M = (int64_t)c.N * c.Ho * c.Wo;
   EMP_REQUIRE(M < (1ll << 31), "conv16x3p: too many output pixels");
   p.M = (int)M;
-  p.mt = cdiv(p.M, 256);
-  p.nt = c.Cout / 256;
-  p.mt_per_xcd = cdiv(p.mt, 8);
+  const int grid = fill_raster(p, 256, 256);
   p.kg = c.x3p_kg > 0 ? c.x3p_kg : c.Cin / KS;      // (the image was packed along this walk)
   EMP_REQUIRE((c.Cin / KS) % p.kg == 0, "conv16x3p: the walk group must divide the channel blocks");
-  const int grid = 8 * p.mt_per_xcd * p.nt;
   const int act = c.act;
   // split-K (Conv32::kpart): a long-K launch of a few pixel tiles -- the merged 3x3 ASPP branches of ONE 1024^2 tile are 32 workgroups
   // over 576 K steps -- as S workgroups per tile while S * tiles fit the chip (one workgroup per CU), every split >= 8 steps; raw partial sums to the scratch, x3p_finish_kernel does the epilogue
@@ -718,10 +694,7 @@ int launch_conv16x3p(const Conv32& c, hipStream_t s) {
         q.bias = nullptr; q.bias_n = nullptr; q.res = nullptr; q.out2 = nullptr; q.split = 0;
         q.out = c.kpart; q.out_ld = c.Cout;
         q.ksteps = per; q.ksplit = S;
-        auto kern = &conv16x3p_kernel<0, 0, 0, true>;
-        if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(kern), X3P_LDS)) return rc;
-        hipLaunchKernelGGL(kern, dim3(8 * cdiv(p.mt * p.nt * S, 8)), dim3(512), X3P_LDS, s, q);
-        EMP_LAUNCH_CHECK();
+        if (int rc = launch_dyn(&conv16x3p_kernel<0, 0, 0, true>, 8 * cdiv(p.mt * p.nt * S, 8), 512, X3P_LDS, s, q)) return rc;
         const int64_t total = M * (c.Cout / 8);
         const dim3 fg((unsigned)std::min<int64_t>((total + 255) / 256, 8192));
         if (act == 1) hipLaunchKernelGGL(x3p_finish_kernel<1>, fg, dim3(256), 0, s, p, c.kpart, S, c.out_fmt, total);
@@ -732,12 +705,7 @@ int launch_conv16x3p(const Conv32& c, hipStream_t s) {
       }
     }
   }
-  auto go = [&](auto kern) -> int {
-    if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(kern), X3P_LDS)) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), X3P_LDS, s, p);
-    EMP_LAUNCH_CHECK();
-    return EMP_OK;
-  };
+  auto go = [&](auto kern) -> int { return launch_dyn(kern, grid, 512, X3P_LDS, s, p); };
   const int resf = !c.res ? 0 : (c.res_fmt ? 2 : 1);
   auto pick = [&](auto A, auto O) -> int {
     constexpr int a = decltype(A)::value, o = decltype(O)::value;

@@ -10,7 +10,7 @@
 // 8 waves = 4 pixel groups (two output rows each) x 2 cout halves; per tile and wave 36 ds_read_b128 + 72 MFMAs, one
 // LDS-only barrier, two 16-byte stores per lane.  K order (tap-major, two 32-channel steps per tap, ascending) and the
 // fp32 epilogue equal conv_igemm_kernel's, so results are bit-identical.
-#include "common.h"
+#include "igemm_common.h"
 
 namespace emp {
 namespace {
@@ -32,20 +32,6 @@ struct C64Params {
   int tiles_x, tiles_y, tiles;
 };
 
-__device__ __forceinline__ int c64_perm32(int x) {
-  const int t = x >> 4, i = x & 15;
-  return ((i >> 2) << 3) + (t << 2) + (i & 3);
-}
-template <int ACT>
-__device__ __forceinline__ float c64_act(float x) {
-  if (ACT == 1) return fmaxf(x, 0.f);
-  if (ACT == 2) return x / (1.f + __expf(-x));
-  return x;
-}
-__device__ __forceinline__ void c64_barrier() {   // LDS-only: the LDS-DMA of younger tiles stays in flight
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
 template <int ACT>
 __global__ void __launch_bounds__(512, 1) conv3x3_c64_kernel(const C64Params p) {
   extern __shared__ __attribute__((aligned(1024))) char lds[];     // 3 x C64_SLOT
@@ -64,7 +50,7 @@ __global__ void __launch_bounds__(512, 1) conv3x3_c64_kernel(const C64Params p) 
   f16x8 wreg[2][9][2];
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
-    const half_t* wr = p.wgt + (size_t)(ch * 32 + c64_perm32(c * 16 + fr)) * (9 * 64) + fq * 8;
+    const half_t* wr = p.wgt + (size_t)(ch * 32 + perm32(c * 16 + fr)) * (9 * 64) + fq * 8;
 #pragma unroll
     for (int t = 0; t < 9; ++t)
 #pragma unroll
@@ -103,8 +89,7 @@ __global__ void __launch_bounds__(512, 1) conv3x3_c64_kernel(const C64Params p) 
                       (unsigned)ix < (unsigned)p.W;
       const half_t* src = ok ? p.in + (((size_t)n * p.H + iy) * p.W + ix) * p.in_ld + (((lane & 7) ^ (hp & 7)) << 3)
                              : p.zero;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                       (__attribute__((address_space(3))) void*)(hb + piece * 1024), 16, 0, 0);
+      lds_dma16(src, hb + piece * 1024);
     }
   };
 
@@ -112,7 +97,7 @@ __global__ void __launch_bounds__(512, 1) conv3x3_c64_kernel(const C64Params p) 
   stage(0, 0);
   stage(1, 1);
   asm volatile("s_waitcnt vmcnt(3)" ::: "memory");   // tile 0 landed (tile 1 may be in flight)
-  c64_barrier();
+  lds_barrier();
 
   int slot = 0;
   for (int it = 0; it < my_tiles; ++it) {
@@ -156,14 +141,14 @@ __global__ void __launch_bounds__(512, 1) conv3x3_c64_kernel(const C64Params p) 
         f16x8 o;
 #pragma unroll
         for (int r4 = 0; r4 < 4; ++r4) {
-          o[r4] = (half_t)c64_act<ACT>(acc[0][t][r4] + bv[r4]);
-          o[4 + r4] = (half_t)c64_act<ACT>(acc[1][t][r4] + bv[4 + r4]);
+          o[r4] = (half_t)conv_act<ACT>(acc[0][t][r4] + bv[r4]);
+          o[4 + r4] = (half_t)conv_act<ACT>(acc[1][t][r4] + bv[4 + r4]);
         }
         if (oy < p.H && ox < p.W)
           *reinterpret_cast<f16x8*>(p.out + (((size_t)n * p.H + oy) * p.W + ox) * p.out_ld + ch * 32 + fq * 8) = o;
       }
     }
-    c64_barrier();     // tile it+1 visible to every wave; slot `slot` free for the DMA of tile it+3
+    lds_barrier();     // tile it+1 visible to every wave; slot `slot` free for the DMA of tile it+3
     slot = slot == 2 ? 0 : slot + 1;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // drain the dummy DMA batches
@@ -228,15 +213,14 @@ __global__ void __launch_bounds__(512, 1) conv3x3_c128_kernel(const C64Params p)
       const bool ok = valid && hp < C64_NPIX && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
       const half_t* src = ok ? p.in + (((size_t)n * p.H + iy) * p.W + ix) * p.in_ld + (((lane & 15) ^ (hp & 15)) << 3)
                              : p.zero;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                       (__attribute__((address_space(3))) void*)(hb + piece * 1024), 16, 0, 0);
+      lds_dma16(src, hb + piece * 1024);
     }
   };
 
   stage(0, 0);
   stage(1, 1);
   asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  c64_barrier();
+  lds_barrier();
 
   int slot = 0;
   for (int it = 0; it < my_tiles; ++it) {
@@ -268,18 +252,18 @@ __global__ void __launch_bounds__(512, 1) conv3x3_c128_kernel(const C64Params p)
     }
     // [DMA(it+1) x6, one tile ago] [stores(it-1)] [DMA(it+2) x6]: loads retire in order -> tile it+1 has landed
     asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    c64_barrier();                 // every wave is done with the halo of tile `it`: the slot becomes the output tile
+    lds_barrier();                 // every wave is done with the halo of tile `it`: the slot becomes the output tile
 #pragma unroll
     for (int y = 0; y < 8; ++y) {
       const int px = y * 16 + fr;
       typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
       f16x4 o;
 #pragma unroll
-      for (int r4 = 0; r4 < 4; ++r4) o[r4] = (half_t)c64_act<ACT>(acc[y][r4] + bv[r4]);
+      for (int r4 = 0; r4 < 4; ++r4) o[r4] = (half_t)conv_act<ACT>(acc[y][r4] + bv[r4]);
       const int chunk = 2 * wave + (fq >> 1);                   // 16-byte chunk of couts 16w + 4fq .. +3
       *reinterpret_cast<f16x4*>(hb + px * 256 + ((chunk ^ (px & 15)) << 4) + (fq & 1) * 8) = o;
     }
-    c64_barrier();
+    lds_barrier();
     {
       int n, y0, x0;
       tile_xy(it, n, y0, x0);
@@ -293,7 +277,7 @@ __global__ void __launch_bounds__(512, 1) conv3x3_c128_kernel(const C64Params p)
           *reinterpret_cast<f16x8*>(p.out + (((size_t)n * p.H + oy) * p.W + ox) * p.out_ld + c * 8) = v;
       }
     }
-    c64_barrier();                 // the slot is free for the DMA of tile it+3; tile it+1 is visible
+    lds_barrier();                 // the slot is free for the DMA of tile it+3; tile it+1 is visible
     slot = slot == 2 ? 0 : slot + 1;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -316,27 +300,16 @@ int launch_conv3x3_c64(const ConvParams& q, hipStream_t stream) {
   p.tiles = q.N * p.tiles_x * p.tiles_y;
   int grid = 256;
   while (grid > 8 && grid > p.tiles) grid -= 8;
-  auto go = [&](auto kern) -> int {
-    if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(kern), 3 * C64_SLOT)) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), 3 * C64_SLOT, stream, p);
-    return EMP_OK;
-  };
-  auto go128 = [&](auto kern) -> int {
-    if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(kern), 3 * C128_SLOT)) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), 3 * C128_SLOT, stream, p);
-    return EMP_OK;
-  };
-  int rc;
+  auto go = [&](auto kern) -> int { return launch_dyn(kern, grid, 512, 3 * C64_SLOT, stream, p); };
+  auto go128 = [&](auto kern) -> int { return launch_dyn(kern, grid, 512, 3 * C128_SLOT, stream, p); };
   if (q.Cin == 128) {
-    if (q.act == 1) rc = go128(&conv3x3_c128_kernel<1>);
-    else if (q.act == 2) rc = go128(&conv3x3_c128_kernel<2>);
-    else rc = go128(&conv3x3_c128_kernel<0>);
-  } else if (q.act == 1) rc = go(&conv3x3_c64_kernel<1>);
-  else if (q.act == 2) rc = go(&conv3x3_c64_kernel<2>);
-  else rc = go(&conv3x3_c64_kernel<0>);
-  if (rc) return rc;
-  EMP_LAUNCH_CHECK();
-  return EMP_OK;
+    if (q.act == 1) return go128(&conv3x3_c128_kernel<1>);
+    if (q.act == 2) return go128(&conv3x3_c128_kernel<2>);
+    return go128(&conv3x3_c128_kernel<0>);
+  }
+  if (q.act == 1) return go(&conv3x3_c64_kernel<1>);
+  if (q.act == 2) return go(&conv3x3_c64_kernel<2>);
+  return go(&conv3x3_c64_kernel<0>);
 }
 
 }  // namespace emp

@@ -32,7 +32,7 @@
 // Work-group -> tile map is XCD-aware: the 8 XCDs get contiguous ranges of
 // pixel tiles (neighbouring tiles share input rows through the XCD's L2) and
 // the cout tiles of one pixel tile run back to back on the same XCD.
-#include "common.h"
+#include "igemm_common.h"
 
 // The same kernel as a GROUPED convolution (nn.Conv2d(groups = g): the 3x3 of a RegNet bottleneck) is compiled from this
 // source by conv_igemm_grouped.hip, which defines EMP_IGEMM_GROUPED before including it: blockIdx.y = group, the group's
@@ -64,22 +64,6 @@ namespace {
 constexpr int BK = 64;          // input channels per K-step
 constexpr int ROWB = BK * 2;    // bytes per LDS row
 
-__device__ __forceinline__ int perm32(int x) {
-  // LDS row (x within a 32-cout group) -> cout within the group.
-  // x = t*16 + i (t = cout-tile parity, i = MFMA row) -> (i>>2)*8 + t*4 + (i&3)
-  int t = x >> 4, i = x & 15;
-  return ((i >> 2) << 3) + (t << 2) + (i & 3);
-}
-
-// epilogue activation: 0 none | 1 ReLU | 2 SiLU (x * sigmoid(x), bifpn.py:35,91)
-// compile-time ACT: a run-time switch inside the unrolled epilogue costs ~6 scalar branches PER ELEMENT
-// [measured: 470-850 s_cbranch per kernel, the epilogue of a 256 x 256 tile took ~10 us]
-template <int ACT>
-__device__ __forceinline__ float apply_act(float x) {
-  if (ACT == 1) return fmaxf(x, 0.f);
-  if (ACT == 2) return x / (1.f + __expf(-x));
-  return x;
-}
 // calls f(integral_constant<int, act>) with act in {0, 1, 2}
 template <typename F>
 __device__ __forceinline__ void dispatch_act(int act, F&& f) {
@@ -121,12 +105,8 @@ __global__ void __launch_bounds__(256, OCC) conv_igemm_kernel(EMP_IGEMM_KARGS) {
   __shared__ __attribute__((aligned(1024))) char lds[2 * (A_BYTES + B_BYTES)];
 
   // ---- tile assignment (XCD-aware) ----
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7;
-  const int j = bid >> 3;
-  const int mtile = xcd * p.mt_per_xcd + j / p.nt;
-  const int ntile = j % p.nt;
-  if (mtile >= p.mt) return;
+  int mtile, ntile;
+  if (!tile_of_block(blockIdx.x, p.mt, p.nt, p.mt_per_xcd, 0, mtile, ntile)) return;
   const int m0 = mtile * BM;
   const int n0 = ntile * BN;
 
@@ -242,9 +222,7 @@ __global__ void __launch_bounds__(256, OCC) conv_igemm_kernel(EMP_IGEMM_KARGS) {
 #pragma unroll
     for (int i = 0; i < A_ITERS; ++i) {
       if constexpr (GLDS) {
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)a_cur[i],
-                                         (__attribute__((address_space(3))) void*)(a_s + (w + 4 * i) * 1024),
-                                         16, 0, 0);
+        lds_dma16(a_cur[i], a_s + (w + 4 * i) * 1024);
       } else {
         ra[i] = *reinterpret_cast<const f16x8*>(a_cur[i]);
       }
@@ -253,9 +231,7 @@ __global__ void __launch_bounds__(256, OCC) conv_igemm_kernel(EMP_IGEMM_KARGS) {
 #pragma unroll
     for (int i = 0; i < B_ITERS; ++i) {
       if constexpr (GLDS) {
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)b_cur[i],
-                                         (__attribute__((address_space(3))) void*)(b_s + (w + 4 * i) * 1024),
-                                         16, 0, 0);
+        lds_dma16(b_cur[i], b_s + (w + 4 * i) * 1024);
       } else {
         rb[i] = *reinterpret_cast<const f16x8*>(b_cur[i]);
       }
@@ -388,7 +364,7 @@ __global__ void __launch_bounds__(256, OCC) conv_igemm_kernel(EMP_IGEMM_KARGS) {
       }
       f16x8 o;
 #pragma unroll
-      for (int r = 0; r < 8; ++r) o[r] = (half_t)apply_act<ACT>(v[r]);
+      for (int r = 0; r < 8; ++r) o[r] = (half_t)conv_act<ACT>(v[r]);
       *reinterpret_cast<f16x8*>(out_ptr(p, m, co_l, HoWo)) = o;
     }
     });
@@ -433,7 +409,7 @@ __global__ void __launch_bounds__(256, OCC) conv_igemm_kernel(EMP_IGEMM_KARGS) {
         }
         f16x8 o;
 #pragma unroll
-        for (int r = 0; r < 8; ++r) o[r] = (half_t)apply_act<ACT>(v[r]);
+        for (int r = 0; r < 8; ++r) o[r] = (half_t)conv_act<ACT>(v[r]);
         *reinterpret_cast<f16x8*>(out_ptr(p, m, co, HoWo)) = o;
       }
     }
@@ -444,10 +420,7 @@ __global__ void __launch_bounds__(256, OCC) conv_igemm_kernel(EMP_IGEMM_KARGS) {
 #ifdef EMP_IGEMM_GROUPED
 template <int BM, int BN, int WPM, int WPN, bool GLDS, bool EPI_LDS, int OCC = 2>
 int launch_grouped_tpl(ConvParams p, int groups, int gs_in, long long gs_w, int gs_out, hipStream_t stream) {
-  p.mt = cdiv(p.M, BM);
-  p.nt = cdiv(p.Cout, BN);
-  p.mt_per_xcd = cdiv(p.mt, 8);
-  const int grid = 8 * p.mt_per_xcd * p.nt;
+  const int grid = fill_raster(p, BM, BN);
   hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WPM, WPN, GLDS, EPI_LDS, OCC>), dim3(grid, groups), dim3(256), 0, stream, p, gs_in,
                      gs_w, gs_out);
   EMP_LAUNCH_CHECK();
@@ -485,10 +458,7 @@ int launch_conv_igemm_grouped(const ConvParams& p, int groups, int gs_in, long l
 #else   // !EMP_IGEMM_GROUPED
 template <int BM, int BN, int WPM, int WPN, bool GLDS, bool EPI_LDS, int OCC = 2>
 int launch_tpl(ConvParams p, hipStream_t stream) {
-  p.mt = cdiv(p.M, BM);
-  p.nt = cdiv(p.Cout, BN);
-  p.mt_per_xcd = cdiv(p.mt, 8);
-  const int grid = 8 * p.mt_per_xcd * p.nt;
+  const int grid = fill_raster(p, BM, BN);
   hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WPM, WPN, GLDS, EPI_LDS, OCC>), dim3(grid), dim3(256), 0, stream, p);
   EMP_LAUNCH_CHECK();
   return EMP_OK;
@@ -502,8 +472,8 @@ int launch_tpl(ConvParams p, hipStream_t stream) {
 // tile).  [profiles/r02_rule_sweep.txt: layer1.0 conv3+ds 508 -> 402 us, layer2.0 conv3+ds 419 -> 313, layer4 conv3
 // 490 -> 450; K = 128 / 256 with a residual (layer2 / layer3 conv3) stay on 128 x 128: 263 vs 294, 165 vs 180.]
 bool conv_uses_256(const ConvParams& p) {
-  static const bool no256 = [] { const char* e = getenv("EMP_CONV_NO256"); return e && e[0] == '1'; }();   // A/B runs
-  static const int min_k = [] { const char* e = getenv("EMP_CONV_256_MINK"); return e ? atoi(e) : 512; }();
+  static const bool no256 = env_is("EMP_CONV_NO256", '1');   // A/B runs
+  static const int min_k = env_int("EMP_CONV_256_MINK", 512);
   const int64_t tiles256 = (int64_t)cdiv(p.M, 256) * (p.Cout / 256);
   const int k256 = p.KH * p.KW * p.Cin + (p.in2 ? p.Cin2 : 0);
   const bool out2_ok = !p.out2 || (!p.out3 && p.split % 256 == 0);      // whole cout tiles to the second tensor
@@ -512,7 +482,7 @@ bool conv_uses_256(const ConvParams& p) {
 // half tile 256 pixels x 128 couts, two workgroups per CU (conv_igemm256.hip): the 128-cout layers with K >= 256
 // (layer2 conv1 / stride-2 conv2: 350 -> 325 us, 244 -> 230) -- the 128 x 128 tile is LDS-read bound there
 bool conv_uses_h256(const ConvParams& p) {
-  static const int h256 = [] { const char* e = getenv("EMP_CONV_H256"); return e ? atoi(e) : 1; }();   // A/B runs: 0 off, 2 all
+  static const int h256 = env_int("EMP_CONV_H256", 1);   // A/B runs: 0 off, 2 all
   if (!h256 || !conv_igemm_h256_supported(p)) return false;
   const int64_t tiles = (int64_t)cdiv(p.M, 128) * (p.Cout / 128) / 2;
   if (tiles < 1024) return false;
@@ -581,7 +551,7 @@ int launch_conv_igemm(const ConvParams& p, int variant, hipStream_t stream) {
   {
     // 64 -> 64 channel 3x3 (ResNet layer1 conv2): weights in registers, halo tile in LDS (conv3x3c64.hip), once there
     // are enough 8 x 16 tiles for its 256 persistent workgroups
-    static const bool no_c64 = [] { const char* e = getenv("EMP_CONV_NO_C64"); return e && e[0] == '1'; }();   // A/B runs
+    static const bool no_c64 = env_is("EMP_CONV_NO_C64", '1');   // A/B runs
     if (tile == 0 && !no_c64 && conv3x3_c64_supported(p) && (int64_t)p.N * cdiv(p.H, 8) * cdiv(p.W, 16) >= 1024)
       return launch_conv3x3_c64(p, stream);
   }
@@ -594,7 +564,7 @@ int launch_conv_igemm(const ConvParams& p, int variant, hipStream_t stream) {
   ConvParams q = p;
   {
     const int CB = p.Cin / 64, KT = p.KH * p.KW;
-    static const int env_kg = [] { const char* e = getenv("EMP_CONV_KGROUP"); return e ? atoi(e) : 0; }();   // A/B runs
+    static const int env_kg = env_int("EMP_CONV_KGROUP", 0);   // A/B runs
     if (kg == 0) kg = env_kg;
     if (kg == 0) kg = (KT > 1 && CB > 4 && CB % 4 == 0) ? 4 : CB;
     if (kg > CB || CB % kg != 0 || KT == 1) kg = CB;
@@ -609,10 +579,10 @@ int launch_conv_igemm(const ConvParams& p, int variant, hipStream_t stream) {
     if (p.Cout > 128 && cdiv(p.Cout, 64) * 64 < cdiv(p.Cout, 128) * 128) tile = 2;
     // a single image leaves the deep layers with a handful of 128x128 tiles for 256 CUs (batch-1 latency, the
     // reference's own calling convention): 64x64 tiles walk K in the same order (bit-identical results) on 4x the CUs
-    static const int small_below = [] { const char* e = getenv("EMP_CONV_SMALL_TILES_BELOW"); return e ? atoi(e) : 256; }();
+    static const int small_below = env_int("EMP_CONV_SMALL_TILES_BELOW", 256);
     if (tile == 1 && (int64_t)cdiv(p.M, 128) * cdiv(p.Cout, 128) < small_below && !p.out2) {
       // one workgroup per CU: only the workgroup's own prefetch hides the memory latency -> deep-ring variant
-      static const bool no_s64 = [] { const char* e = getenv("EMP_CONV_NO_S64"); return e && e[0] == '1'; }();   // A/B runs
+      static const bool no_s64 = env_is("EMP_CONV_NO_S64", '1');   // A/B runs
       if (!no_s64 && conv_igemm_s64_supported(p)) return launch_conv_igemm_s64(p, stream);
       tile = 3;
     }

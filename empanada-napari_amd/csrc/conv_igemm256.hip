@@ -36,7 +36,7 @@
 //       256^2 template measures the same 1.32 PFLOP/s on random operands.
 //   * LDS rows are 64 B; 16-byte chunk c of row r is stored at chunk c ^ ((-(r >> 2)) & 3): conflict-free for the
 //     ds_read_b128 lane groups of gfx950; the swizzle is applied to the DMA source address (lane-linear dest).
-#include "common.h"
+#include "igemm_common.h"
 
 namespace emp {
 
@@ -47,27 +47,10 @@ constexpr int SLOT_BYTES = 512 * 64;      // 256 pixel rows + 256 cout rows
 constexpr int W_OFF = 256 * 64;           // cout rows start
 constexpr int NSLOT = 4;
 
-__device__ __forceinline__ int perm32b(int x) {
-  const int t = x >> 4, i = x & 15;
-  return ((i >> 2) << 3) + (t << 2) + (i & 3);
-}
-__device__ __forceinline__ void lds_barrier() {
-  // Raw barrier that orders LDS traffic only.  A fence (or __syncthreads) would also drain vmcnt: an in-flight
-  // LDS-DMA is a pending LDS write on the VM counter.  The "memory" clobber keeps the compiler from moving
-  // memory accesses across it; DMA completion is handled by the counted vmcnt waits of the issuing waves.
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
 // Epilogue of a 128-pixel x 64-cout wave tile straight from the accumulators: lane (fq, fr) owns couts
 // co0 + pair*32 + fq*8 + [0,8) of pixel mrow0 + q*16 + fr.  ACT is a compile-time constant (a run-time switch inside
 // the unrolled loops costs ~6 scalar branches per ELEMENT: 850 s_cbranch, ~10 us per 256 x 256 tile [measured]); the
 // bias is read once and the 16 residual fragments are requested up front (the K-loop's fragment registers are free).
-template <int ACT>
-__device__ __forceinline__ float act_c(float x) {
-  if (ACT == 1) return fmaxf(x, 0.f);
-  if (ACT == 2) return x / (1.f + __expf(-x));
-  return x;
-}
 template <int ACT>
 __device__ __forceinline__ void wave_epilogue(const ConvParams& p, f32x4 (&acc)[4][8], int mrow0, int co0, int fr, int fq,
                                               int HoWo) {
@@ -122,7 +105,7 @@ __device__ __forceinline__ void wave_epilogue(const ConvParams& p, f32x4 (&acc)[
       }
       f16x8 o;
 #pragma unroll
-      for (int r = 0; r < 8; ++r) o[r] = (half_t)act_c<ACT>(v[r]);
+      for (int r = 0; r < 8; ++r) o[r] = (half_t)conv_act<ACT>(v[r]);
       *reinterpret_cast<f16x8*>(orow + P * 32) = o;
     }
   }
@@ -178,7 +161,7 @@ __device__ __forceinline__ void wave_epilogue_b2b(const ConvParams& p, f32x4 (&a
       }
       f16x8 o;
 #pragma unroll
-      for (int r = 0; r < 8; ++r) o[r] = (half_t)act_c<ACT>(v[r]);
+      for (int r = 0; r < 8; ++r) o[r] = (half_t)conv_act<ACT>(v[r]);
       if (m < p.M) *reinterpret_cast<f16x8*>(orow + P * 32) = o;
       const int chunk = wc * 8 + P * 4 + fq;
       *reinterpret_cast<f16x8*>(lds + row * 512 + ((chunk ^ (row & 15)) << 4)) = o;
@@ -196,7 +179,7 @@ __device__ __forceinline__ void wave_epilogue_b2b(const ConvParams& p, f32x4 (&a
     for (int tp = 0; tp < 2; ++tp)
 #pragma unroll
       for (int t = 0; t < 2; ++t) a2[tp][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int r0 = pp * 32 + perm32b(fr), r1 = pp * 32 + perm32b(16 + fr);
+    const int r0 = pp * 32 + perm32(fr), r1 = pp * 32 + perm32(16 + fr);
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) {
       const f16x8 wa = *reinterpret_cast<const f16x8*>(w2 + r0 * 512 + (((ks * 4 + fq) ^ (r0 & 15)) << 4));
@@ -248,19 +231,8 @@ __global__ void __launch_bounds__(512, 1) conv_igemm256_kernel(const ConvParams 
   const unsigned long long stamp_c0 = __builtin_amdgcn_s_memtime(), stamp_r0 = __builtin_amdgcn_s_memrealtime();
 #endif
 
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, j = bid >> 3;
-  int mtile = xcd * p.mt_per_xcd + j / p.nt;
-  int ntile = j % p.nt;
-  if (p.ngroup > 0) {
-    // intermediate raster (round 6): the XCD keeps `ngroup` cout tiles resident and walks ALL its pixel
-    // tiles under them, then the next group -- the weights (ngroup x K x 512 B) survive the rounds' output in L2, the
-    // activations are re-read nt / ngroup times instead of the weights mt_per_xcd times
-    const int per = p.mt_per_xcd * p.ngroup, g = j / per, rem = j - g * per;
-    mtile = xcd * p.mt_per_xcd + rem / p.ngroup;
-    ntile = g * p.ngroup + rem % p.ngroup;
-  }
-  if (mtile >= p.mt) return;
+  int mtile, ntile;
+  if (!tile_of_block(blockIdx.x, p.mt, p.nt, p.mt_per_xcd, p.ngroup, mtile, ntile)) return;
   const int m0 = mtile * 256, n0 = ntile * 256;
 
   const int tid = threadIdx.x, l = tid & 63;
@@ -281,7 +253,7 @@ __global__ void __launch_bounds__(512, 1) conv_igemm256_kernel(const ConvParams 
 
   // ---- staging: wave w moves pixel pieces {w, w+8} and cout pieces {w, w+8} (16 rows x 64 B each) ----
   const int srow = l >> 2;                                   // row within the piece
-  const int schunk = (l & 3) ^ ((-(l >> 4)) & 3);            // logical 16-B chunk this lane fetches
+  const int schunk = stage_chunk64(l);                       // logical 16-B chunk this lane fetches
   const half_t* a_img[2];
   int a_iy0[2], a_ix0[2];
   const half_t* a_cur[2];
@@ -290,39 +262,14 @@ __global__ void __launch_bounds__(512, 1) conv_igemm256_kernel(const ConvParams 
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int m = m0 + (wave + 8 * i) * 16 + srow;
-    a_img[i] = p.in;
-    a_iy0[i] = a_ix0[i] = -(1 << 28);
-    a_cur[i] = p.zero;
-    a_inc[i] = 0;
-    a_two[i] = p.zero;
-    if (m < p.M) {
-      if (p.in2) {
-        const int n = m / HoWo;
-        const int r = m - n * HoWo;
-        const int oy = r / p.Wo;
-        const int ox = r - oy * p.Wo;
-        a_two[i] = p.in2 + (((size_t)n * p.H2 + oy * p.stride2) * p.W2 + ox * p.stride2) * p.in2_ld + schunk * 8;
-      }
-      if (pointwise) {
-        a_cur[i] = p.in + (size_t)m * p.in_ld + schunk * 8;
-        a_inc[i] = KS;
-      } else {
-        const int n = m / HoWo;
-        const int r = m - n * HoWo;
-        const int oy = r / p.Wo;
-        const int ox = r - oy * p.Wo;
-        a_iy0[i] = oy * p.stride - p.pad;
-        a_ix0[i] = ox * p.stride - p.pad;
-        a_img[i] = p.in + (size_t)n * p.H * p.W * p.in_ld + schunk * 8;
-      }
-    }
+    pixel_row_ptr(p, m, HoWo, pointwise, schunk * 8, KS, a_img[i], a_iy0[i], a_ix0[i], a_cur[i], a_inc[i], a_two[i]);
   }
   const half_t* b_base[2];
   const half_t* b_cur[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int row = (wave + 8 * i) * 16 + srow;
-    const int co = n0 + (row & ~31) + perm32b(row & 31);
+    const int co = n0 + (row & ~31) + perm32(row & 31);
     b_base[i] = b_cur[i] = p.wgt + (size_t)co * (KT * p.Cin + (p.in2 ? p.Cin2 : 0)) + schunk * 8;
     if (wpacked) b_cur[i] = p.wgt + (((size_t)ntile * KTOT * 16 + (wave + 8 * i)) * 512 + l * 8);
   }
@@ -342,12 +289,7 @@ __global__ void __launch_bounds__(512, 1) conv_igemm256_kernel(const ConvParams 
       if (!pointwise) {
         const int dy = st_ky * p.dil, dx = st_kx * p.dil;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const int iy = a_iy0[i] + dy, ix = a_ix0[i] + dx;
-          const bool ok = (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
-          a_cur[i] = ok ? a_img[i] + ((size_t)iy * p.W + ix) * p.in_ld + c0 : p.zero;
-          a_inc[i] = ok ? KS : 0;
-        }
+        for (int i = 0; i < 2; ++i) tap_src(a_img[i], a_iy0[i], a_ix0[i], dy, dx, p.H, p.W, p.in_ld, c0, p.zero, KS, a_cur[i], a_inc[i]);
       }
       if (KG != CB && !wpacked) {
         const int koff = (st_ky * p.KW + st_kx) * p.Cin + c0;
@@ -372,8 +314,7 @@ __global__ void __launch_bounds__(512, 1) conv_igemm256_kernel(const ConvParams 
   };
   auto dma = [&](int i) {     // piece i of K-tile st_u into ring slot st_u & 3
     char* dst = lds + (st_u & (NSLOT - 1)) * SLOT_BYTES + (i >> 1) * W_OFF + (wave + 8 * (i & 1)) * 1024;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src[i],
-                                     (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+    lds_dma16(src[i], dst);
   };
 
   // ---- fragment addressing (lane-constant) ----
@@ -397,8 +338,7 @@ __global__ void __launch_bounds__(512, 1) conv_igemm256_kernel(const ConvParams 
       const int piece = wave * 4 + i;                    // 1 KiB = rows 2*piece, 2*piece + 1
       const int r = piece * 2 + (l >> 5), cdst = l & 31;
       const half_t* srcw = p.next_w + (size_t)r * 256 + ((cdst ^ (r & 15)) << 3);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)srcw,
-                                       (__attribute__((address_space(3))) void*)(lds + NSLOT * SLOT_BYTES + piece * 1024), 16, 0, 0);
+      lds_dma16(srcw, lds + NSLOT * SLOT_BYTES + piece * 1024);
     }
   }
   f16x8 pf[8], wf[4];
@@ -534,19 +474,8 @@ constexpr int WIDE_LDS_BYTES = WP_BASE + 3 * WP_SLOT;      // 163840
 
 __global__ void __launch_bounds__(512, 1) conv_igemm256w_kernel(const ConvParams p) {
   extern __shared__ __attribute__((aligned(1024))) char lds[];
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, j = bid >> 3;
-  int mtile = xcd * p.mt_per_xcd + j / p.nt;
-  int ntile = j % p.nt;
-  if (p.ngroup > 0) {
-    // intermediate raster (round 6): the XCD keeps `ngroup` cout tiles resident and walks ALL its pixel
-    // tiles under them, then the next group -- the weights (ngroup x K x 512 B) survive the rounds' output in L2, the
-    // activations are re-read nt / ngroup times instead of the weights mt_per_xcd times
-    const int per = p.mt_per_xcd * p.ngroup, g = j / per, rem = j - g * per;
-    mtile = xcd * p.mt_per_xcd + rem / p.ngroup;
-    ntile = g * p.ngroup + rem % p.ngroup;
-  }
-  if (mtile >= p.mt) return;
+  int mtile, ntile;
+  if (!tile_of_block(blockIdx.x, p.mt, p.nt, p.mt_per_xcd, p.ngroup, mtile, ntile)) return;
   const int m0 = mtile * 256, n0 = ntile * 256;
 
   const int tid = threadIdx.x, l = tid & 63;
@@ -566,11 +495,11 @@ __global__ void __launch_bounds__(512, 1) conv_igemm256w_kernel(const ConvParams
   const half_t* b_base[2];
   const half_t* b_cur[2];
   {
-    const int srow = l >> 2, schunk = (l & 3) ^ ((-(l >> 4)) & 3);
+    const int srow = l >> 2, schunk = stage_chunk64(l);
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int row = (wave + 8 * i) * 16 + srow;
-      const int co = n0 + (row & ~31) + perm32b(row & 31);
+      const int co = n0 + (row & ~31) + perm32(row & 31);
       b_base[i] = b_cur[i] = p.wgt + (size_t)co * (KT * p.Cin + (p.in2 ? p.Cin2 : 0)) + schunk * 8;
       if (wpacked) b_cur[i] = p.wgt + (((size_t)ntile * KTOT * 16 + (wave + 8 * i)) * 512 + l * 8);
     }
@@ -593,8 +522,7 @@ __global__ void __launch_bounds__(512, 1) conv_igemm256w_kernel(const ConvParams
   };
   auto dma_w = [&](int i) {      // cout piece i of K-tile w_t
     char* dst = lds + (w_t & 3) * WW_SLOT + (wave + 8 * i) * 1024;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)b_cur[i],
-                                     (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+    lds_dma16(b_cur[i], dst);
     b_cur[i] += b_step;
   };
 
@@ -607,24 +535,7 @@ __global__ void __launch_bounds__(512, 1) conv_igemm256w_kernel(const ConvParams
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int m = m0 + (wave + 8 * i) * 8 + prow;
-    a_iy0[i] = a_ix0[i] = -(1 << 28);
-    a_pix[i] = 0;
-    a_cur[i] = p.zero;
-    a_inc[i] = 0;
-    if (m < p.M) {
-      if (pointwise) {
-        a_cur[i] = p.in + (size_t)m * p.in_ld + pchunk * 8;
-        a_inc[i] = 2 * KS;
-      } else {
-        const int n = m / HoWo;
-        const int r = m - n * HoWo;
-        const int oy = r / p.Wo;
-        const int ox = r - oy * p.Wo;
-        a_iy0[i] = oy * p.stride - p.pad;
-        a_ix0[i] = ox * p.stride - p.pad;
-        a_pix[i] = n * p.H * p.W;
-      }
-    }
+    pixel_row_pix(p, m, HoWo, pointwise, p.in_ld, pchunk * 8, 2 * KS, a_iy0[i], a_ix0[i], a_pix[i], a_cur[i], a_inc[i]);
   }
   int p_u = 0, p_ky = 0, p_kx = 0, p_cb = 0, p_grp = 0, p_slot = 0;      // pair the next pixel pieces belong to
   const int KG2 = KG >> 1;
@@ -636,11 +547,7 @@ __global__ void __launch_bounds__(512, 1) conv_igemm256w_kernel(const ConvParams
         a_cur[i] = p.zero;
         a_inc[i] = 0;
         if (m < p.M) {
-          const int n = m / HoWo;
-          const int r = m - n * HoWo;
-          const int oy = r / p.Wo;
-          const int ox = r - oy * p.Wo;
-          a_cur[i] = p.in2 + (((size_t)n * p.H2 + oy * p.stride2) * p.W2 + ox * p.stride2) * p.in2_ld + pchunk * 8;
+          a_cur[i] = second_source_row(p, m, HoWo, pchunk * 8);
           a_inc[i] = 2 * KS;
         }
       }
@@ -649,12 +556,8 @@ __global__ void __launch_bounds__(512, 1) conv_igemm256w_kernel(const ConvParams
       const int c0 = p_grp * KG * KS + pchunk * 8;
       const int dy = p_ky * p.dil, dx = p_kx * p.dil;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int iy = a_iy0[i] + dy, ix = a_ix0[i] + dx;
-        const bool ok = (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
-        a_cur[i] = ok ? p.in + ((size_t)(a_pix[i] + iy * p.W + ix) * p.in_ld + c0) : p.zero;
-        a_inc[i] = ok ? 2 * KS : 0;
-      }
+      for (int i = 0; i < 4; ++i)
+        tap_src_pix(p.in, a_pix[i], a_iy0[i], a_ix0[i], dy, dx, p.H, p.W, p.in_ld, c0, p.zero, 2 * KS, a_cur[i], a_inc[i]);
     }
     if (++p_cb == KG2) {
       p_cb = 0;
@@ -666,8 +569,7 @@ __global__ void __launch_bounds__(512, 1) conv_igemm256w_kernel(const ConvParams
   };
   auto dma_p = [&](int i) {      // pixel piece i of pair p_u into pixel slot p_slot
     char* dst = lds + WP_BASE + p_slot * WP_SLOT + (wave + 8 * i) * 1024;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)a_cur[i],
-                                     (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+    lds_dma16(a_cur[i], dst);
     a_cur[i] += a_inc[i];
   };
   auto p_next = [&]() { ++p_u; p_slot = (p_slot == 2) ? 0 : p_slot + 1; };
@@ -818,11 +720,8 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_h256_kernel(const ConvParam
   static_assert(PXR + COR == 384 && NP == 6, "half tile: 128 x 256 or 256 x 128");
   extern __shared__ __attribute__((aligned(1024))) char lds[];
 
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, j = bid >> 3;
-  const int mtile = xcd * p.mt_per_xcd + j / p.nt;
-  const int ntile = j % p.nt;
-  if (mtile >= p.mt) return;
+  int mtile, ntile;
+  if (!tile_of_block(blockIdx.x, p.mt, p.nt, p.mt_per_xcd, 0, mtile, ntile)) return;
   const int m0 = mtile * PXR, n0 = ntile * COR;
 
   const int tid = threadIdx.x, l = tid & 63;
@@ -837,7 +736,7 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_h256_kernel(const ConvParam
   const bool pointwise = (KT == 1) && p.stride == 1 && p.pad == 0;
 
   const int srow = l >> 2;
-  const int schunk = (l & 3) ^ ((-(l >> 4)) & 3);
+  const int schunk = stage_chunk64(l);
   const half_t* a_img[PPW];
   int a_iy0[PPW], a_ix0[PPW];
   const half_t* a_cur[PPW];
@@ -846,39 +745,14 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_h256_kernel(const ConvParam
 #pragma unroll
   for (int i = 0; i < PPW; ++i) {
     const int m = m0 + (wave + 4 * i) * 16 + srow;
-    a_img[i] = p.in;
-    a_iy0[i] = a_ix0[i] = -(1 << 28);
-    a_cur[i] = p.zero;
-    a_inc[i] = 0;
-    a_two[i] = p.zero;
-    if (m < p.M) {
-      if (p.in2) {
-        const int n = m / HoWo;
-        const int r = m - n * HoWo;
-        const int oy = r / p.Wo;
-        const int ox = r - oy * p.Wo;
-        a_two[i] = p.in2 + (((size_t)n * p.H2 + oy * p.stride2) * p.W2 + ox * p.stride2) * p.in2_ld + schunk * 8;
-      }
-      if (pointwise) {
-        a_cur[i] = p.in + (size_t)m * p.in_ld + schunk * 8;
-        a_inc[i] = KS;
-      } else {
-        const int n = m / HoWo;
-        const int r = m - n * HoWo;
-        const int oy = r / p.Wo;
-        const int ox = r - oy * p.Wo;
-        a_iy0[i] = oy * p.stride - p.pad;
-        a_ix0[i] = ox * p.stride - p.pad;
-        a_img[i] = p.in + (size_t)n * p.H * p.W * p.in_ld + schunk * 8;
-      }
-    }
+    pixel_row_ptr(p, m, HoWo, pointwise, schunk * 8, KS, a_img[i], a_iy0[i], a_ix0[i], a_cur[i], a_inc[i], a_two[i]);
   }
   const half_t* b_base[CPW];
   const half_t* b_cur[CPW];
 #pragma unroll
   for (int i = 0; i < CPW; ++i) {
     const int row = (wave + 4 * i) * 16 + srow;
-    const int co = n0 + (row & ~31) + perm32b(row & 31);
+    const int co = n0 + (row & ~31) + perm32(row & 31);
     b_base[i] = b_cur[i] = p.wgt + (size_t)co * (KT * p.Cin + (p.in2 ? p.Cin2 : 0)) + schunk * 8;
   }
   int st_ky = 0, st_kx = 0, st_cb = 0, st_grp = 0, st_u = 0;
@@ -895,12 +769,7 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_h256_kernel(const ConvParam
       if (!pointwise) {
         const int dy = st_ky * p.dil, dx = st_kx * p.dil;
 #pragma unroll
-        for (int i = 0; i < PPW; ++i) {
-          const int iy = a_iy0[i] + dy, ix = a_ix0[i] + dx;
-          const bool ok = (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
-          a_cur[i] = ok ? a_img[i] + ((size_t)iy * p.W + ix) * p.in_ld + c0 : p.zero;
-          a_inc[i] = ok ? KS : 0;
-        }
+        for (int i = 0; i < PPW; ++i) tap_src(a_img[i], a_iy0[i], a_ix0[i], dy, dx, p.H, p.W, p.in_ld, c0, p.zero, KS, a_cur[i], a_inc[i]);
       }
       if (KG != CB) {
         const int koff = (st_ky * p.KW + st_kx) * p.Cin + c0;
@@ -911,14 +780,12 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_h256_kernel(const ConvParam
     char* slot = lds + (st_u % 3) * HSLOT;
 #pragma unroll
     for (int i = 0; i < PPW; ++i) {
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)a_cur[i],
-                                       (__attribute__((address_space(3))) void*)(slot + (wave + 4 * i) * 1024), 16, 0, 0);
+      lds_dma16(a_cur[i], slot + (wave + 4 * i) * 1024);
       a_cur[i] += a_inc[i];
     }
 #pragma unroll
     for (int i = 0; i < CPW; ++i) {
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)b_cur[i],
-                                       (__attribute__((address_space(3))) void*)(slot + HW_OFF + (wave + 4 * i) * 1024), 16, 0, 0);
+      lds_dma16(b_cur[i], slot + HW_OFF + (wave + 4 * i) * 1024);
       b_cur[i] += KS;
     }
     if (++st_cb == KG) {
@@ -1004,8 +871,8 @@ __global__ void __launch_bounds__(256) pack256_kernel(const half_t* __restrict__
     const int64_t tt = i >> 10;
     const int t = (int)(tt % KTOT), ntile = (int)(tt / KTOT);
     const int row = pc * 16 + (l >> 2);
-    const int co = ntile * 256 + (row & ~31) + perm32b(row & 31);
-    const int chunk = (l & 3) ^ ((-(l >> 4)) & 3);
+    const int co = ntile * 256 + (row & ~31) + perm32(row & 31);
+    const int chunk = stage_chunk64(l);
     int koff;
     if (t < KT1) {
       const int per = KT * KG, g = t / per, idx = t - g * per, tap = idx / KG, cb = idx - tap * KG;
@@ -1020,10 +887,7 @@ __global__ void __launch_bounds__(256) pack256_kernel(const half_t* __restrict__
 template <int DMA_EARLY, bool B2B = false>
 static int launch256(const ConvParams& p, int grid, hipStream_t stream) {
   constexpr int LDS_BYTES = NSLOT * SLOT_BYTES + (B2B ? 64 * 256 * 2 : 0);
-  if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(&conv_igemm256_kernel<DMA_EARLY, B2B>), LDS_BYTES)) return rc;
-  hipLaunchKernelGGL((conv_igemm256_kernel<DMA_EARLY, B2B>), dim3(grid), dim3(512), LDS_BYTES, stream, p);
-  EMP_LAUNCH_CHECK();
-  return EMP_OK;
+  return launch_dyn(&conv_igemm256_kernel<DMA_EARLY, B2B>, grid, 512, LDS_BYTES, stream, p);
 }
 
 // kg: channel slabs (32 ch) per K-walk group, 0 = default; mode: 0 = default, 1 / 2 = 2 / 4 DMA pieces issued early
@@ -1033,43 +897,30 @@ int launch_conv_igemm256(ConvParams p, hipStream_t stream, int kg, int mode, boo
   EMP_REQUIRE(p.out2 == nullptr || (p.split % 256 == 0 && p.split > 0 && p.split < p.Cout && p.out3 == nullptr &&
                                     p.next_w == nullptr && p.out2_ld % 8 == 0 && p.out2_ld >= p.Cout - p.split),
               "conv256: a second destination takes whole 256-cout tiles (split=%d)", p.split);
-  {
-    const int CB = p.Cin / KS, KT = p.KH * p.KW;
-    static const int env_kg = [] { const char* e = getenv("EMP_CONV256_KGROUP"); return e ? atoi(e) : 0; }();   // A/B runs
-    if (kg == 0) kg = env_kg;
-    if (kg == 0) kg = 8;                                       // 256-channel groups, see conv_igemm.hip
-    if (KT == 1 || kg > CB || CB % kg != 0) kg = CB;
-    p.kgroup = kg;
-  }
+  static const int env_kg = env_int("EMP_CONV256_KGROUP", 0);   // A/B runs
+  p.kgroup = default_kgroup(p.KH * p.KW, p.Cin / KS, kg ? kg : env_kg);      // 256-channel groups, see conv_igemm.hip
   if (wpacked) {      // ConvParams::wgt is conv256_pack_weights' image, made for the walk group conv256_pack_kgroup returns
     EMP_REQUIRE(p.next_w == nullptr && p.kgroup == conv256_pack_kgroup(p.KH * p.KW, p.Cin), "conv256: packed weights need the default K walk");
     p.kgroup = -p.kgroup;
   }
-  static const int env_mode = [] { const char* e = getenv("EMP_CONV256_MODE"); return e ? atoi(e) : 0; }();
+  static const int env_mode = env_int("EMP_CONV256_MODE", 0);
   if (mode == 0) mode = env_mode;
-  p.mt = cdiv(p.M, 256);
-  p.nt = p.Cout / 256;
-  p.mt_per_xcd = cdiv(p.mt, 8);
+  const int grid = fill_raster(p, 256, 256);
   {
     // EMP_CONV256_NGROUP=g: the intermediate raster for the 1x1 convolutions with at least 2g cout tiles (A/B; the measured
     // outcome is in profiles/r06_conv_raster.txt)
-    static const int env_ng = [] { const char* e = getenv("EMP_CONV256_NGROUP"); return e ? atoi(e) : 0; }();
+    static const int env_ng = env_int("EMP_CONV256_NGROUP", 0);
     p.ngroup = (env_ng > 0 && p.KH * p.KW == 1 && p.nt >= 2 * env_ng && p.nt % env_ng == 0 && !p.next_w) ? env_ng : 0;
   }
-  const int grid = 8 * p.mt_per_xcd * p.nt;
   if (p.next_w) return launch256<0, true>(p, grid, stream);
   {
     // whole-line pixel fetches (conv_igemm256w_kernel): K-tile pairs need 64-channel granularity along the whole walk
-    static const bool wide_on = [] { const char* e = getenv("EMP_CONV256_WIDE"); return !(e && e[0] == '0'); }();      // A/B runs
+    static const bool wide_on = env_on("EMP_CONV256_WIDE");      // A/B runs
     const int kga = p.kgroup < 0 ? -p.kgroup : p.kgroup;
     const int ktot = p.KH * p.KW * (p.Cin / KS) + (p.in2 ? p.Cin2 / KS : 0);
     if (wide_on && mode == 0 && p.Cin % (2 * KS) == 0 && (!p.in2 || p.Cin2 % (2 * KS) == 0) && kga % 2 == 0 && ktot >= 8 &&
-        (int64_t)p.N * p.H * p.W < (1ll << 31)) {      // (its pixel indices are 32-bit)
-      if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(&conv_igemm256w_kernel), WIDE_LDS_BYTES)) return rc;
-      hipLaunchKernelGGL(conv_igemm256w_kernel, dim3(grid), dim3(512), WIDE_LDS_BYTES, stream, p);
-      EMP_LAUNCH_CHECK();
-      return EMP_OK;
-    }
+        (int64_t)p.N * p.H * p.W < (1ll << 31))      // (its pixel indices are 32-bit)
+      return launch_dyn(&conv_igemm256w_kernel, grid, 512, WIDE_LDS_BYTES, stream, p);
   }
   if (mode == 1) return launch256<2>(p, grid, stream);
   if (mode == 2) return launch256<4>(p, grid, stream);
@@ -1078,11 +929,8 @@ int launch_conv_igemm256(ConvParams p, hipStream_t stream, int kg, int mode, boo
 
 // the K-walk group (32-channel slabs) launch_conv_igemm256 takes by default: the packed image is laid out along it
 int conv256_pack_kgroup(int KT, int Cin) {
-  const int CB = Cin / KS;
-  static const int env_kg = [] { const char* e = getenv("EMP_CONV256_KGROUP"); return e ? atoi(e) : 0; }();
-  int kg = env_kg ? env_kg : 8;
-  if (KT == 1 || kg > CB || CB % kg != 0) kg = CB;
-  return kg;
+  static const int env_kg = env_int("EMP_CONV256_KGROUP", 0);
+  return default_kgroup(KT, Cin / KS, env_kg);
 }
 // w: [Cout][KT * Cin + Cin2] halfs -> out: the same number of halfs as a packed image (Cout % 256 == 0, Cin, Cin2 % 32 == 0)
 int conv256_pack_weights(const half_t* w, half_t* out, int Cout, int KT, int Cin, int Cin2, hipStream_t stream) {
@@ -1103,22 +951,13 @@ bool conv_igemm_h256_supported(const ConvParams& p) {
 template <int PXR, int COR>
 static int launch_h256(ConvParams p, hipStream_t stream) {
   constexpr int LDS_BYTES = 3 * (PXR + COR) * 64;
-  if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(&conv_igemm_h256_kernel<PXR, COR>), LDS_BYTES)) return rc;
-  p.mt = cdiv(p.M, PXR);
-  p.nt = p.Cout / COR;
-  p.mt_per_xcd = cdiv(p.mt, 8);
-  const int grid = 8 * p.mt_per_xcd * p.nt;
-  hipLaunchKernelGGL((conv_igemm_h256_kernel<PXR, COR>), dim3(grid), dim3(256), LDS_BYTES, stream, p);
-  EMP_LAUNCH_CHECK();
-  return EMP_OK;
+  const int grid = fill_raster(p, PXR, COR);
+  return launch_dyn(&conv_igemm_h256_kernel<PXR, COR>, grid, 256, LDS_BYTES, stream, p);
 }
 
 int launch_conv_igemm_h256(ConvParams p, hipStream_t stream, int kg) {
   EMP_REQUIRE(conv_igemm_h256_supported(p), "conv h256: unsupported shape (Cout=%d)", p.Cout);
-  const int CB = p.Cin / KS, KT = p.KH * p.KW;
-  if (kg == 0) kg = 8;
-  if (KT == 1 || kg > CB || CB % kg != 0) kg = CB;
-  p.kgroup = kg;
+  p.kgroup = default_kgroup(p.KH * p.KW, p.Cin / KS, kg);
   if (p.Cout % 256 == 0) return launch_h256<128, 256>(p, stream);
   return launch_h256<256, 128>(p, stream);
 }

@@ -8,7 +8,7 @@
 // ahead (64 KiB in flight per workgroup), one LDS-only barrier per pair (64 channels), counted vmcnt.  4 waves, wave tile 32 pixels x 32 couts
 // (4 MFMAs and 4 fragment reads per K-tile).  K order, operands and epilogue arithmetic are those of the other conv
 // kernels: bit-identical results (tests/test_gpu_conv.py), so a batch of N still equals N batch-1 calls.
-#include "common.h"
+#include "igemm_common.h"
 
 #include <type_traits>
 
@@ -20,25 +20,11 @@ constexpr int SKS = 32;                   // channels per K-tile
 constexpr int S_SLOT = 128 * 64;          // 64 pixel rows + 64 cout rows
 constexpr int S_WOFF = 64 * 64;
 
-__device__ __forceinline__ int s_perm32(int x) {
-  const int t = x >> 4, i = x & 15;
-  return ((i >> 2) << 3) + (t << 2) + (i & 3);
-}
-template <int ACT>
-__device__ __forceinline__ float s_act(float x) {
-  if (ACT == 1) return fmaxf(x, 0.f);
-  if (ACT == 2) return x / (1.f + __expf(-x));
-  return x;
-}
-
 template <int NS>
 __global__ void __launch_bounds__(256, 2) conv_igemm_s64_kernel(const ConvParams p) {
   extern __shared__ __attribute__((aligned(1024))) char lds[];
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, j = bid >> 3;
-  const int mtile = xcd * p.mt_per_xcd + j / p.nt;
-  const int ntile = j % p.nt;
-  if (mtile >= p.mt) return;
+  int mtile, ntile;
+  if (!tile_of_block(blockIdx.x, p.mt, p.nt, p.mt_per_xcd, 0, mtile, ntile)) return;
   const int m0 = mtile * 64, n0 = ntile * 64;
 
   const int tid = threadIdx.x, l = tid & 63;
@@ -54,7 +40,7 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_s64_kernel(const ConvParams
 
   // staging: wave w moves pixel piece w and cout piece w (16 rows x 64 B each)
   const int srow = l >> 2;
-  const int schunk = (l & 3) ^ ((-(l >> 4)) & 3);
+  const int schunk = stage_chunk64(l);
   const half_t* a_img = p.in;
   int a_iy0 = -(1 << 28), a_ix0 = -(1 << 28);
   const half_t* a_cur = p.zero;
@@ -83,7 +69,7 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_s64_kernel(const ConvParams
   int b_inc;
   {
     const int row = wave * 16 + srow;
-    const int co = n0 + (row & ~31) + s_perm32(row & 31);
+    const int co = n0 + (row & ~31) + perm32(row & 31);
     const bool ok = co < p.Cout;
     b_base = b_cur = ok ? p.wgt + (size_t)co * (KT * p.Cin + (p.in2 ? p.Cin2 : 0)) + schunk * 8 : p.zero;
     b_inc = ok ? SKS : 0;
@@ -93,10 +79,8 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_s64_kernel(const ConvParams
   // (the second half of the last pair when the tile count is odd) copy the zero page: 0 x 0 leaves the sums untouched
   auto stage = [&](char* dst) {
     if (st_u >= KTOT) {
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)p.zero,
-                                       (__attribute__((address_space(3))) void*)(dst + wave * 1024), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)p.zero,
-                                       (__attribute__((address_space(3))) void*)(dst + S_WOFF + wave * 1024), 16, 0, 0);
+      lds_dma16(p.zero, dst + wave * 1024);
+      lds_dma16(p.zero, dst + S_WOFF + wave * 1024);
       ++st_u;
       return;
     }
@@ -114,10 +98,8 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_s64_kernel(const ConvParams
       }
       if (KG != CB) b_cur = b_inc ? b_base + (st_ky * p.KW + st_kx) * p.Cin + c0 : b_base;
     }
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)a_cur,
-                                     (__attribute__((address_space(3))) void*)(dst + wave * 1024), 16, 0, 0);
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)b_cur,
-                                     (__attribute__((address_space(3))) void*)(dst + S_WOFF + wave * 1024), 16, 0, 0);
+    lds_dma16(a_cur, dst + wave * 1024);
+    lds_dma16(b_cur, dst + S_WOFF + wave * 1024);
     a_cur += a_inc;
     b_cur += b_inc;
     if (++st_cb == KG) {
@@ -156,7 +138,7 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_s64_kernel(const ConvParams
   for (int u = 0; u < npro; ++u) stage_pair();
   if (npro == NS - 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(4 * (NS - 2)) : "memory");
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  lds_barrier();
 
   for (int t = 0; t < NPAIR; ++t) {
     const char* base = lds + (t % NS) * (2 * S_SLOT);
@@ -224,7 +206,7 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_s64_kernel(const ConvParams
       }
       f16x8 o;
 #pragma unroll
-      for (int r = 0; r < 8; ++r) o[r] = (half_t)s_act<ACT>(v[r]);
+      for (int r = 0; r < 8; ++r) o[r] = (half_t)conv_act<ACT>(v[r]);
       *reinterpret_cast<f16x8*>(p.out + (size_t)m * p.out_ld + co) = o;
     }
   };
@@ -244,18 +226,9 @@ bool conv_igemm_s64_supported(const ConvParams& p) {
 int launch_conv_igemm_s64(ConvParams p, hipStream_t stream, int kg) {
   EMP_REQUIRE(conv_igemm_s64_supported(p), "conv s64: unsupported shape (Cin=%d Cout=%d)", p.Cin, p.Cout);
   constexpr int NS = 5;      // ring of 5 pairs of K-tiles = 80 KiB: 4 pairs (64 KiB) in flight, two workgroups per CU
-  const int CB = p.Cin / SKS, KT = p.KH * p.KW;
-  if (kg == 0) kg = 8;
-  if (KT == 1 || kg > CB || CB % kg != 0) kg = CB;
-  p.kgroup = kg;
-  if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(&conv_igemm_s64_kernel<NS>), NS * 2 * S_SLOT)) return rc;
-  p.mt = cdiv(p.M, 64);
-  p.nt = cdiv(p.Cout, 64);
-  p.mt_per_xcd = cdiv(p.mt, 8);
-  const int grid = 8 * p.mt_per_xcd * p.nt;
-  hipLaunchKernelGGL(conv_igemm_s64_kernel<NS>, dim3(grid), dim3(256), NS * 2 * S_SLOT, stream, p);
-  EMP_LAUNCH_CHECK();
-  return EMP_OK;
+  p.kgroup = default_kgroup(p.KH * p.KW, p.Cin / SKS, kg);
+  const int grid = fill_raster(p, 64, 64);
+  return launch_dyn(&conv_igemm_s64_kernel<NS>, grid, 256, NS * 2 * S_SLOT, stream, p);
 }
 
 }  // namespace emp

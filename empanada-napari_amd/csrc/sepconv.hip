@@ -263,8 +263,8 @@ __global__ void __launch_bounds__(64 * (NDW + NMW), 1) sepconv5_kernel(const Sep
               f16x8 o;
 #pragma unroll
               for (int e = 0; e < 4; ++e) {
-                o[e] = (half_t)sc_act<ACT>(acc[2 * blk][nt][e] + bv[e]);
-                o[4 + e] = (half_t)sc_act<ACT>(acc[2 * blk + 1][nt][e] + bv[4 + e]);
+                o[e] = (half_t)conv_act<ACT>(acc[2 * blk][nt][e] + bv[e]);
+                o[4 + e] = (half_t)conv_act<ACT>(acc[2 * blk + 1][nt][e] + bv[4 + e]);
               }
               const int oy = y0 + nt;
               if (oy < p.H && ox < p.W)
@@ -282,8 +282,8 @@ __global__ void __launch_bounds__(64 * (NDW + NMW), 1) sepconv5_kernel(const Sep
             for (int nt = 0; nt < 8; ++nt)
 #pragma unroll
               for (int e = 0; e < 4; ++e) {
-                acc[2 * blk][nt][e] = sc_act<ACT>(acc[2 * blk][nt][e] + bv[e]);
-                acc[2 * blk + 1][nt][e] = sc_act<ACT>(acc[2 * blk + 1][nt][e] + bv[4 + e]);
+                acc[2 * blk][nt][e] = conv_act<ACT>(acc[2 * blk][nt][e] + bv[e]);
+                acc[2 * blk + 1][nt][e] = conv_act<ACT>(acc[2 * blk + 1][nt][e] + bv[4 + e]);
               }
           }
 #pragma unroll 1

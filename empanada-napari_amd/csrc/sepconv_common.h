@@ -10,7 +10,7 @@
 #pragma once
 #include <type_traits>
 
-#include "common.h"
+#include "igemm_common.h"
 
 namespace emp {
 
@@ -48,13 +48,6 @@ struct SepParams {
   int64_t plane;
 };
 
-template <int ACT>
-__device__ __forceinline__ float sc_act(float x) {
-  if (ACT == 1) return fmaxf(x, 0.f);
-  if (ACT == 2) return x / (1.f + __expf(-x));
-  return x;
-}
-
 __device__ __forceinline__ void tile_coords(int tiles_x, int tiles_y, int tile, int& n, int& y0, int& x0) {
   const int tx = tile % tiles_x;
   const int r = tile / tiles_x;
@@ -62,14 +55,6 @@ __device__ __forceinline__ void tile_coords(int tiles_x, int tiles_y, int tile, 
   n = r / tiles_y;
   y0 = ty * SC_TH;
   x0 = tx * SC_TW;
-}
-
-// workgroup barrier that orders LDS traffic only: global loads / LDS-DMA stay in flight across it
-__device__ __forceinline__ void lds_barrier() {
-  // Raw barrier that orders LDS traffic only.  A fence (or __syncthreads) would also drain vmcnt: an in-flight
-  // LDS-DMA is a pending LDS write on the VM counter.  The "memory" clobber keeps the compiler from moving
-  // memory accesses across it; DMA completion is handled by the counted vmcnt waits of the issuing waves.
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
 // fp32 pair -> fp16 hi pair + fp16 lo pair with x == hi + lo to 21 bits: hi = rtz(x), lo = rtz(x - hi) (the residual is

@@ -327,8 +327,8 @@ __global__ void __launch_bounds__(64 * (SC_NDW + SC_NMW), 1) sepconvp_kernel(con
               f16x8 o;
 #pragma unroll
               for (int e = 0; e < 4; ++e) {
-                o[e] = (half_t)sc_act<ACT>(acc[2 * blk][nt][e]);
-                o[4 + e] = (half_t)sc_act<ACT>(acc[2 * blk + 1][nt][e]);
+                o[e] = (half_t)conv_act<ACT>(acc[2 * blk][nt][e]);
+                o[4 + e] = (half_t)conv_act<ACT>(acc[2 * blk + 1][nt][e]);
               }
               const int oy = y0 + nt;
               if (oy < p.H && ox < p.W)
@@ -341,7 +341,7 @@ __global__ void __launch_bounds__(64 * (SC_NDW + SC_NMW), 1) sepconvp_kernel(con
 #pragma unroll
             for (int nt = 0; nt < 8; ++nt)
 #pragma unroll
-              for (int e = 0; e < 4; ++e) acc[t][nt][e] = sc_act<ACT>(acc[t][nt][e]);
+              for (int e = 0; e < 4; ++e) acc[t][nt][e] = conv_act<ACT>(acc[t][nt][e]);
 #pragma unroll 1
           for (int h = 0; h < p.hc; ++h) {
             float sum[8];

@@ -247,10 +247,10 @@ __global__ void __launch_bounds__(64 * (SC_NDW + SC_NMW), 1) sepconv_x3_kernel(c
               const int oy = y0 + nt;
               if (oy < p.H && ox < p.W) {
                 float* op = p.out + (((size_t)n * p.H + oy) * p.W + ox) * p.out_ld + cb;
-                *reinterpret_cast<float4*>(op) = make_float4(sc_act<ACT>(acc[2 * blk][nt][0]), sc_act<ACT>(acc[2 * blk][nt][1]),
-                                                             sc_act<ACT>(acc[2 * blk][nt][2]), sc_act<ACT>(acc[2 * blk][nt][3]));
-                *reinterpret_cast<float4*>(op + 4) = make_float4(sc_act<ACT>(acc[2 * blk + 1][nt][0]), sc_act<ACT>(acc[2 * blk + 1][nt][1]),
-                                                                 sc_act<ACT>(acc[2 * blk + 1][nt][2]), sc_act<ACT>(acc[2 * blk + 1][nt][3]));
+                *reinterpret_cast<float4*>(op) = make_float4(conv_act<ACT>(acc[2 * blk][nt][0]), conv_act<ACT>(acc[2 * blk][nt][1]),
+                                                             conv_act<ACT>(acc[2 * blk][nt][2]), conv_act<ACT>(acc[2 * blk][nt][3]));
+                *reinterpret_cast<float4*>(op + 4) = make_float4(conv_act<ACT>(acc[2 * blk + 1][nt][0]), conv_act<ACT>(acc[2 * blk + 1][nt][1]),
+                                                                 conv_act<ACT>(acc[2 * blk + 1][nt][2]), conv_act<ACT>(acc[2 * blk + 1][nt][3]));
               }
             }
           }
@@ -260,7 +260,7 @@ __global__ void __launch_bounds__(64 * (SC_NDW + SC_NMW), 1) sepconv_x3_kernel(c
 #pragma unroll
             for (int nt = 0; nt < 8; ++nt)
 #pragma unroll
-              for (int e = 0; e < 4; ++e) acc[t][nt][e] = sc_act<ACT>(acc[t][nt][e]);
+              for (int e = 0; e < 4; ++e) acc[t][nt][e] = conv_act<ACT>(acc[t][nt][e]);
 #pragma unroll 1
           for (int h = 0; h < p.hc; ++h) {
             float sum[8];
