@@ -7,6 +7,8 @@
 #include <array>
 #include <map>
 #include <memory>
+#include <new>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -37,6 +39,53 @@ struct DevConv {  // packed conv weights
 
 inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
 
+// ---- the topology, written once: every walk over the encoder (parameter list, packers, arena plan, both schedules) reads these ----
+const int kLayers[4] = {3, 4, 6, 3};
+const int kPlanes[4] = {64, 128, 256, 512};
+const char* const kDecoders[2] = {"semantic_decoder", "instance_decoder"};
+const char* const kHeads[3] = {"semantic_head", "ins_center", "ins_xy"};
+const char* const kBifpn[2] = {"semantic", "instance"};      // "<kBifpn>_fpn", "<kBifpn>_decoder"
+
+// ResNet50 bottleneck b of layer li (resnet.py:217-229): "encoder.layer<li>.<b>"
+struct ResBlock {
+  int li, b, stride, dil, planes;      // stride: of this block's conv2 and shortcut (the layer's at b == 0, else 1); dil: the layer's
+  bool last;                           // last block of its layer: its output is a pyramid level
+  std::string name, next;              // next: the block that follows (the next layer's first one included), empty after the last
+};
+
+inline std::vector<ResBlock> resnet_blocks(const emp_pdl_config& c) {
+  std::vector<ResBlock> v;
+  for (int li = 1; li <= 4; ++li) {
+    int stride = li == 1 ? 1 : 2, dil = 1;
+    if (li == 4 && c.stage4_stride == 16) { stride = 1; dil = 2; }
+    for (int b = 0; b < kLayers[li - 1]; ++b)
+      v.push_back({li, b, b == 0 ? stride : 1, dil, kPlanes[li - 1], b + 1 == kLayers[li - 1],
+                   "encoder.layer" + std::to_string(li) + "." + std::to_string(b), ""});
+  }
+  for (size_t i = 0; i + 1 < v.size(); ++i) v[i].next = v[i + 1].name;
+  return v;
+}
+
+// RegNet block b (1-based) of stage si (1-based) (regnet.py:51-97): "encoder.stage<si>.block<b>"
+struct RegBlock {
+  int si, b, stride, width, groups;
+  bool shortcut;      // the block carries a shortcut convolution
+  bool last;          // last block of its stage: its output is a pyramid level
+  std::string name;
+};
+
+inline std::vector<RegBlock> regnet_blocks(const emp_pdl_config& c) {
+  std::vector<RegBlock> v;
+  for (int si = 1; si <= 4; ++si)
+    for (int b = 1; b <= c.rn_depths[si - 1]; ++b) {
+      const int w_in = si == 1 ? c.rn_stem : c.rn_widths[si - 2];
+      v.push_back({si, b, b == 1 ? c.rn_strides[si - 1] : 1, c.rn_widths[si - 1], c.rn_groups[si - 1],
+                   b == 1 && (w_in != c.rn_widths[si - 1] || c.rn_strides[si - 1] > 1), b == c.rn_depths[si - 1],
+                   "encoder.stage" + std::to_string(si) + ".block" + std::to_string(b)});
+    }
+  return v;
+}
+
 }  // namespace emp
 
 using namespace emp;
@@ -44,6 +93,8 @@ using namespace emp;
 struct emp_pdl {
   emp_pdl_config cfg;
   int aspp_ch = 256, dec_ch = 256, ncls = 1;
+  std::vector<ResBlock> res_blocks;      // the encoder's blocks in order (emp_pdl_create): one of the two lists is empty
+  std::vector<RegBlock> reg_blocks;
   std::vector<std::string> param_names;
   std::map<std::string, HostParam> params;
   bool finalized = false;
@@ -178,20 +229,15 @@ struct emp_pdl {
 
 namespace emp {
 
-const int kLayers[4] = {3, 4, 6, 3};
-const int kPlanes[4] = {64, 128, 256, 512};
-
-// RegNet block (regnet.py:51-97): does block b (1-based) of stage si (1-based) carry a shortcut convolution?
-inline bool regnet_has_shortcut(const emp_pdl_config& c, int si, int b) {
-  if (b > 1) return false;
-  const int w_in = si == 1 ? c.rn_stem : c.rn_widths[si - 2];
-  return w_in != c.rn_widths[si - 1] || c.rn_strides[si - 1] > 1;
-}
+inline int head_planes(const emp_pdl* n, int k) { return k == 0 ? n->ncls : k; }      // output planes of kHeads[k]: ncls, 1, 2
 
 enum { ACT_NONE, ACT_RELU, ACT_SILU };      // ConvParams::act / Conv32::act
 
 // defined in pdl_net.hip
 int dev_upload(emp_pdl* n, const void* h, size_t bytes, void** out);
+int upload_heads_f32(emp_pdl* n);
+void split_aspp_project(const HostParam& hp, int A, HostParam* head, std::vector<float>* tail);
+std::vector<float> padded_predictor(const HostParam& hp, int ncls, int ldp);
 int upload_f32(emp_pdl* n, const std::string& key, const std::vector<float>& v);
 int upload_regnet_stem(emp_pdl* n);
 // defined in pdl_net32.hip
@@ -222,4 +268,102 @@ int profiled_launch(emp_pdl* n, hipStream_t s, double flops, Launch launch) {
   EMP_CHECK_HIP(hipEventRecord(ev.second, s));
   n->prof_flops += flops;
   return rc;
+}
+
+// One forward's arguments and what the stages of either schedule hand on: the pyramid's maps (index 0: the stem / p1 map), the
+// decoders' outputs and the heads' buffers, by name
+struct Forward {
+  emp_pdl* n;
+  const emp_pdl_config& c;
+  const void* img;
+  int dtype;
+  float sub, mul;
+  int N, H, W, vh, vw, RS, interp;
+  float *o_sem, *o_ctr, *o_off;
+  hipStream_t s;
+  std::string pyr[5], dec_out[2];
+  float* head_out[3] = {nullptr, nullptr, nullptr};
+};
+
+// device memory the network owns (freed with it), uninitialised: count elements of T
+template <typename T>
+int dev_alloc(emp_pdl* n, size_t count, T** out) {
+  void* d = nullptr;
+  EMP_CHECK_HIP(hipMalloc(&d, count * sizeof(T)));
+  n->owned.push_back(d);
+  *out = (T*)d;
+  return EMP_OK;
+}
+
+// conv3 and the projection shortcut of a bottleneck as one weight matrix [Cout][cin3 | cin_ds], either K range padded to a multiple
+// of `pad` channels, with the summed (folded BN) bias: relu(conv3(c2) + downsample(x)) becomes a single GEMM over the concatenated
+// K (ConvParams::in2 / Conv32::in2).  T: half_t (fp16 engine) or float (fp16x3 mode)
+template <typename T>
+int concat_conv3_ds(emp_pdl* n, const std::string& block, int pad, int* cout, int* cin, int* cin_pad, int* cin2, int* cin2_pad,
+                    std::vector<T>* pk, std::vector<float>* b) {
+  const HostParam& h3 = n->params.at(block + ".conv3");
+  const HostParam& hd = n->params.at(block + ".downsample.0");
+  EMP_REQUIRE(h3.shape.size() == 4 && hd.shape.size() == 4 && h3.shape[0] == hd.shape[0] && h3.shape[2] == 1 &&
+                  hd.shape[2] == 1 && h3.b.size() == hd.b.size(), "%s: conv3 / downsample shapes do not match", block.c_str());
+  *cout = (int)h3.shape[0];
+  *cin = (int)h3.shape[1];
+  *cin_pad = round_up(*cin, pad);
+  *cin2 = (int)hd.shape[1];
+  *cin2_pad = round_up(*cin2, pad);
+  const size_t K = (size_t)*cin_pad + *cin2_pad;
+  pk->assign((size_t)*cout * K, (T)0.f);
+  b->resize((size_t)*cout);
+  for (int o = 0; o < *cout; ++o) {
+    for (int i = 0; i < *cin; ++i) (*pk)[o * K + i] = (T)h3.w[(size_t)o * *cin + i];
+    for (int i = 0; i < *cin2; ++i) (*pk)[o * K + *cin_pad + i] = (T)hd.w[(size_t)o * *cin2 + i];
+    (*b)[o] = h3.b[o] + hd.b[o];
+  }
+  return EMP_OK;
+}
+
+// An extern "C" entry's body: no exception (a map's .at() on a name two walks disagree on, bad_alloc) crosses the boundary
+template <typename Body>
+int guarded(const char* entry, Body body) {
+  try {
+    return body();
+  } catch (const std::bad_alloc&) {
+    set_error("%s: out of host memory", entry);
+    return EMP_ERR_NOMEM;
+  } catch (const std::exception& e) {
+    set_error("%s: %s", entry, e.what());
+    return EMP_ERR_STATE;
+  }
+}
+
+// One BiFPN layer (bifpn.py:47-69, 103-137), shared by both schedules: top-down P7 -> P3, then bottom-up P3' -> P7, on the maps
+// feat[lv] (level index lv: 0 = P3 .. 4 = P7), which leave as the layer's outputs.  pre: the layer's parameter prefix, L: its maps'.
+//   resample(rk, src, dst, &name): if the resampling conv rk exists, run it from map src into map dst; name = the map to read
+//   node(dirpre, q, a, b, c, ca, cb, cc, mode, out): ca * a + cb * b [+ cc * c; c may be empty] and the node's separable block into
+//   map out (mode 1: a bottom-up node)
+template <typename Resample, typename Node>
+int bifpn_layer(const emp_pdl* n, const std::string& pre, const std::string& L, std::string feat[5], Resample resample, Node node) {
+  std::string newfeat[5];
+  for (int up = 0; up < 2; ++up) {
+    const std::string dp = pre + (up ? ".bottom_up_fpn" : ".top_down_fpn");
+    const float* w = n->fusew.at(dp + ".weights").data();
+    std::string prev = up ? L + ".P3.td" : feat[4];
+    if (up) newfeat[0] = prev;
+    for (int i = 0; i < 4; ++i) {
+      const int lv = up ? i + 1 : 3 - i;
+      const std::string q = L + ".P" + std::to_string(3 + lv), out = q + (up ? ".bu" : ".td");
+      std::string in;
+      RC(resample(dp + ".resamplings." + std::to_string(i) + ".conv.0", feat[lv], q + (up ? ".rbu" : ".rtd"), &in));
+      if (up && i < 3) {
+        const float den = w[i] + w[i + 1] + w[i + 2] + 1e-4f;
+        RC(node(dp, q, prev, in, q + ".td", w[i] / den, w[i + 1] / den, w[i + 2] / den, 1, out));
+      } else {
+        const float den = w[i] + w[i + 1] + 1e-4f;
+        RC(node(dp, q, prev, in, std::string(), w[i] / den, w[i + 1] / den, 0.f, up, out));
+      }
+      prev = out;
+      if (up) newfeat[lv] = prev;
+    }
+  }
+  for (int lv = 0; lv < 5; ++lv) feat[lv] = newfeat[lv];
+  return EMP_OK;
 }

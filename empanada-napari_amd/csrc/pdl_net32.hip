@@ -36,6 +36,14 @@ int t32(emp_pdl* n, const std::string& key, int N, int H, int W, int C, T32* t) 
   return buf32(n, key, (size_t)N * H * W * C, &t->p);
 }
 
+// packed weights and bias to the device, the conv under its name
+int store32(emp_pdl* n, const std::string& name, emp_pdl::W32 w, const std::vector<float>& pk, const std::vector<float>& b) {
+  RC(dev_upload(n, pk.data(), pk.size() * sizeof(float), (void**)&w.w));
+  RC(dev_upload(n, b.data(), b.size() * sizeof(float), (void**)&w.b));
+  n->w32[name] = w;
+  return EMP_OK;
+}
+
 // OIHW / OIW fp32 -> [O][KH*KW][I16] fp32 (+ bias); cin_to: pad the input channels to this many (PointRend rows)
 int pack32(emp_pdl* n, const std::string& name, int cin_to = 0, const HostParam* src = nullptr) {
   const HostParam& hp = src ? *src : n->params.at(name);
@@ -52,47 +60,17 @@ int pack32(emp_pdl* n, const std::string& name, int cin_to = 0, const HostParam*
   for (int o = 0; o < w.cout; ++o)
     for (int i = 0; i < w.cin; ++i)
       for (int t = 0; t < kt; ++t) pk[((size_t)o * kt + t) * w.cin16 + i] = hp.w[((size_t)o * w.cin + i) * kt + t];
-  void* d;
-  int rc = dev_upload(n, pk.data(), pk.size() * sizeof(float), &d);
-  if (rc) return rc;
-  w.w = (float*)d;
-  rc = dev_upload(n, hp.b.data(), hp.b.size() * sizeof(float), &d);
-  if (rc) return rc;
-  w.b = (float*)d;
-  n->w32[name] = w;
-  return EMP_OK;
+  return store32(n, name, w, pk, hp.b);
 }
 
 // fp16x3 mode: conv3 and the projection shortcut of a bottleneck as one fp32 weight matrix [Cout][cin3_16 | cin_ds_16] with
 // the summed (folded BN) bias -- relu(conv3(c2) + downsample(x)) as a single convolution over the concatenated K
 // (Conv32::in2; the fp16 engine's pack_conv3_ds): the shortcut map is neither written nor read back
 int pack32_conv3_ds(emp_pdl* n, const std::string& block) {
-  const HostParam& h3 = n->params.at(block + ".conv3");
-  const HostParam& hd = n->params.at(block + ".downsample.0");
-  EMP_REQUIRE(h3.shape.size() == 4 && hd.shape.size() == 4 && h3.shape[0] == hd.shape[0] && h3.shape[2] == 1 && hd.shape[2] == 1 &&
-                  h3.b.size() == hd.b.size(), "%s: conv3 / downsample shapes do not match", block.c_str());
   emp_pdl::W32 w;
-  w.cout = (int)h3.shape[0];
-  w.cin = (int)h3.shape[1];
-  w.cin16 = round_up(w.cin, 16);
-  w.cin2 = (int)hd.shape[1];
-  w.cin2_16 = round_up(w.cin2, 16);
-  const size_t K = (size_t)w.cin16 + w.cin2_16;
-  std::vector<float> pk((size_t)w.cout * K, 0.f), b((size_t)w.cout);
-  for (int o = 0; o < w.cout; ++o) {
-    for (int i = 0; i < w.cin; ++i) pk[o * K + i] = h3.w[(size_t)o * w.cin + i];
-    for (int i = 0; i < w.cin2; ++i) pk[o * K + w.cin16 + i] = hd.w[(size_t)o * w.cin2 + i];
-    b[o] = h3.b[o] + hd.b[o];
-  }
-  void* d;
-  int rc = dev_upload(n, pk.data(), pk.size() * sizeof(float), &d);
-  if (rc) return rc;
-  w.w = (float*)d;
-  rc = dev_upload(n, b.data(), b.size() * sizeof(float), &d);
-  if (rc) return rc;
-  w.b = (float*)d;
-  n->w32[block + ".conv3+ds"] = w;
-  return EMP_OK;
+  std::vector<float> pk, b;
+  RC(concat_conv3_ds(n, block, 16, &w.cout, &w.cin, &w.cin16, &w.cin2, &w.cin2_16, &pk, &b));
+  return store32(n, block + ".conv3+ds", w, pk, b);
 }
 
 // depthwise (C,1,k,k) -> [k*k][C] fp32
@@ -128,18 +106,196 @@ int stack32(emp_pdl* n, const emp_pdl::W32& wa, const emp_pdl::W32& wb, emp_pdl:
   *m = wa;
   m->cout = wa.cout + wb.cout; m->wp = nullptr; m->wimg = nullptr; m->wimgp = nullptr;
   const size_t K = (size_t)wa.kh * wa.kw * wa.cin16, na = (size_t)wa.cout * K, nb = (size_t)wb.cout * K;
-  void* d = nullptr;
-  EMP_CHECK_HIP(hipMalloc(&d, (na + nb) * sizeof(float)));
-  n->owned.push_back(d);
-  m->w = (float*)d;
+  RC(dev_alloc(n, na + nb, &m->w));
   EMP_CHECK_HIP(hipMemcpy(m->w, wa.w, na * sizeof(float), hipMemcpyDeviceToDevice));
   EMP_CHECK_HIP(hipMemcpy(m->w + na, wb.w, nb * sizeof(float), hipMemcpyDeviceToDevice));
-  EMP_CHECK_HIP(hipMalloc(&d, (size_t)m->cout * sizeof(float)));
-  n->owned.push_back(d);
-  m->b = (float*)d;
+  RC(dev_alloc(n, (size_t)m->cout, &m->b));
   EMP_CHECK_HIP(hipMemcpy(m->b, wa.b, (size_t)wa.cout * sizeof(float), hipMemcpyDeviceToDevice));
   EMP_CHECK_HIP(hipMemcpy(m->b + wa.cout, wb.b, (size_t)wb.cout * sizeof(float), hipMemcpyDeviceToDevice));
   return EMP_OK;
+}
+
+// ---- finalize32's stages ----
+
+int pack32_encoder(emp_pdl* n) {
+  const emp_pdl_config& c = n->cfg;
+  if (c.encoder == 1) RC(upload_regnet_stem(n));
+  for (const RegBlock& k : n->reg_blocks) {
+    const std::string& p = k.name;
+    const int w = k.width, g = k.groups;
+    RC(pack32(n, p + ".bottleneck.a.0"));
+    RC(pack32(n, p + ".bottleneck.b.0"));      // (w, w / g, 3, 3): rows [o][tap][(w / g) padded to 16], group-major in o
+    const emp_pdl::W32& wb = n->w32.at(p + ".bottleneck.b.0");
+    EMP_REQUIRE(wb.cout == w && wb.cin * g == w && wb.kh == 3 && wb.kw == 3, "%s.bottleneck.b.0 must be (%d,%d,3,3)", p.c_str(), w,
+                w / g);
+    if (c.rn_se) {
+      RC(pack32(n, p + ".bottleneck.se.se.0"));
+      RC(pack32(n, p + ".bottleneck.se.se.2"));
+    }
+    RC(pack32(n, p + ".bottleneck.c.0"));
+    if (k.shortcut) RC(pack32(n, p + ".downsample.conv.0"));
+  }
+  for (const ResBlock& k : n->res_blocks) {
+    const std::string& p = k.name;
+    RC(pack32(n, p + ".conv1"));
+    RC(pack32(n, p + ".conv2"));
+    RC(pack32(n, p + ".conv3"));
+    if (k.b == 0) RC(pack32(n, p + ".downsample.0"));
+    if (k.b == 0 && n->precision == 2) RC(pack32_conv3_ds(n, p));
+  }
+  return EMP_OK;
+}
+
+int pack32_bifpn(emp_pdl* n) {
+  RC(pack32(n, "p2_resample.conv.0"));
+  for (const auto& nm : n->param_names) {
+    const bool fpn = nm.find("_fpn.") != std::string::npos, dec = nm.find("_decoder.") != std::string::npos;
+    if (!fpn && !dec) continue;
+    if (nm.size() > 8 && nm.compare(nm.size() - 8, 8, ".weights") == 0) continue;      // fusew: host side (finalize)
+    if (nm.find(".sepconv.0") != std::string::npos) RC(pack32_dw(n, nm, (int)n->params[nm].shape[0]));
+    else if (nm.find(".upsamplings.") != std::string::npos) RC(pack32_convT(n, nm));
+    else RC(pack32(n, nm));
+  }
+  return EMP_OK;
+}
+
+int pack32_deeplab(emp_pdl* n) {
+  const emp_pdl_config& c = n->cfg;
+  for (int d = 0; d < (c.ins_decoder ? 2 : 1); ++d) {
+    const std::string p = kDecoders[d];
+    for (int i = 0; i <= 3; ++i) RC(pack32(n, p + ".aspp.convs." + std::to_string(i) + ".0"));
+    // projection: first 4A input channels -> conv; the pooled branch's A channels -> per-image bias (projpool.w)
+    HostParam head;
+    std::vector<float> tail;
+    split_aspp_project(n->params[p + ".aspp.project.0"], n->aspp_ch, &head, &tail);
+    RC(pack32(n, p + ".aspp.project.0", 0, &head));
+    int xch = n->aspp_ch;
+    for (int i = 0; i < c.n_stages; ++i) {
+      const int lp = d == 0 ? c.low_level_proj_sem[i] : c.low_level_proj_ins[i];
+      RC(pack32(n, p + ".project." + std::to_string(i) + ".0"));
+      const int cpad = round_up(xch + lp, n->precision == 2 ? 32 : 16);      // (the fused block walks the channels in chunks of 32)
+      RC(pack32_dw(n, p + ".fuse." + std::to_string(i) + ".0.sepconv.0", cpad));
+      RC(pack32(n, p + ".fuse." + std::to_string(i) + ".0.sepconv.1", cpad));
+      xch = n->dec_ch;
+    }
+  }
+  return EMP_OK;
+}
+
+int pack32_heads_pointrend(emp_pdl* n) {
+  for (int k = 0; k < 3; ++k) {
+    const std::string p = kHeads[k];
+    RC(pack32_dw(n, p + ".head.0.0.sepconv.0", n->dec_ch));
+    RC(pack32(n, p + ".head.0.0.sepconv.1"));
+  }
+  const int ldp = round_up(n->dec_ch + n->ncls, 16);
+  for (int k = 0; k < n->cfg.num_fc; ++k) RC(pack32(n, "semantic_pr.point_head.fc_layers." + std::to_string(k) + ".0", ldp));
+  return upload_f32(n, "pr.predictor.w32", padded_predictor(n->params["semantic_pr.point_head.predictor"], n->ncls, ldp));
+}
+
+// fp16x3 mode, round 6: the separable blocks' weights in the fused kernel's orders (sepconv_x3.hip)
+int x3_sep_weights(emp_pdl* n) {
+  for (auto& kv : n->w32) {
+    const std::string& nm = kv.first;
+    if (nm.size() < 10 || nm.compare(nm.size() - 10, 10, ".sepconv.1") != 0) continue;
+    const std::string base = nm.substr(0, nm.size() - 2);      // "... .sepconv"
+    auto dwi = n->f32w.find(base + ".0.dw32");
+    auto hpi = n->params.find(base + ".0");
+    if (dwi == n->f32w.end() || hpi == n->params.end() || hpi->second.shape.size() != 4) continue;
+    const emp_pdl::W32& w = kv.second;
+    const int ks = (int)hpi->second.shape[2], C = w.cin16;
+    if (w.kh != 1 || w.kw != 1 || !sepconv_x3_supported(C, w.cout, 0, ks)) continue;
+    emp_pdl::SepX3 sx;
+    sx.C = C; sx.Cout = w.cout; sx.ks = ks;
+    RC(dev_alloc(n, (size_t)ks * ks * C, &sx.dw));
+    RC(launch_sepx3_pack_dw(dwi->second, ks, C, C, sx.dw, nullptr));
+    RC(dev_alloc(n, (size_t)sepx3_pw_halfs(C, w.cout), &sx.pw));
+    RC(launch_sepx3_pack_pw(w.w, C, C, w.cout, sx.pw, nullptr));
+    n->sepx3[base] = sx;
+  }
+  EMP_CHECK_HIP(hipStreamSynchronize(nullptr));
+  return EMP_OK;
+}
+
+// fp16x3 mode, round 6: the two decoders' low-level projections of stage i read the same encoder map: weights stacked along
+// Cout, one launch with two destinations (conv16x3.hip store4) -- the widest map of the network is read once instead of twice
+int x3_merged_projections(emp_pdl* n) {
+  for (int i = 0; i < n->cfg.n_stages; ++i) {
+    const std::string tail = ".project." + std::to_string(i) + ".0";
+    auto ia = n->w32.find(kDecoders[0] + tail), ib = n->w32.find(kDecoders[1] + tail);
+    if (ia == n->w32.end() || ib == n->w32.end()) continue;
+    const emp_pdl::W32 &wa = ia->second, &wb = ib->second;
+    if (wa.cin16 != wb.cin16 || wa.kh != 1 || wb.kh != 1 || wa.kw != 1 || wb.kw != 1 || wa.cout % 4 || wb.cout % 4 || wa.cin16 >= 1024) continue;
+    emp_pdl::W32 m;
+    RC(stack32(n, wa, wb, &m));
+    n->w32["decoders" + tail] = m;
+  }
+  return EMP_OK;
+}
+
+// the plane region's layers: ResNet layer3 / layer4 and the ASPP convolutions
+bool x3_region(const std::string& name) {
+  return name.find("encoder.layer3.") == 0 || name.find("encoder.layer4.") == 0 || name.find(".aspp.") != std::string::npos;
+}
+
+// conv16x3p_kernel's packed hi / lo image of w
+int x3p_image(emp_pdl* n, emp_pdl::W32& w, int64_t halfs) {
+  RC(dev_alloc(n, (size_t)halfs, &w.wimgp));
+  w.x3p_kg = x3p_kgroup(w.kh * w.kw, w.cin16);
+  return launch_x3p_pack(w.w, w.wimgp, w.cout, w.kh * w.kw * w.cin16, nullptr, w.kh * w.kw, w.cin16, w.x3p_kg);
+}
+
+// fp16x3 mode: every convolution weight once more as fp16 pairs (hi | lo << 16, the fp32 blob's layout), so that the
+// kernel's weight staging is a lane permutation instead of five vector operations per element (conv16x3.hip)
+int x3_weight_images(emp_pdl* n) {
+  for (auto& kv : n->w32) {
+    emp_pdl::W32& w = kv.second;
+    const int64_t cnt = (int64_t)w.cout * (w.kh * w.kw * w.cin16 + w.cin2_16);
+    RC(dev_alloc(n, (size_t)(cnt > 0 ? cnt : 4), &w.wp));
+    RC(launch_split_pairs(w.w, w.wp, cnt, nullptr));
+    // long-K layers (the split-role kernel's): the weights once more as that kernel's LDS image, fetched by LDS-DMA
+    const int K = w.kh * w.kw * w.cin16;
+    const int64_t ih = (w.cin2_16 == 0 && K >= 1024) ? x3_weight_image_halfs(w.cout, K, w.cin16) : 0;
+    if (ih > 0) {
+      RC(dev_alloc(n, (size_t)ih, &w.wimg));
+      RC(launch_x3_weight_image(w.w, w.wimg, w.cout, K, nullptr));
+    }
+    // round 6: the plane region's layers (Cout % 256 == 0, Cin % 32 == 0) once more as conv16x3p_kernel's packed hi / lo image
+    const int64_t ip = (n->x3_planes && n->cfg.encoder == 0 && x3_region(kv.first) && w.cin2_16 == 0 && w.cin16 % 32 == 0 && K >= 128) ? x3p_image_halfs(w.cout, K) : 0;
+    if (ip > 0) RC(x3p_image(n, w, ip));
+  }
+  return EMP_OK;
+}
+
+// the two decoders' ASPP branch i reads the same p5: [semantic ; instance] weights stacked along Cout, ONE launch with two
+// destinations (twice the workgroups per launch: a batch of 8 tiles of 1024^2 fills the chip with the 256-channel branches)
+int x3_merged_aspp(emp_pdl* n) {
+  for (int i = 0; i <= 3; ++i) {
+    const std::string tail = ".aspp.convs." + std::to_string(i) + ".0";
+    auto ia = n->w32.find(kDecoders[0] + tail), ib = n->w32.find(kDecoders[1] + tail);
+    if (ia == n->w32.end() || ib == n->w32.end()) continue;
+    const emp_pdl::W32 &wa = ia->second, &wb = ib->second;
+    if (!wa.wimgp || !wb.wimgp || wa.cout != wb.cout || wa.cin16 != wb.cin16 || wa.kh != wb.kh || wa.kw != wb.kw) continue;
+    emp_pdl::W32 m;
+    RC(stack32(n, wa, wb, &m));
+    const int64_t ip = x3p_image_halfs(m.cout, m.kh * m.kw * m.cin16);
+    if (ip <= 0) continue;
+    RC(x3p_image(n, m, ip));
+    n->w32["decoders" + tail] = m;
+  }
+  return EMP_OK;
+}
+
+// every layer of the plane region has its packed image, and no low-level skip leaves the region
+bool x3_planes_complete(const emp_pdl* n) {
+  const emp_pdl_config& c = n->cfg;
+  bool ok = true;
+  for (auto& kv : n->w32) {
+    const bool boundary = kv.first == "encoder.layer3.0.conv1" || kv.first == "encoder.layer3.0.downsample.0" || kv.first.find("conv3+ds") != std::string::npos;
+    if (x3_region(kv.first) && !boundary && !kv.second.wimgp) ok = false;      // (the boundary layers read the fp32 layer2 map: round 5's kernels)
+  }
+  for (int i = 0; i < (c.arch == 0 ? c.n_stages : 0); ++i) ok = ok && c.low_level_stages[i] <= 2;      // a low-level skip out of the region would need a conversion
+  return ok;
 }
 
 }  // namespace
@@ -148,202 +304,17 @@ namespace emp {
 
 int finalize32(emp_pdl* n) {
   const emp_pdl_config& c = n->cfg;
-  if (c.encoder == 1) {
-    RC(upload_regnet_stem(n));
-    for (int si = 1; si <= 4; ++si)
-      for (int b = 1; b <= c.rn_depths[si - 1]; ++b) {
-        const std::string p = "encoder.stage" + std::to_string(si) + ".block" + std::to_string(b);
-        const int w = c.rn_widths[si - 1], g = c.rn_groups[si - 1];
-        RC(pack32(n, p + ".bottleneck.a.0"));
-        RC(pack32(n, p + ".bottleneck.b.0"));      // (w, w / g, 3, 3): rows [o][tap][(w / g) padded to 16], group-major in o
-        const emp_pdl::W32& wb = n->w32.at(p + ".bottleneck.b.0");
-        EMP_REQUIRE(wb.cout == w && wb.cin * g == w && wb.kh == 3 && wb.kw == 3, "%s.bottleneck.b.0 must be (%d,%d,3,3)", p.c_str(), w,
-                    w / g);
-        if (c.rn_se) {
-          RC(pack32(n, p + ".bottleneck.se.se.0"));
-          RC(pack32(n, p + ".bottleneck.se.se.2"));
-        }
-        RC(pack32(n, p + ".bottleneck.c.0"));
-        if (regnet_has_shortcut(c, si, b)) RC(pack32(n, p + ".downsample.conv.0"));
-      }
-  } else {
-    for (int li = 1; li <= 4; ++li)
-      for (int b = 0; b < kLayers[li - 1]; ++b) {
-        const std::string p = "encoder.layer" + std::to_string(li) + "." + std::to_string(b);
-        RC(pack32(n, p + ".conv1"));
-        RC(pack32(n, p + ".conv2"));
-        RC(pack32(n, p + ".conv3"));
-        if (b == 0) RC(pack32(n, p + ".downsample.0"));
-        if (b == 0 && n->precision == 2) RC(pack32_conv3_ds(n, p));
-      }
-  }
-  if (c.arch == 1) {
-    RC(pack32(n, "p2_resample.conv.0"));
-    for (const auto& nm : n->param_names) {
-      const bool fpn = nm.find("_fpn.") != std::string::npos, dec = nm.find("_decoder.") != std::string::npos;
-      if (!fpn && !dec) continue;
-      if (nm.size() > 8 && nm.compare(nm.size() - 8, 8, ".weights") == 0) continue;      // fusew: host side (finalize)
-      if (nm.find(".sepconv.0") != std::string::npos) RC(pack32_dw(n, nm, (int)n->params[nm].shape[0]));
-      else if (nm.find(".upsamplings.") != std::string::npos) RC(pack32_convT(n, nm));
-      else RC(pack32(n, nm));
-    }
-  } else {
-    const char* decs[2] = {"semantic_decoder", "instance_decoder"};
-    for (int d = 0; d < (c.ins_decoder ? 2 : 1); ++d) {
-      const std::string p = decs[d];
-      for (int i = 0; i <= 3; ++i) RC(pack32(n, p + ".aspp.convs." + std::to_string(i) + ".0"));
-      {   // projection: first 4A input channels -> conv; the pooled branch's A channels -> per-image bias (projpool.w)
-        const HostParam& hp = n->params[p + ".aspp.project.0"];
-        const int A = n->aspp_ch;
-        HostParam head;
-        head.shape = {A, 4 * A, 1, 1};
-        head.w.resize((size_t)A * 4 * A);
-        head.b = hp.b;
-        for (int o = 0; o < A; ++o)
-          for (int i = 0; i < 4 * A; ++i) head.w[(size_t)o * 4 * A + i] = hp.w[(size_t)o * 5 * A + i];
-        RC(pack32(n, p + ".aspp.project.0", 0, &head));
-      }
-      int xch = n->aspp_ch;
-      for (int i = 0; i < c.n_stages; ++i) {
-        const int lp = d == 0 ? c.low_level_proj_sem[i] : c.low_level_proj_ins[i];
-        RC(pack32(n, p + ".project." + std::to_string(i) + ".0"));
-        const int cpad = round_up(xch + lp, n->precision == 2 ? 32 : 16);      // (the fused block walks the channels in chunks of 32)
-        RC(pack32_dw(n, p + ".fuse." + std::to_string(i) + ".0.sepconv.0", cpad));
-        RC(pack32(n, p + ".fuse." + std::to_string(i) + ".0.sepconv.1", cpad));
-        xch = n->dec_ch;
-      }
-    }
-  }
-  const char* heads[3] = {"semantic_head", "ins_center", "ins_xy"};
-  for (int k = 0; k < 3; ++k) {
-    const std::string p = heads[k];
-    RC(pack32_dw(n, p + ".head.0.0.sepconv.0", n->dec_ch));
-    RC(pack32(n, p + ".head.0.0.sepconv.1"));
-  }
-  const int ldp = round_up(n->dec_ch + n->ncls, 16);
-  for (int k = 0; k < c.num_fc; ++k) RC(pack32(n, "semantic_pr.point_head.fc_layers." + std::to_string(k) + ".0", ldp));
-  {
-    const HostParam& hp = n->params["semantic_pr.point_head.predictor"];
-    const int K = (int)hp.shape[1];
-    std::vector<float> w((size_t)n->ncls * ldp, 0.f);
-    for (int o = 0; o < n->ncls; ++o)
-      for (int i = 0; i < K; ++i) w[(size_t)o * ldp + i] = hp.w[(size_t)o * K + i];
-    RC(upload_f32(n, "pr.predictor.w32", w));
-  }
-  if (n->precision == 2 && n->x3_ksplit && !n->x3_kpart) {
-    void* d = nullptr;
-    EMP_CHECK_HIP(hipMalloc(&d, (size_t)X3_KPART_BYTES));
-    n->owned.push_back(d);
-    n->x3_kpart = (float*)d;
-  }
-  if (n->precision == 2 && n->x3_fuse_sep) {
-    // fp16x3 mode, round 6: the separable blocks' weights in the fused kernel's orders (sepconv_x3.hip)
-    for (auto& kv : n->w32) {
-      const std::string& nm = kv.first;
-      if (nm.size() < 10 || nm.compare(nm.size() - 10, 10, ".sepconv.1") != 0) continue;
-      const std::string base = nm.substr(0, nm.size() - 2);      // "... .sepconv"
-      auto dwi = n->f32w.find(base + ".0.dw32");
-      auto hpi = n->params.find(base + ".0");
-      if (dwi == n->f32w.end() || hpi == n->params.end() || hpi->second.shape.size() != 4) continue;
-      const emp_pdl::W32& w = kv.second;
-      const int ks = (int)hpi->second.shape[2], C = w.cin16;
-      if (w.kh != 1 || w.kw != 1 || !sepconv_x3_supported(C, w.cout, 0, ks)) continue;
-      emp_pdl::SepX3 sx;
-      sx.C = C; sx.Cout = w.cout; sx.ks = ks;
-      void* d = nullptr;
-      EMP_CHECK_HIP(hipMalloc(&d, (size_t)ks * ks * C * sizeof(float)));
-      n->owned.push_back(d);
-      sx.dw = (float*)d;
-      RC(launch_sepx3_pack_dw(dwi->second, ks, C, C, sx.dw, nullptr));
-      EMP_CHECK_HIP(hipMalloc(&d, (size_t)sepx3_pw_halfs(C, w.cout) * sizeof(half_t)));
-      n->owned.push_back(d);
-      sx.pw = (half_t*)d;
-      RC(launch_sepx3_pack_pw(w.w, C, C, w.cout, sx.pw, nullptr));
-      n->sepx3[base] = sx;
-    }
-    EMP_CHECK_HIP(hipStreamSynchronize(nullptr));
-  }
-  if (n->precision == 2 && c.arch == 0 && c.ins_decoder && n->x3_merge_proj) {
-    // fp16x3 mode, round 6: the two decoders' low-level projections of stage i read the same encoder map: weights stacked along
-    // Cout, one launch with two destinations (conv16x3.hip store4) -- the widest map of the network is read once instead of twice
-    for (int i = 0; i < c.n_stages; ++i) {
-      const std::string a = "semantic_decoder.project." + std::to_string(i) + ".0", b = "instance_decoder.project." + std::to_string(i) + ".0";
-      auto ia = n->w32.find(a), ib = n->w32.find(b);
-      if (ia == n->w32.end() || ib == n->w32.end()) continue;
-      const emp_pdl::W32 &wa = ia->second, &wb = ib->second;
-      if (wa.cin16 != wb.cin16 || wa.kh != 1 || wb.kh != 1 || wa.kw != 1 || wb.kw != 1 || wa.cout % 4 || wb.cout % 4 || wa.cin16 >= 1024) continue;
-      emp_pdl::W32 m;
-      RC(stack32(n, wa, wb, &m));
-      n->w32["decoders.project." + std::to_string(i) + ".0"] = m;
-    }
-  }
-  if (n->precision == 2) {
-    // fp16x3 mode: every convolution weight once more as fp16 pairs (hi | lo << 16, the fp32 blob's layout), so that the
-    // kernel's weight staging is a lane permutation instead of five vector operations per element (conv16x3.hip)
-    for (auto& kv : n->w32) {
-      emp_pdl::W32& w = kv.second;
-      const int64_t cnt = (int64_t)w.cout * (w.kh * w.kw * w.cin16 + w.cin2_16);
-      void* d = nullptr;
-      EMP_CHECK_HIP(hipMalloc(&d, (size_t)(cnt > 0 ? cnt : 4) * sizeof(uint32_t)));
-      n->owned.push_back(d);
-      w.wp = (uint32_t*)d;
-      RC(launch_split_pairs(w.w, w.wp, cnt, nullptr));
-      // long-K layers (the split-role kernel's): the weights once more as that kernel's LDS image, fetched by LDS-DMA
-      const int K = w.kh * w.kw * w.cin16;
-      const int64_t ih = (w.cin2_16 == 0 && K >= 1024) ? x3_weight_image_halfs(w.cout, K, w.cin16) : 0;
-      if (ih > 0) {
-        EMP_CHECK_HIP(hipMalloc(&d, (size_t)ih * sizeof(half_t)));
-        n->owned.push_back(d);
-        w.wimg = (half_t*)d;
-        RC(launch_x3_weight_image(w.w, w.wimg, w.cout, K, nullptr));
-      }
-      // round 6: the plane region's layers (ResNet layer3 / layer4 and the ASPP convolutions: Cout % 256 == 0, Cin % 32 == 0)
-      // once more as conv16x3p_kernel's packed hi / lo image
-      const bool region = kv.first.find("encoder.layer3.") == 0 || kv.first.find("encoder.layer4.") == 0 || kv.first.find(".aspp.") != std::string::npos;
-      const int64_t ip = (n->x3_planes && n->cfg.encoder == 0 && region && w.cin2_16 == 0 && w.cin16 % 32 == 0 && K >= 128) ? x3p_image_halfs(w.cout, K) : 0;
-      if (ip > 0) {
-        EMP_CHECK_HIP(hipMalloc(&d, (size_t)ip * sizeof(half_t)));
-        n->owned.push_back(d);
-        w.wimgp = (half_t*)d;
-        w.x3p_kg = x3p_kgroup(w.kh * w.kw, w.cin16);
-        RC(launch_x3p_pack(w.w, w.wimgp, w.cout, K, nullptr, w.kh * w.kw, w.cin16, w.x3p_kg));
-      }
-    }
-    if (n->x3_planes && c.encoder == 0 && c.arch == 0 && c.ins_decoder && n->x3_merge_aspp) {
-      // the two decoders' ASPP branch i reads the same p5: [semantic ; instance] weights stacked along Cout, ONE launch with two
-      // destinations (twice the workgroups per launch: a batch of 8 tiles of 1024^2 fills the chip with the 256-channel branches)
-      for (int i = 0; i <= 3; ++i) {
-        const std::string a = "semantic_decoder.aspp.convs." + std::to_string(i) + ".0", b = "instance_decoder.aspp.convs." + std::to_string(i) + ".0";
-        auto ia = n->w32.find(a), ib = n->w32.find(b);
-        if (ia == n->w32.end() || ib == n->w32.end()) continue;
-        const emp_pdl::W32 &wa = ia->second, &wb = ib->second;
-        if (!wa.wimgp || !wb.wimgp || wa.cout != wb.cout || wa.cin16 != wb.cin16 || wa.kh != wb.kh || wa.kw != wb.kw) continue;
-        emp_pdl::W32 m;
-        RC(stack32(n, wa, wb, &m));
-        const size_t K = (size_t)wa.kh * wa.kw * wa.cin16;
-        void* d = nullptr;
-        const int64_t ip = x3p_image_halfs(m.cout, (int)K);
-        if (ip <= 0) continue;
-        EMP_CHECK_HIP(hipMalloc(&d, (size_t)ip * sizeof(half_t)));
-        n->owned.push_back(d);
-        m.wimgp = (half_t*)d;
-        m.x3p_kg = x3p_kgroup(m.kh * m.kw, m.cin16);
-        RC(launch_x3p_pack(m.w, m.wimgp, m.cout, (int)K, nullptr, m.kh * m.kw, m.cin16, m.x3p_kg));
-        n->w32["decoders.aspp.convs." + std::to_string(i) + ".0"] = m;
-      }
-    }
-    EMP_CHECK_HIP(hipStreamSynchronize(nullptr));
-    if (n->x3_planes && c.encoder == 0) {
-      bool ok = true;
-      for (auto& kv : n->w32) {
-        const bool region = kv.first.find("encoder.layer3.") == 0 || kv.first.find("encoder.layer4.") == 0 || kv.first.find(".aspp.") != std::string::npos;
-        const bool boundary = kv.first == "encoder.layer3.0.conv1" || kv.first == "encoder.layer3.0.downsample.0" || kv.first.find("conv3+ds") != std::string::npos;
-        if (region && !boundary && !kv.second.wimgp) ok = false;      // (the boundary layers read the fp32 layer2 map: round 5's kernels)
-      }
-      for (int i = 0; i < (c.arch == 0 ? c.n_stages : 0); ++i) ok = ok && c.low_level_stages[i] <= 2;      // a low-level skip out of the region would need a conversion
-      n->x3_planes_ready = ok;
-    }
-  }
+  RC(pack32_encoder(n));
+  RC(c.arch == 1 ? pack32_bifpn(n) : pack32_deeplab(n));
+  RC(pack32_heads_pointrend(n));
+  if (n->precision != 2) return EMP_OK;
+  if (n->x3_ksplit && !n->x3_kpart) RC(dev_alloc(n, (size_t)X3_KPART_BYTES / sizeof(float), &n->x3_kpart));
+  if (n->x3_fuse_sep) RC(x3_sep_weights(n));
+  if (c.arch == 0 && c.ins_decoder && n->x3_merge_proj) RC(x3_merged_projections(n));
+  RC(x3_weight_images(n));
+  if (n->x3_planes && c.encoder == 0 && c.arch == 0 && c.ins_decoder && n->x3_merge_aspp) RC(x3_merged_aspp(n));
+  EMP_CHECK_HIP(hipStreamSynchronize(nullptr));
+  if (n->x3_planes && c.encoder == 0) n->x3_planes_ready = x3_planes_complete(n);
   return EMP_OK;
 }
 
@@ -422,401 +393,375 @@ int c32(emp_pdl* n, const std::string& wname, const T32& in, int in_coff, const 
   return launch_conv32(p, s);
 }
 
-}  // namespace
-
-namespace emp {
-
-int run32(emp_pdl* n, const void* img, int dtype, float sub, float mul, int N, int H, int W, int vh, int vw, int RS, int interp,
-          float* o_sem, float* o_ctr, float* o_off, hipStream_t s) {
-  const emp_pdl_config& c = n->cfg;
-  EMP_REQUIRE(N > 0 && H > 0 && W > 0 && H % 16 == 0 && W % 16 == 0, "forward: H=%d W=%d must be positive multiples of 16", H, W);
-  EMP_REQUIRE(RS >= 1 && RS <= 6, "render_steps=%d out of range", RS);
-  EMP_REQUIRE(c.arch == 0 || (H % 128 == 0 && W % 128 == 0), "BiFPN forward: H=%d W=%d must be multiples of 128", H, W);
-  n->flops = 0.0;
+// One forward of the fp32 / fp16x3 graph: the maps made so far by name, and what its stages share
+struct Fwd32 : Forward {
+  bool hlr;      // fp16x3 mode, round 6: layer3 / layer4 / ASPP maps as hl32 planes on conv16x3p_kernel (emp_pdl members x3_planes*)
   std::map<std::string, T32> T;
-  auto mk = [&](const std::string& k, int H_, int W_, int C_, int fmt = 0) -> int { T32 t; int rc = t32(n, k, N, H_, W_, C_, &t); t.fmt = fmt; T[k] = t; return rc; };
-  // fp16x3 mode, round 6: layer3 / layer4 / ASPP maps as hl32 planes on conv16x3p_kernel (emp_pdl members x3_planes*)
-  const bool hlr = n->precision == 2 && n->x3_planes_ready && c.encoder == 0 &&
-                      ((int64_t)N * (H / 16) * (W / 16)) / 256 >= n->x3_planes_min_tiles * (c.stage4_stride == 32 ? 2 : 1);
-  // (an encoder at output stride 32 -- the BiFPN networks -- has a quarter of those tiles in layer4: BiFPN-PR with the region on / off
-  //  492 / 513 tiles/s at batch 8, 594 / 581 at 16, 651 / 631 at 32: its threshold is twice the stride-16 one)
-  auto A = [&](const std::string& k) -> T32& { return T.at(k); };
-  // The separable block `base` ("... .sepconv": depthwise ks x ks -> pointwise -> act [-> a head's 1x1]) of `in`.  fp16x3 mode: ONE launch
-  // where the fused kernel takes it (sepconv_x3.hip; at a head, out == nullptr, hw / hb / hcn -> hout and no map).  Else the depthwise
-  // launch into the buffer `dwkey` -- made on this path only -- and, where there is an output map, the pointwise conv; *fused tells a
-  // head whether its pointwise half is still to run
-  auto sep = [&](const std::string& base, const T32& in, int ks, int act, const std::string& dwkey, const T32* out, const float* hw,
-                 const float* hb, int hcn, float* hout, bool* fused) -> int {
-    auto it = n->sepx3.find(base);
-    const int64_t tiles = (int64_t)N * ((in.H + 7) / 8) * ((in.W + 15) / 16);
-    *fused = n->precision == 2 && it != n->sepx3.end() && !in.fmt && in.ld >= it->second.C && tiles >= n->x3_sep_min_tiles &&
-             sepconv_x3_supported(it->second.C, it->second.Cout, hcn, it->second.ks);
-    if (*fused) {
-      const emp_pdl::SepX3& sx = it->second;
-      n->flops += 2.0 * sx.ks * sx.ks * (double)N * in.H * in.W * in.C + 2.0 * (double)N * in.H * in.W * sx.Cout * (double)n->w32.at(base + ".1").cin;
-      return launch_sepconv_x3(in.p, N, in.H, in.W, sx.C, in.ld, sx.dw, sx.pw, n->w32.at(base + ".1").b, sx.Cout, act, out ? out->p : nullptr,
-                               out ? out->ld : 0, hw, hb, hcn, hout, (int64_t)in.H * in.W, s, sx.ks);
+  std::string x;
+
+  T32& A(const std::string& k) { return T.at(k); }
+  int mk(const std::string& k, int H_, int W_, int C_, int fmt = 0) {
+    T32 t;
+    int rc = t32(n, k, N, H_, W_, C_, &t);
+    t.fmt = fmt;
+    T[k] = t;
+    return rc;
+  }
+  int mkp(const std::string& k, int H_, int W_, int C_);
+  int sep(const std::string& base, const T32& in, int ks, int act, const std::string& dwkey, const T32* out, const float* hw,
+          const float* hb, int hcn, float* hout, bool* fused);
+  int regnet_encoder();
+  int resnet_encoder();
+  int bifpn_decoders();
+  int merged_aspp(const T32& src, int fmt);
+  int deeplab_decoders();
+  int heads();
+  int pointrend();
+};
+
+// A RegNet map.  RegNet's widths are multiples of 8, not of 16: every map gets a row of round_up(C, 16) + 16
+// floats whose tail stays zero (buf32 clears a buffer when it allocates it and no kernel writes beyond C), so that a
+// consumer reading its input channels padded to 16 -- from a group's first channel, in the grouped 3x3 -- stays
+// inside the row and meets zeros (or the next group's finite values) under zero weights.
+int Fwd32::mkp(const std::string& k, int H_, int W_, int C_) {
+  T32 t;
+  t.N = N; t.H = H_; t.W = W_; t.C = C_; t.ld = round_up(C_, 16) + 16;
+  const size_t had = n->pool32.count(k) ? n->pool32[k].second : 0;
+  const int rc = buf32(n, k, (size_t)N * H_ * W_ * t.ld, &t.p);
+  if (rc) return rc;
+  // a buffer kept from a forward of another shape holds that forward's values where this one's row tails are
+  const std::array<int, 4> geo = {N, H_, W_, t.ld};
+  auto gi = n->geom32.find(k);
+  if (gi == n->geom32.end() || gi->second != geo) {
+    if (had >= (size_t)N * H_ * W_ * t.ld && gi != n->geom32.end())
+      EMP_CHECK_HIP(hipMemsetAsync(t.p, 0, (size_t)N * H_ * W_ * t.ld * sizeof(float), s));
+    n->geom32[k] = geo;
+  }
+  T[k] = t;
+  return EMP_OK;
+}
+
+// The separable block `base` ("... .sepconv": depthwise ks x ks -> pointwise -> act [-> a head's 1x1]) of `in`.  fp16x3 mode: ONE launch
+// where the fused kernel takes it (sepconv_x3.hip; at a head, out == nullptr, hw / hb / hcn -> hout and no map).  Else the depthwise
+// launch into the buffer `dwkey` -- made on this path only -- and, where there is an output map, the pointwise conv; *fused tells a
+// head whether its pointwise half is still to run
+int Fwd32::sep(const std::string& base, const T32& in, int ks, int act, const std::string& dwkey, const T32* out, const float* hw,
+               const float* hb, int hcn, float* hout, bool* fused) {
+  auto it = n->sepx3.find(base);
+  const int64_t tiles = (int64_t)N * ((in.H + 7) / 8) * ((in.W + 15) / 16);
+  *fused = n->precision == 2 && it != n->sepx3.end() && !in.fmt && in.ld >= it->second.C && tiles >= n->x3_sep_min_tiles &&
+           sepconv_x3_supported(it->second.C, it->second.Cout, hcn, it->second.ks);
+  if (*fused) {
+    const emp_pdl::SepX3& sx = it->second;
+    n->flops += 2.0 * sx.ks * sx.ks * (double)N * in.H * in.W * in.C + 2.0 * (double)N * in.H * in.W * sx.Cout * (double)n->w32.at(base + ".1").cin;
+    return launch_sepconv_x3(in.p, N, in.H, in.W, sx.C, in.ld, sx.dw, sx.pw, n->w32.at(base + ".1").b, sx.Cout, act, out ? out->p : nullptr,
+                             out ? out->ld : 0, hw, hb, hcn, hout, (int64_t)in.H * in.W, s, sx.ks);
+  }
+  RC(mk(dwkey, in.H, in.W, in.C));
+  n->flops += 2.0 * ks * ks * (double)N * in.H * in.W * in.C;
+  RC(launch_dwconv_f32(in.p, N, in.H, in.W, in.C, in.ld, n->f32w.at(base + ".0.dw32"), ks, A(dwkey).p, A(dwkey).ld, s));
+  return out ? c32(n, base + ".1", A(dwkey), 0, *out, 0, s, {.act = act}) : EMP_OK;
+}
+
+// RegNet (regnet.py:160-166)
+int Fwd32::regnet_encoder() {
+  RC(mkp("stem", H / 2, W / 2, c.rn_stem));
+  RC(launch_stem3x3s2_f32(img, dtype, sub, mul, N, H, W, vh, vw, n->f32w.at("rn.stem.w"), n->f32w.at("rn.stem.b"), c.rn_stem,
+                            A("stem").p, A("stem").ld, s));
+  n->flops += 2.0 * N * (H / 2) * (W / 2) * (double)c.rn_stem * 9.0;
+  x = "stem";
+  pyr[0] = "stem";
+  for (const RegBlock& k : n->reg_blocks) {
+    const std::string& p = k.name;
+    const int w = k.width, g = k.groups, sb = k.stride;
+    const T32 xin = A(x);
+    const int ho = (xin.H - 1) / sb + 1, wo = (xin.W - 1) / sb + 1;
+    RC(mkp(p + ".a", xin.H, xin.W, w));
+    RC(c32(n, p + ".bottleneck.a.0", xin, 0, A(p + ".a"), 0, s, {.act = ACT_RELU}));
+    RC(mkp(p + ".b", ho, wo, w));
+    RC(c32(n, p + ".bottleneck.b.0", A(p + ".a"), 0, A(p + ".b"), 0, s, {.stride = sb, .pad = 1, .act = ACT_RELU, .groups = g}));
+    if (c.rn_se) {      // per-pixel gate: x * sigmoid(W2 relu(W1 x)) (blocks.py:35-50: the pool is 1 x 1)
+      RC(mkp(p + ".se1", ho, wo, w / 4));
+      RC(c32(n, p + ".bottleneck.se.se.0", A(p + ".b"), 0, A(p + ".se1"), 0, s, {.act = ACT_RELU}));
+      RC(mkp(p + ".se2", ho, wo, w));
+      RC(c32(n, p + ".bottleneck.se.se.2", A(p + ".se1"), 0, A(p + ".se2"), 0, s));
+      RC(launch_gate_mul_f32(A(p + ".b").p, A(p + ".b").ld, A(p + ".se2").p, A(p + ".se2").ld, (int64_t)N * ho * wo, w, s));
     }
-    RC(mk(dwkey, in.H, in.W, in.C));
-    n->flops += 2.0 * ks * ks * (double)N * in.H * in.W * in.C;
-    RC(launch_dwconv_f32(in.p, N, in.H, in.W, in.C, in.ld, n->f32w.at(base + ".0.dw32"), ks, A(dwkey).p, A(dwkey).ld, s));
-    return out ? c32(n, base + ".1", A(dwkey), 0, *out, 0, s, {.act = act}) : EMP_OK;
-  };
-  // ---- encoder ----
-  std::string x, pyr[5];
-  if (c.encoder == 1) {
-    // RegNet (regnet.py:160-166).  Its widths are multiples of 8, not of 16: every map gets a row of round_up(C, 16) + 16
-    // floats whose tail stays zero (buf32 clears a buffer when it allocates it and no kernel writes beyond C), so that a
-    // consumer reading its input channels padded to 16 -- from a group's first channel, in the grouped 3x3 -- stays
-    // inside the row and meets zeros (or the next group's finite values) under zero weights.
-    auto mkp = [&](const std::string& k, int H_, int W_, int C_) -> int {
-      T32 t;
-      t.N = N; t.H = H_; t.W = W_; t.C = C_; t.ld = round_up(C_, 16) + 16;
-      const size_t had = n->pool32.count(k) ? n->pool32[k].second : 0;
-      const int rc = buf32(n, k, (size_t)N * H_ * W_ * t.ld, &t.p);
-      if (rc) return rc;
-      // a buffer kept from a forward of another shape holds that forward's values where this one's row tails are
-      const std::array<int, 4> geo = {N, H_, W_, t.ld};
-      auto gi = n->geom32.find(k);
-      if (gi == n->geom32.end() || gi->second != geo) {
-        if (had >= (size_t)N * H_ * W_ * t.ld && gi != n->geom32.end())
-          EMP_CHECK_HIP(hipMemsetAsync(t.p, 0, (size_t)N * H_ * W_ * t.ld * sizeof(float), s));
-        n->geom32[k] = geo;
-      }
-      T[k] = t;
-      return EMP_OK;
-    };
-    RC(mkp("stem", H / 2, W / 2, c.rn_stem));
-    RC(launch_stem3x3s2_f32(img, dtype, sub, mul, N, H, W, vh, vw, n->f32w.at("rn.stem.w"), n->f32w.at("rn.stem.b"), c.rn_stem,
-                              A("stem").p, A("stem").ld, s));
-    n->flops += 2.0 * N * (H / 2) * (W / 2) * (double)c.rn_stem * 9.0;
-    x = "stem";
-    pyr[0] = "stem";
-    for (int si = 1; si <= 4; ++si) {
-      const int w = c.rn_widths[si - 1], g = c.rn_groups[si - 1];
-      for (int b = 1; b <= c.rn_depths[si - 1]; ++b) {
-        const std::string p = "encoder.stage" + std::to_string(si) + ".block" + std::to_string(b);
-        const int sb = b == 1 ? c.rn_strides[si - 1] : 1;
-        const T32 xin = A(x);
-        const int ho = (xin.H - 1) / sb + 1, wo = (xin.W - 1) / sb + 1;
-        RC(mkp(p + ".a", xin.H, xin.W, w));
-        RC(c32(n, p + ".bottleneck.a.0", xin, 0, A(p + ".a"), 0, s, {.act = ACT_RELU}));
-        RC(mkp(p + ".b", ho, wo, w));
-        RC(c32(n, p + ".bottleneck.b.0", A(p + ".a"), 0, A(p + ".b"), 0, s, {.stride = sb, .pad = 1, .act = ACT_RELU, .groups = g}));
-        if (c.rn_se) {      // per-pixel gate: x * sigmoid(W2 relu(W1 x)) (blocks.py:35-50: the pool is 1 x 1)
-          RC(mkp(p + ".se1", ho, wo, w / 4));
-          RC(c32(n, p + ".bottleneck.se.se.0", A(p + ".b"), 0, A(p + ".se1"), 0, s, {.act = ACT_RELU}));
-          RC(mkp(p + ".se2", ho, wo, w));
-          RC(c32(n, p + ".bottleneck.se.se.2", A(p + ".se1"), 0, A(p + ".se2"), 0, s));
-          RC(launch_gate_mul_f32(A(p + ".b").p, A(p + ".b").ld, A(p + ".se2").p, A(p + ".se2").ld, (int64_t)N * ho * wo, w, s));
-        }
-        const T32* idn = &A(x);
-        if (regnet_has_shortcut(c, si, b)) {
-          RC(mkp(p + ".ds", ho, wo, w));
-          RC(c32(n, p + ".downsample.conv.0", xin, 0, A(p + ".ds"), 0, s, {.stride = sb}));
-          idn = &A(p + ".ds");
-        }
-        RC(mkp(p, ho, wo, w));
-        RC(c32(n, p + ".bottleneck.c.0", A(p + ".b"), 0, A(p), 0, s, {.act = ACT_RELU, .res = idn}));
-        x = p;
-      }
-      pyr[si] = x;
+    const T32* idn = &A(x);
+    if (k.shortcut) {
+      RC(mkp(p + ".ds", ho, wo, w));
+      RC(c32(n, p + ".downsample.conv.0", xin, 0, A(p + ".ds"), 0, s, {.stride = sb}));
+      idn = &A(p + ".ds");
     }
+    RC(mkp(p, ho, wo, w));
+    RC(c32(n, p + ".bottleneck.c.0", A(p + ".b"), 0, A(p), 0, s, {.act = ACT_RELU, .res = idn}));
+    x = p;
+    if (k.last) pyr[k.si] = p;
+  }
+  return EMP_OK;
+}
+
+int Fwd32::resnet_encoder() {
+  n->flops += 2.0 * N * (H / 2) * (W / 2) * 64.0 * 49.0;
+  RC(mk("p1", H / 4, W / 4, 64));
+  if (n->precision == 2 && n->x3_fuse_stem) {
+    // fp16x3 mode, round 6: conv1 + bn1 + relu + maxpool as one launch on the matrix pipe (stem.hip stem_pool32_kernel: the three-MFMA
+    // split product of every other convolution of the mode, fp32 tile and output); the half-resolution map is never written
+    RC(launch_stem_pool_f32(img, dtype, sub, mul, N, H, W, vh, vw, n->f32w.at("stem.w"), n->f32w.at("stem.b"), A("p1").p, s));
   } else {
-    n->flops += 2.0 * N * (H / 2) * (W / 2) * 64.0 * 49.0;
-    RC(mk("p1", H / 4, W / 4, 64));
-    if (n->precision == 2 && n->x3_fuse_stem) {
-      // fp16x3 mode, round 6: conv1 + bn1 + relu + maxpool as one launch on the matrix pipe (stem.hip stem_pool32_kernel: the three-MFMA
-      // split product of every other convolution of the mode, fp32 tile and output); the half-resolution map is never written
-      RC(launch_stem_pool_f32(img, dtype, sub, mul, N, H, W, vh, vw, n->f32w.at("stem.w"), n->f32w.at("stem.b"), A("p1").p, s));
+    RC(mk("stem", H / 2, W / 2, 64));
+    RC(launch_stem7x7_f32(img, dtype, sub, mul, N, H, W, vh, vw, n->f32w.at("stem.w"), n->f32w.at("stem.b"), A("stem").p, s));
+    RC(launch_maxpool3x3s2_f32(A("stem").p, N, H / 2, W / 2, 64, A("p1").p, s));
+  }
+  x = "p1";
+  pyr[0] = "p1";
+  for (const ResBlock& k : n->res_blocks) {
+    const std::string& p = k.name;
+    const int sb = k.stride, dil = k.dil, planes = k.planes;
+    const T32 xin = A(x);
+    const int ho = (xin.H - 1) / sb + 1, wo = (xin.W - 1) / sb + 1;
+    // plane region (li >= 3): every map hl32 except where round 5's kernels still read it -- layer3.0's conv1 and
+    // conv3 + shortcut take the fp32 layer2 map (and the fp32 c2) and WRITE hl32 (Conv32::out_fmt)
+    const int pl = (hlr && k.li >= 3) ? 1 : 0;
+    const bool fuse_ds = k.b == 0 && n->precision == 2 && n->x3_fuse_ds && !(pl && xin.fmt);
+    RC(mk(p + ".c1", xin.H, xin.W, planes, pl));
+    RC(c32(n, p + ".conv1", xin, 0, A(p + ".c1"), 0, s, {.act = ACT_RELU}));
+    RC(mk(p + ".c2", ho, wo, planes, (pl && !fuse_ds) ? 1 : 0));
+    RC(c32(n, p + ".conv2", A(p + ".c1"), 0, A(p + ".c2"), 0, s, {.stride = sb, .pad = dil, .dil = dil, .act = ACT_RELU}));
+    RC(mk(p, ho, wo, planes * 4, pl));
+    if (fuse_ds) {
+      // fp16x3 mode: relu(conv3(c2) + downsample(x)) as one convolution over the concatenated K (the shortcut map is
+      // neither written nor read back)
+      RC(c32(n, p + ".conv3+ds", A(p + ".c2"), 0, A(p), 0, s, {.act = ACT_RELU, .in2 = &xin, .stride2 = sb}));
     } else {
-      RC(mk("stem", H / 2, W / 2, 64));
-      RC(launch_stem7x7_f32(img, dtype, sub, mul, N, H, W, vh, vw, n->f32w.at("stem.w"), n->f32w.at("stem.b"), A("stem").p, s));
-      RC(launch_maxpool3x3s2_f32(A("stem").p, N, H / 2, W / 2, 64, A("p1").p, s));
-    }
-    x = "p1";
-    pyr[0] = "p1";
-    for (int li = 1; li <= 4; ++li) {
-      int stride = li == 1 ? 1 : 2, dil = 1;
-      if (li == 4 && c.stage4_stride == 16) { stride = 1; dil = 2; }
-      for (int b = 0; b < kLayers[li - 1]; ++b) {
-        const int sb = b == 0 ? stride : 1, planes = kPlanes[li - 1];
-        const std::string p = "encoder.layer" + std::to_string(li) + "." + std::to_string(b);
-        const T32 xin = A(x);
-        const int ho = (xin.H - 1) / sb + 1, wo = (xin.W - 1) / sb + 1;
-        // plane region (li >= 3): every map hl32 except where round 5's kernels still read it -- layer3.0's conv1 and
-        // conv3 + shortcut take the fp32 layer2 map (and the fp32 c2) and WRITE hl32 (Conv32::out_fmt)
-        const int pl = (hlr && li >= 3) ? 1 : 0;
-        const bool fuse_ds = b == 0 && n->precision == 2 && n->x3_fuse_ds && !(pl && xin.fmt);
-        RC(mk(p + ".c1", xin.H, xin.W, planes, pl));
-        RC(c32(n, p + ".conv1", xin, 0, A(p + ".c1"), 0, s, {.act = ACT_RELU}));
-        RC(mk(p + ".c2", ho, wo, planes, (pl && !fuse_ds) ? 1 : 0));
-        RC(c32(n, p + ".conv2", A(p + ".c1"), 0, A(p + ".c2"), 0, s, {.stride = sb, .pad = dil, .dil = dil, .act = ACT_RELU}));
-        const T32* idn = &A(x);
-        RC(mk(p, ho, wo, planes * 4, pl));
-        if (fuse_ds) {
-          // fp16x3 mode: relu(conv3(c2) + downsample(x)) as one convolution over the concatenated K (the shortcut map is
-          // neither written nor read back)
-          RC(c32(n, p + ".conv3+ds", A(p + ".c2"), 0, A(p), 0, s, {.act = ACT_RELU, .in2 = &xin, .stride2 = sb}));
-          x = p;
-          continue;
-        }
-        if (b == 0) {
-          RC(mk(p + ".ds", ho, wo, planes * 4, pl));
-          RC(c32(n, p + ".downsample.0", xin, 0, A(p + ".ds"), 0, s, {.stride = sb}));
-          idn = &A(p + ".ds");
-        }
-        RC(c32(n, p + ".conv3", A(p + ".c2"), 0, A(p), 0, s, {.act = ACT_RELU, .res = idn}));
-        x = p;
+      const T32* idn = &A(x);
+      if (k.b == 0) {
+        RC(mk(p + ".ds", ho, wo, planes * 4, pl));
+        RC(c32(n, p + ".downsample.0", xin, 0, A(p + ".ds"), 0, s, {.stride = sb}));
+        idn = &A(p + ".ds");
       }
-      pyr[li] = x;
+      RC(c32(n, p + ".conv3", A(p + ".c2"), 0, A(p), 0, s, {.act = ACT_RELU, .res = idn}));
     }
-    if (hlr && c.arch == 1) {
-      // the BiFPN reads P4 / P5 with round 5's kernels (128-channel nodes): fp32 copies of the two pyramid levels
-      for (int li = 3; li <= 4; ++li) {
-        const T32 src = A(pyr[li]);
-        const std::string k = pyr[li] + ".f32";
-        RC(mk(k, src.H, src.W, src.C));
-        RC(launch_hl32_to_f32(reinterpret_cast<const half_t*>(src.p), A(k).p, (int64_t)N * src.H * src.W, src.C, src.ld, src.C, s));
-        pyr[li] = k;
-      }
+    x = p;
+    if (k.last) pyr[k.li] = p;
+  }
+  if (hlr && c.arch == 1) {
+    // the BiFPN reads P4 / P5 with round 5's kernels (128-channel nodes): fp32 copies of the two pyramid levels
+    for (int li = 3; li <= 4; ++li) {
+      const T32 src = A(pyr[li]);
+      const std::string k = pyr[li] + ".f32";
+      RC(mk(k, src.H, src.W, src.C));
+      RC(launch_hl32_to_f32(reinterpret_cast<const half_t*>(src.p), A(k).p, (int64_t)N * src.H * src.W, src.C, src.ld, src.C, s));
+      pyr[li] = k;
     }
   }
-  std::string dec_out[2];
-  if (c.arch == 1) {
-    // ---- BiFPN decoders (bifpn.py:185-236) ----
-    const int F = c.fpn_dim;
-    const T32 p2 = A(pyr[1]);
-    RC(mk("p2f", p2.H, p2.W, F));
-    RC(c32(n, "p2_resample.conv.0", p2, 0, A("p2f"), 0, s));
-    const char* dn[2] = {"semantic", "instance"};
-    for (int d = 0; d < (c.ins_decoder ? 2 : 1); ++d) {
-      const std::string fp = std::string(dn[d]) + "_fpn";
-      const T32 p5 = A(pyr[4]);
-      RC(mk(fp + ".p6pre", p5.H, p5.W, F));
-      RC(c32(n, fp + ".p6_resample.conv.0", p5, 0, A(fp + ".p6pre"), 0, s));
-      RC(mk(fp + ".in.P6", p5.H / 2, p5.W / 2, F));
-      RC(launch_maxpool3x3s2_f32(A(fp + ".p6pre").p, N, p5.H, p5.W, F, A(fp + ".in.P6").p, s));
-      RC(mk(fp + ".in.P7", p5.H / 4, p5.W / 4, F));
-      RC(launch_maxpool3x3s2_f32(A(fp + ".in.P6").p, N, p5.H / 2, p5.W / 2, F, A(fp + ".in.P7").p, s));
-      std::string feat[5] = {pyr[2], pyr[3], pyr[4], fp + ".in.P6", fp + ".in.P7"};
-      for (int li = 0; li < c.fpn_layers; ++li) {
-        const std::string L = fp + ".l" + std::to_string(li), pre = fp + ".bifpns." + std::to_string(li);
-        auto node = [&](const std::string& dirpre, const std::string& q, const float* a, const float* b2, const float* c3,
-                        float ca, float cb, float cc, int mode, int h_, int w_, const std::string& outname) -> int {
-          RC(mk(q + ".fz", h_, w_, F));
-          RC(launch_fuse_combine_f32(a, b2, c3, ca, cb, cc, mode, N, h_, w_, F, A(q + ".fz").p, s));
-          bool fused = false;
-          RC(mk(outname, h_, w_, F));
-          return sep(dirpre + ".after_combines.0.0.sepconv", A(q + ".fz"), 3, ACT_SILU, q + ".dw", &A(outname), nullptr, nullptr, 0, nullptr, &fused);
-        };
-        auto resampled = [&](const std::string& rk, const std::string& src, const std::string& dst, std::string* name) -> int {
-          *name = src;
-          if (!n->w32.count(rk)) return EMP_OK;
-          const T32 in = A(src);
-          RC(mk(dst, in.H, in.W, F));
-          *name = dst;
-          return c32(n, rk, in, 0, A(dst), 0, s);
-        };
-        {
-          const std::string dp = pre + ".top_down_fpn";
-          const float* w = n->fusew.at(dp + ".weights").data();
-          std::string td_prev = feat[4];
-          for (int i = 0; i < 4; ++i) {
-            const int lv = 3 - i;
-            const std::string q = L + ".P" + std::to_string(3 + lv);
-            std::string hi;
-            RC(resampled(dp + ".resamplings." + std::to_string(i) + ".conv.0", feat[lv], q + ".rtd", &hi));
-            const float den = w[i] + w[i + 1] + 1e-4f;
-            const T32 hi_t = A(hi);
-            RC(node(dp, q + ".tdn", A(td_prev).p, hi_t.p, nullptr, w[i] / den, w[i + 1] / den, 0.f, 0, hi_t.H, hi_t.W, q + ".td"));
-            td_prev = q + ".td";
-          }
-        }
-        {
-          const std::string dp = pre + ".bottom_up_fpn";
-          const float* w = n->fusew.at(dp + ".weights").data();
-          std::string bu_prev = L + ".P3.td", newfeat[5];
-          newfeat[0] = bu_prev;
-          for (int i = 0; i < 4; ++i) {
-            const int lv = i + 1;
-            const std::string q = L + ".P" + std::to_string(3 + lv);
-            std::string lo;
-            RC(resampled(dp + ".resamplings." + std::to_string(i) + ".conv.0", feat[lv], q + ".rbu", &lo));
-            const T32 lo_t = A(lo);
-            if (i < 3) {
-              const float den = w[i] + w[i + 1] + w[i + 2] + 1e-4f;
-              RC(node(dp, q + ".bun", A(bu_prev).p, lo_t.p, A(q + ".td").p, w[i] / den, w[i + 1] / den, w[i + 2] / den, 1, lo_t.H,
-                        lo_t.W, q + ".bu"));
-            } else {
-              const float den = w[i] + w[i + 1] + 1e-4f;
-              RC(node(dp, q + ".bun", A(bu_prev).p, lo_t.p, nullptr, w[i] / den, w[i + 1] / den, 0.f, 1, lo_t.H, lo_t.W, q + ".bu"));
-            }
-            bu_prev = q + ".bu";
-            newfeat[lv] = bu_prev;
-          }
-          for (int lv = 0; lv < 5; ++lv) feat[lv] = newfeat[lv];
-        }
-      }
-      const std::string dp = std::string(dn[d]) + "_decoder";
-      const std::string skips[5] = {feat[3], feat[2], feat[1], feat[0], "p2f"};
-      std::string xx = feat[4];
-      for (int i = 0; i < 5; ++i) {
-        const T32 in = A(xx);
-        const std::string cn = dp + ".cat" + std::to_string(i);
-        RC(mk(cn, in.H * 2, in.W * 2, 2 * F));
-        RC(c32(n, dp + ".upsamplings." + std::to_string(i) + ".0", in, 0, A(cn), 0, s, {.act = ACT_RELU, .ps_cout = F}));
-        const T32 sk = A(skips[i]);
-        RC(launch_bilinear_ac_f32_nhwc(sk.p, N, sk.H, sk.W, F, sk.ld, A(cn).p + F, sk.H, sk.W, 2 * F, s));      // same size: copy
-        xx = cn;
-      }
-      const T32 cat = A(xx);
-      RC(mk(dp + ".out", cat.H, cat.W, F));
-      bool fused = false;
-      RC(sep(dp + ".fusion.0.sepconv", cat, 5, ACT_RELU, dp + ".dw", &A(dp + ".out"), nullptr, nullptr, 0, nullptr, &fused));
-      dec_out[d] = dp + ".out";
-    }
-  } else {
-    // ---- Panoptic-DeepLab decoders (decoders/panoptic_deeplab.py:68-80, aspp.py:96-102) ----
+  return EMP_OK;
+}
+
+// ---- BiFPN decoders (bifpn.py:185-236) ----
+int Fwd32::bifpn_decoders() {
+  const int F = c.fpn_dim;
+  const T32 p2 = A(pyr[1]);
+  RC(mk("p2f", p2.H, p2.W, F));
+  RC(c32(n, "p2_resample.conv.0", p2, 0, A("p2f"), 0, s));
+  auto resample = [&](const std::string& rk, const std::string& src, const std::string& dst, std::string* name) -> int {
+    *name = src;
+    if (!n->w32.count(rk)) return EMP_OK;
+    const T32 in = A(src);
+    RC(mk(dst, in.H, in.W, F));
+    *name = dst;
+    return c32(n, rk, in, 0, A(dst), 0, s);
+  };
+  auto node = [&](const std::string& dirpre, const std::string& q, const std::string& a, const std::string& b2, const std::string& c3,
+                  float ca, float cb, float cc, int mode, const std::string& outname) -> int {
+    const T32 tb = A(b2);      // the node's size: its (resampled) input of this level
+    const float *pa = A(a).p, *pc = c3.empty() ? nullptr : A(c3).p;
+    const std::string fz = q + (mode ? ".bun.fz" : ".tdn.fz");
+    RC(mk(fz, tb.H, tb.W, F));
+    RC(launch_fuse_combine_f32(pa, tb.p, pc, ca, cb, cc, mode, N, tb.H, tb.W, F, A(fz).p, s));
+    bool fused = false;
+    RC(mk(outname, tb.H, tb.W, F));
+    return sep(dirpre + ".after_combines.0.0.sepconv", A(fz), 3, ACT_SILU, q + (mode ? ".bun.dw" : ".tdn.dw"), &A(outname), nullptr, nullptr, 0,
+               nullptr, &fused);
+  };
+  for (int d = 0; d < (c.ins_decoder ? 2 : 1); ++d) {
+    const std::string fp = std::string(kBifpn[d]) + "_fpn";
     const T32 p5 = A(pyr[4]);
-    float* pooled;
-    RC(buf32(n, "pooled", (size_t)N * p5.C, &pooled));
-    if (p5.fmt) RC(launch_avgpool_hl32(reinterpret_cast<const half_t*>(p5.p), N, p5.H * p5.W, p5.C, p5.ld, pooled, s));
-    else RC(launch_avgpool_f32(p5.p, N, p5.H * p5.W, p5.C, p5.ld, pooled, s));
-    const char* decs[2] = {"semantic_decoder", "instance_decoder"};
-    // plane region: branch i of BOTH decoders as one launch (weights stacked along Cout at finalize, two destinations)
-    const bool merged_aspp = p5.fmt && c.ins_decoder && n->w32.count("decoders.aspp.convs.0.0") && n->w32.count("decoders.aspp.convs.3.0");
-    // below the plane region's threshold (small batches; round 6, late): the branches still run merged on the plane kernel -- K-split
-    // (Conv32::kpart: 32 workgroups x 8 splits for ONE 1024^2 tile) -- from an hl32 copy of p5, into fp32 concat buffers
-    bool small_aspp = false;
-    if (!p5.fmt && n->precision == 2 && n->x3_planes_ready && n->x3_ksplit && n->x3_small_aspp && n->x3_kpart && c.ins_decoder &&
-        n->w32.count("decoders.aspp.convs.0.0") && n->w32.count("decoders.aspp.convs.3.0") && p5.C % 32 == 0) {
-      small_aspp = true;
-      RC(mk("p5.hl32", p5.H, p5.W, p5.C, 1));
-      const T32& ph = A("p5.hl32");
-      RC(launch_hl32_from_f32(p5.p, reinterpret_cast<half_t*>(ph.p), (int64_t)N * p5.H * p5.W, p5.C, p5.ld, ph.ld, s));
-      for (int d = 0; d < 2; ++d) RC(mk(std::string(decs[d]) + ".aspp.cat", p5.H, p5.W, 4 * n->aspp_ch, 0));
-      const T32 &c0 = A("semantic_decoder.aspp.cat"), &c1 = A("instance_decoder.aspp.cat");
-      for (int i = 0; i <= 3; ++i) {
-        const int r = i ? c.atrous_rates[i - 1] : 1;
-        RC(c32(n, "decoders.aspp.convs." + std::to_string(i) + ".0", ph, 0, c0, i * n->aspp_ch, s,
-            {.pad = i ? r : 0, .dil = r, .act = ACT_RELU, .out2 = &c1, .out2_coff = i * n->aspp_ch, .split2 = n->aspp_ch}));
-      }
+    RC(mk(fp + ".p6pre", p5.H, p5.W, F));
+    RC(c32(n, fp + ".p6_resample.conv.0", p5, 0, A(fp + ".p6pre"), 0, s));
+    RC(mk(fp + ".in.P6", p5.H / 2, p5.W / 2, F));
+    RC(launch_maxpool3x3s2_f32(A(fp + ".p6pre").p, N, p5.H, p5.W, F, A(fp + ".in.P6").p, s));
+    RC(mk(fp + ".in.P7", p5.H / 4, p5.W / 4, F));
+    RC(launch_maxpool3x3s2_f32(A(fp + ".in.P6").p, N, p5.H / 2, p5.W / 2, F, A(fp + ".in.P7").p, s));
+    std::string feat[5] = {pyr[2], pyr[3], pyr[4], fp + ".in.P6", fp + ".in.P7"};
+    for (int li = 0; li < c.fpn_layers; ++li)
+      RC(bifpn_layer(n, fp + ".bifpns." + std::to_string(li), fp + ".l" + std::to_string(li), feat, resample, node));
+    const std::string dp = std::string(kBifpn[d]) + "_decoder";
+    const std::string skips[5] = {feat[3], feat[2], feat[1], feat[0], "p2f"};
+    std::string xx = feat[4];
+    for (int i = 0; i < 5; ++i) {
+      const T32 in = A(xx);
+      const std::string cn = dp + ".cat" + std::to_string(i);
+      RC(mk(cn, in.H * 2, in.W * 2, 2 * F));
+      RC(c32(n, dp + ".upsamplings." + std::to_string(i) + ".0", in, 0, A(cn), 0, s, {.act = ACT_RELU, .ps_cout = F}));
+      const T32 sk = A(skips[i]);
+      RC(launch_bilinear_ac_f32_nhwc(sk.p, N, sk.H, sk.W, F, sk.ld, A(cn).p + F, sk.H, sk.W, 2 * F, s));      // same size: copy
+      xx = cn;
     }
-    if (merged_aspp) {
-      for (int d = 0; d < 2; ++d) RC(mk(std::string(decs[d]) + ".aspp.cat", p5.H, p5.W, 4 * n->aspp_ch, 1));
-      const T32 &c0 = A("semantic_decoder.aspp.cat"), &c1 = A("instance_decoder.aspp.cat");
-      for (int i = 0; i <= 3; ++i) {
-        const int r = i ? c.atrous_rates[i - 1] : 1;
-        RC(c32(n, "decoders.aspp.convs." + std::to_string(i) + ".0", p5, 0, c0, i * n->aspp_ch, s,
-            {.pad = i ? r : 0, .dil = r, .act = ACT_RELU, .out2 = &c1, .out2_coff = i * n->aspp_ch, .split2 = n->aspp_ch}));
-      }
-    }
-    // the decoders' low-level projections, both decoders in one launch where finalize32 stacked their weights: the .cat buffers of
-    // both decoders exist before the loop below fills their up-sampled halves
-    bool proj_done[3] = {false, false, false};
-    if (n->precision == 2 && c.ins_decoder) {
-      int xch0 = n->aspp_ch;
-      for (int i = 0; i < c.n_stages; ++i) {
-        const std::string wn = "decoders.project." + std::to_string(i) + ".0";
-        if (n->w32.count(wn)) {
-          const T32 low = A(pyr[c.low_level_stages[i]]);
-          const int cps = round_up(xch0 + c.low_level_proj_sem[i], 32), cpi = round_up(xch0 + c.low_level_proj_ins[i], 32);
-          const std::string qs = std::string(decs[0]) + ".stage" + std::to_string(i), qi = std::string(decs[1]) + ".stage" + std::to_string(i);
-          RC(mk(qs + ".cat", low.H, low.W, cps));
-          RC(mk(qi + ".cat", low.H, low.W, cpi));
-          if (!low.fmt && xch0 % 4 == 0) {
-            RC(c32(n, wn, low, 0, A(qs + ".cat"), xch0, s,
-                {.act = ACT_RELU, .out2 = &A(qi + ".cat"), .out2_coff = xch0, .split2 = c.low_level_proj_sem[i]}));
-            proj_done[i] = true;
-          }
-        }
-        xch0 = n->dec_ch;
-      }
-    }
-    for (int d = 0; d < (c.ins_decoder ? 2 : 1); ++d) {
-      const std::string p = decs[d];
-      float *poolfeat, *bias_n;
-      RC(buf32(n, p + ".poolfeat", (size_t)N * n->aspp_ch, &poolfeat));
-      RC(buf32(n, p + ".bias_n", (size_t)N * n->aspp_ch, &bias_n));
-      RC(launch_gemv(pooled, N, p5.C, n->f32w.at(p + ".pool.w"), nullptr, n->aspp_ch, 1, poolfeat, s));
-      RC(launch_gemv(poolfeat, N, n->aspp_ch, n->f32w.at(p + ".projpool.w"), nullptr, n->aspp_ch, 0, bias_n, s));
-      if (!merged_aspp && !small_aspp) {
-        RC(mk(p + ".aspp.cat", p5.H, p5.W, 4 * n->aspp_ch, p5.fmt));      // (the projection reads it as it was written; its output is fp32: the up-sampler's input)
-        RC(c32(n, p + ".aspp.convs.0.0", p5, 0, A(p + ".aspp.cat"), 0, s, {.act = ACT_RELU}));
-        for (int i = 1; i <= 3; ++i) {
-          const int r = c.atrous_rates[i - 1];
-          RC(c32(n, p + ".aspp.convs." + std::to_string(i) + ".0", p5, 0, A(p + ".aspp.cat"), i * n->aspp_ch, s,
-              {.pad = r, .dil = r, .act = ACT_RELU}));
-        }
-      }
-      RC(mk(p + ".aspp", p5.H, p5.W, n->aspp_ch));
-      RC(c32(n, p + ".aspp.project.0", A(p + ".aspp.cat"), 0, A(p + ".aspp"), 0, s, {.act = ACT_RELU, .bias_n = bias_n}));
-      std::string xx = p + ".aspp";
-      int xch = n->aspp_ch;
-      for (int i = 0; i < c.n_stages; ++i) {
+    const T32 cat = A(xx);
+    RC(mk(dp + ".out", cat.H, cat.W, F));
+    bool fused = false;
+    RC(sep(dp + ".fusion.0.sepconv", cat, 5, ACT_RELU, dp + ".dw", &A(dp + ".out"), nullptr, nullptr, 0, nullptr, &fused));
+    dec_out[d] = dp + ".out";
+  }
+  return EMP_OK;
+}
+
+// ASPP branch i of BOTH decoders as one launch on the plane kernel (weights stacked along Cout at finalize, two destinations): src is p5
+// as an hl32 map, the concat buffers are made in format fmt
+int Fwd32::merged_aspp(const T32& src, int fmt) {
+  for (int d = 0; d < 2; ++d) RC(mk(std::string(kDecoders[d]) + ".aspp.cat", src.H, src.W, 4 * n->aspp_ch, fmt));
+  const T32 &c0 = A(std::string(kDecoders[0]) + ".aspp.cat"), &c1 = A(std::string(kDecoders[1]) + ".aspp.cat");
+  for (int i = 0; i <= 3; ++i) {
+    const int r = i ? c.atrous_rates[i - 1] : 1;
+    RC(c32(n, "decoders.aspp.convs." + std::to_string(i) + ".0", src, 0, c0, i * n->aspp_ch, s,
+        {.pad = i ? r : 0, .dil = r, .act = ACT_RELU, .out2 = &c1, .out2_coff = i * n->aspp_ch, .split2 = n->aspp_ch}));
+  }
+  return EMP_OK;
+}
+
+// ---- Panoptic-DeepLab decoders (decoders/panoptic_deeplab.py:68-80, aspp.py:96-102) ----
+int Fwd32::deeplab_decoders() {
+  const T32 p5 = A(pyr[4]);
+  float* pooled;
+  RC(buf32(n, "pooled", (size_t)N * p5.C, &pooled));
+  if (p5.fmt) RC(launch_avgpool_hl32(reinterpret_cast<const half_t*>(p5.p), N, p5.H * p5.W, p5.C, p5.ld, pooled, s));
+  else RC(launch_avgpool_f32(p5.p, N, p5.H * p5.W, p5.C, p5.ld, pooled, s));
+  // plane region: the ASPP branches of both decoders merged, from the hl32 p5 into hl32 concat buffers
+  const bool have_merged = c.ins_decoder && n->w32.count("decoders.aspp.convs.0.0") && n->w32.count("decoders.aspp.convs.3.0");
+  const bool merged = p5.fmt && have_merged;
+  // below the plane region's threshold (small batches; round 6, late): the branches still run merged on the plane kernel -- K-split
+  // (Conv32::kpart: 32 workgroups x 8 splits for ONE 1024^2 tile) -- from an hl32 copy of p5, into fp32 concat buffers
+  const bool small = !p5.fmt && n->precision == 2 && n->x3_planes_ready && n->x3_ksplit && n->x3_small_aspp && n->x3_kpart && have_merged &&
+                     p5.C % 32 == 0;
+  if (small) {
+    RC(mk("p5.hl32", p5.H, p5.W, p5.C, 1));
+    const T32& ph = A("p5.hl32");
+    RC(launch_hl32_from_f32(p5.p, reinterpret_cast<half_t*>(ph.p), (int64_t)N * p5.H * p5.W, p5.C, p5.ld, ph.ld, s));
+    RC(merged_aspp(ph, 0));
+  }
+  if (merged) RC(merged_aspp(p5, 1));
+  // the decoders' low-level projections, both decoders in one launch where finalize32 stacked their weights: the .cat buffers of
+  // both decoders exist before the loop below fills their up-sampled halves
+  bool proj_done[3] = {false, false, false};
+  if (n->precision == 2 && c.ins_decoder) {
+    int xch0 = n->aspp_ch;
+    for (int i = 0; i < c.n_stages; ++i) {
+      const std::string wn = "decoders.project." + std::to_string(i) + ".0";
+      if (n->w32.count(wn)) {
         const T32 low = A(pyr[c.low_level_stages[i]]);
-        const int lp = d == 0 ? c.low_level_proj_sem[i] : c.low_level_proj_ins[i];
-        const int cpad = round_up(xch + lp, n->precision == 2 ? 32 : 16);      // (finalize32 packed the block's weights for this width)
-        const std::string q = p + ".stage" + std::to_string(i);
-        RC(mk(q + ".cat", low.H, low.W, cpad));
-        const T32 xa = A(xx);
-        RC(launch_bilinear_ac_f32_nhwc(xa.p, N, xa.H, xa.W, xch, xa.ld, A(q + ".cat").p, low.H, low.W, cpad, s));
-        if (!proj_done[i]) RC(c32(n, p + ".project." + std::to_string(i) + ".0", low, 0, A(q + ".cat"), xch, s, {.act = ACT_RELU}));
-        RC(mk(q + ".out", low.H, low.W, n->dec_ch));
-        bool fused = false;
-        RC(sep(p + ".fuse." + std::to_string(i) + ".0.sepconv", A(q + ".cat"), 5, ACT_RELU, q + ".dw", &A(q + ".out"), nullptr, nullptr, 0, nullptr, &fused));
-        xx = q + ".out";
-        xch = n->dec_ch;
+        const int cps = round_up(xch0 + c.low_level_proj_sem[i], 32), cpi = round_up(xch0 + c.low_level_proj_ins[i], 32);
+        const std::string qs = std::string(kDecoders[0]) + ".stage" + std::to_string(i), qi = std::string(kDecoders[1]) + ".stage" + std::to_string(i);
+        RC(mk(qs + ".cat", low.H, low.W, cps));
+        RC(mk(qi + ".cat", low.H, low.W, cpi));
+        if (!low.fmt && xch0 % 4 == 0) {
+          RC(c32(n, wn, low, 0, A(qs + ".cat"), xch0, s,
+              {.act = ACT_RELU, .out2 = &A(qi + ".cat"), .out2_coff = xch0, .split2 = c.low_level_proj_sem[i]}));
+          proj_done[i] = true;
+        }
       }
-      dec_out[d] = xx;
+      xch0 = n->dec_ch;
     }
   }
-  if (!c.ins_decoder) dec_out[1] = dec_out[0];
+  for (int d = 0; d < (c.ins_decoder ? 2 : 1); ++d) {
+    const std::string p = kDecoders[d];
+    float *poolfeat, *bias_n;
+    RC(buf32(n, p + ".poolfeat", (size_t)N * n->aspp_ch, &poolfeat));
+    RC(buf32(n, p + ".bias_n", (size_t)N * n->aspp_ch, &bias_n));
+    RC(launch_gemv(pooled, N, p5.C, n->f32w.at(p + ".pool.w"), nullptr, n->aspp_ch, 1, poolfeat, s));
+    RC(launch_gemv(poolfeat, N, n->aspp_ch, n->f32w.at(p + ".projpool.w"), nullptr, n->aspp_ch, 0, bias_n, s));
+    if (!merged && !small) {
+      RC(mk(p + ".aspp.cat", p5.H, p5.W, 4 * n->aspp_ch, p5.fmt));      // (the projection reads it as it was written; its output is fp32: the up-sampler's input)
+      RC(c32(n, p + ".aspp.convs.0.0", p5, 0, A(p + ".aspp.cat"), 0, s, {.act = ACT_RELU}));
+      for (int i = 1; i <= 3; ++i) {
+        const int r = c.atrous_rates[i - 1];
+        RC(c32(n, p + ".aspp.convs." + std::to_string(i) + ".0", p5, 0, A(p + ".aspp.cat"), i * n->aspp_ch, s,
+            {.pad = r, .dil = r, .act = ACT_RELU}));
+      }
+    }
+    RC(mk(p + ".aspp", p5.H, p5.W, n->aspp_ch));
+    RC(c32(n, p + ".aspp.project.0", A(p + ".aspp.cat"), 0, A(p + ".aspp"), 0, s, {.act = ACT_RELU, .bias_n = bias_n}));
+    std::string xx = p + ".aspp";
+    int xch = n->aspp_ch;
+    for (int i = 0; i < c.n_stages; ++i) {
+      const T32 low = A(pyr[c.low_level_stages[i]]);
+      const int lp = d == 0 ? c.low_level_proj_sem[i] : c.low_level_proj_ins[i];
+      const int cpad = round_up(xch + lp, n->precision == 2 ? 32 : 16);      // (finalize32 packed the block's weights for this width)
+      const std::string q = p + ".stage" + std::to_string(i);
+      RC(mk(q + ".cat", low.H, low.W, cpad));
+      const T32 xa = A(xx);
+      RC(launch_bilinear_ac_f32_nhwc(xa.p, N, xa.H, xa.W, xch, xa.ld, A(q + ".cat").p, low.H, low.W, cpad, s));
+      if (!proj_done[i]) RC(c32(n, p + ".project." + std::to_string(i) + ".0", low, 0, A(q + ".cat"), xch, s, {.act = ACT_RELU}));
+      RC(mk(q + ".out", low.H, low.W, n->dec_ch));
+      bool fused = false;
+      RC(sep(p + ".fuse." + std::to_string(i) + ".0.sepconv", A(q + ".cat"), 5, ACT_RELU, q + ".dw", &A(q + ".out"), nullptr, nullptr, 0, nullptr, &fused));
+      xx = q + ".out";
+      xch = n->dec_ch;
+    }
+    dec_out[d] = xx;
+  }
+  return EMP_OK;
+}
+
+// ---- heads (heads.py:12-19) ----
+int Fwd32::heads() {
   const T32 semx = A(dec_out[0]), insx = A(dec_out[1]);
   const int hq = semx.H, wq = semx.W;
   EMP_REQUIRE(hq * 4 == H && wq * 4 == W, "the decoder output must be at 1/4 resolution (got %dx%d)", hq, wq);
-  // ---- heads (heads.py:12-19) ----
-  const char* heads[3] = {"semantic_head", "ins_center", "ins_xy"};
-  const int hc[3] = {n->ncls, 1, 2};
-  float* head_out[3];
   for (int k = 0; k < 3; ++k) {
-    const std::string p = heads[k];
+    const std::string p = kHeads[k];
+    const int hc = head_planes(n, k);
     const T32& xin = k == 0 ? semx : insx;
     float* dst;
-    RC(buf32(n, p + ".out", (size_t)N * hc[k] * hq * wq, &dst));
+    RC(buf32(n, p + ".out", (size_t)N * hc * hq * wq, &dst));
     if (k == 1 && !interp) dst = o_ctr;
     if (k == 2 && !interp) dst = o_off;
     head_out[k] = dst;
     // fp16x3 mode, round 6: depthwise + pointwise + ReLU + the head's 1x1 in one launch (sepconv_x3.hip, head_c <= 2); else the depthwise half
     bool fused = false;
-    RC(sep(p + ".head.0.0.sepconv", xin, 5, ACT_RELU, p + ".dw", nullptr, n->f32w.at(p + ".head.1.w"), n->f32w.at(p + ".head.1.b"), hc[k], dst, &fused));
+    RC(sep(p + ".head.0.0.sepconv", xin, 5, ACT_RELU, p + ".dw", nullptr, n->f32w.at(p + ".head.1.w"), n->f32w.at(p + ".head.1.b"), hc, dst, &fused));
     if (fused) {
-      n->flops += 2.0 * (double)N * hq * wq * n->dec_ch * hc[k];
+      n->flops += 2.0 * (double)N * hq * wq * n->dec_ch * hc;
       continue;
     }
-    if (n->precision == 2 && n->x3_fuse_head && hc[k] <= 4) {
+    if (n->precision == 2 && n->x3_fuse_head && hc <= 4) {
       // fp16x3 mode: the head's 1x1 inside the pointwise conv's epilogue (conv16x3.hip HEAD): the dec_ch-wide map is
       // neither written nor read back; every cout tile leaves per-pixel partial sums, added in ascending order
       const int tiles = conv16x3_cout_tiles(n->dec_ch);
       float* part;
-      RC(buf32(n, p + ".part", (size_t)tiles * N * hq * wq * hc[k], &part));
+      RC(buf32(n, p + ".part", (size_t)tiles * N * hq * wq * hc, &part));
       RC(c32(n, p + ".head.0.0.sepconv.1", A(p + ".dw"), 0, A(p + ".dw"), 0, s,
-          {.act = ACT_RELU, .head_w = n->f32w.at(p + ".head.1.w"), .head_part = part, .head_c = hc[k]}));
-      RC(launch_head_finish_f32(part, tiles, N, hq * wq, hc[k], n->f32w.at(p + ".head.1.b"), dst, s));
+          {.act = ACT_RELU, .head_w = n->f32w.at(p + ".head.1.w"), .head_part = part, .head_c = hc}));
+      RC(launch_head_finish_f32(part, tiles, N, hq * wq, hc, n->f32w.at(p + ".head.1.b"), dst, s));
     } else {
       RC(mk(p + ".pw", hq, wq, n->dec_ch));
       RC(c32(n, p + ".head.0.0.sepconv.1", A(p + ".dw"), 0, A(p + ".pw"), 0, s, {.act = ACT_RELU}));
       RC(launch_head1x1_f32(A(p + ".pw").p, N, hq * wq, n->dec_ch, n->dec_ch, n->f32w.at(p + ".head.1.w"), n->f32w.at(p + ".head.1.b"),
-                              hc[k], dst, (int64_t)hq * wq, nullptr, s));
+                              hc, dst, (int64_t)hq * wq, nullptr, s));
     }
-    n->flops += 2.0 * (double)N * hq * wq * n->dec_ch * hc[k];
+    n->flops += 2.0 * (double)N * hq * wq * n->dec_ch * hc;
   }
   if (interp) {
     RC(launch_bilinear_ac_f32_nchw(head_out[1], N * 1, hq, wq, o_ctr, 4, s));
     RC(launch_bilinear_ac_f32_nchw(head_out[2], N * 2, hq, wq, o_off, 4, s));
   }
-  // ---- PointRend subdivision (point_rend.py:241-269, eval) ----
+  return EMP_OK;
+}
+
+// ---- PointRend subdivision (point_rend.py:241-269, eval) ----
+int Fwd32::pointrend() {
+  const T32 semx = A(dec_out[0]);
+  const int hq = semx.H, wq = semx.W;
   const int P = c.subdivision_num_points;
   const int ldp = round_up(n->dec_ch + n->ncls, 16);
   const float* coarse = head_out[0];
@@ -859,6 +804,29 @@ int run32(emp_pdl* n, const void* img, int dtype, float sub, float mul, int N, i
     cur = nxt;
   }
   return EMP_OK;
+}
+
+}  // namespace
+
+namespace emp {
+
+int run32(emp_pdl* n, const void* img, int dtype, float sub, float mul, int N, int H, int W, int vh, int vw, int RS, int interp,
+          float* o_sem, float* o_ctr, float* o_off, hipStream_t s) {
+  const emp_pdl_config& c = n->cfg;
+  EMP_REQUIRE(N > 0 && H > 0 && W > 0 && H % 16 == 0 && W % 16 == 0, "forward: H=%d W=%d must be positive multiples of 16", H, W);
+  EMP_REQUIRE(RS >= 1 && RS <= 6, "render_steps=%d out of range", RS);
+  EMP_REQUIRE(c.arch == 0 || (H % 128 == 0 && W % 128 == 0), "BiFPN forward: H=%d W=%d must be multiples of 128", H, W);
+  n->flops = 0.0;
+  // (an encoder at output stride 32 -- the BiFPN networks -- has a quarter of those tiles in layer4: BiFPN-PR with the region on / off
+  //  492 / 513 tiles/s at batch 8, 594 / 581 at 16, 651 / 631 at 32: its threshold is twice the stride-16 one)
+  const bool hlr = n->precision == 2 && n->x3_planes_ready && c.encoder == 0 &&
+                   ((int64_t)N * (H / 16) * (W / 16)) / 256 >= n->x3_planes_min_tiles * (c.stage4_stride == 32 ? 2 : 1);
+  Fwd32 f{{n, c, img, dtype, sub, mul, N, H, W, vh, vw, RS, interp, o_sem, o_ctr, o_off, s}, hlr};
+  RC(c.encoder == 1 ? f.regnet_encoder() : f.resnet_encoder());
+  RC(c.arch == 1 ? f.bifpn_decoders() : f.deeplab_decoders());
+  if (!c.ins_decoder) f.dec_out[1] = f.dec_out[0];
+  RC(f.heads());
+  return f.pointrend();
 }
 
 }  // namespace emp

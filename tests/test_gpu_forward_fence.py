@@ -1,11 +1,15 @@
 """The forward fence: every schedule branch of csrc/pdl_net.hip / pdl_net32.hip pinned to the bits it produced when
 tests/forward_fence.json was recorded -- the three heads, ``last_flops()``, the EMP_LAYER_LOG text of the forward (fp16
-engine) and, at the small sizes, every tap the engine serves.  No tolerance anywhere: hashes and exact values.
+engine) and, at the small sizes, every tap the engine serves.  No tolerance anywhere: hashes and exact values.  Besides the single
+forwards at render_steps 2: render_steps 1 and 3, and four forwards on ONE model (a smaller batch, the full batch again, another size),
+which pin the heads and ``last_flops()`` of every step.
 
 A refactor of the scheduler (named arguments, shared dispatch helpers, moved files) must leave every case equal in every
 field.  ``python tests/test_gpu_forward_fence.py --record`` rewrites tests/forward_fence.json; the file is re-recorded ONLY
 by a change that means to alter numerics or launches (a new kernel, another fusion rule, another summation order), from
-two recordings in two fresh processes that agree, and its header names the commit and the compiler it was recorded with."""
+two recordings in two fresh processes that agree, and its header names the commit and the compiler it was recorded with.
+``--record --add`` records only the cases the file does not hold yet and lists them, with their commit, under "added": what a
+refactor does FIRST, at its parent commit, for the paths it is about to move."""
 import hashlib
 import json
 import os
@@ -29,8 +33,16 @@ X3_OFF = {k: '0' for k in X3_SWITCHES}
 PLANES1 = {'EMP_X3_PLANES_MIN_TILES': '1'}
 
 
-def _case(net, precision, batch, size, env=None, interp=False, ncls=None):
-    return dict(net=net, precision=precision, batch=batch, size=size, env=env or {}, interp=interp, ncls=ncls)
+def _case(net, precision, batch, size, env=None, interp=False, ncls=None, steps=2):
+    return dict(net=net, precision=precision, batch=batch, size=size, env=env or {}, interp=interp, ncls=ncls, steps=steps)
+
+
+# one model, four forwards: a smaller batch in the planned layout, the full batch again, then another size (a re-plan)
+SEQ = ((2, 256), (1, 256), (2, 256), (1, 384))
+
+
+def _seq(net, precision):
+    return dict(net=net, precision=precision, seq=SEQ, env={}, ncls=None)
 
 
 CASES = {
@@ -58,8 +70,17 @@ CASES = {
     'fp32-mini-b2-256': _case('mini', 'fp32', 2, 256),
     'fp32-regnety-b2-256': _case('regnety', 'fp32', 2, 256),               # squeeze-excite
     'x3-regnety-b2-256': _case('regnety', 'fp16x3', 2, 256),
+    # ---- other render steps: the pr.sem<k> buffers and the sizes that depend on render_steps ----
+    'fp16-pdl-b2-256-rs1': _case('pdl', 'fp16', 2, 256, steps=1),
+    'fp16-pdl-b2-256-rs3': _case('pdl', 'fp16', 2, 256, steps=3),
+    'x3-pdl-b1-384-rs3': _case('pdl', 'fp16x3', 1, 384, steps=3),
+    # ---- re-batch and re-plan on one model (heads and last_flops() per step) ----
+    'fp16-pdl-seq': _seq('pdl', 'fp16'),                                   # rebatch() and the re-plan path
+    'x3-regnety-seq': _seq('regnety', 'fp16x3'),                           # buffer reuse, row tails cleared for a new geometry
+    'fp32-regnety-seq': _seq('regnety', 'fp32'),
 }
 
+HEADS = ('sem_logits', 'ctr_hmp', 'offsets')
 _WEIGHTS = {}
 
 
@@ -83,18 +104,41 @@ def _sha(t):
     return hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()
 
 
-def run_case(name, setenv, delenv, tmpdir):
-    """One forward of case ``name`` -> the record the fence file holds for it."""
+def _input(batch, size):
     import torch
     from empanada_napari_amd import synth
-    from empanada_napari_amd.engines import HipPanopticDeepLab
     from empanada_napari_amd.preprocess import normalize
-    c = CASES[name]
+    return torch.from_numpy(normalize(synth.em_tiles(batch, size, seed=5), 0.57571, 0.12765))[:, None].cuda()
+
+
+def run_seq(c):
+    """The forwards of a sequence case on ONE model -> the heads and last_flops() of every step."""
+    import torch
+    from empanada_napari_amd.engines import HipPanopticDeepLab
     cfg, P = _weights(c['net'], c['ncls'])
+    model = HipPanopticDeepLab(P, cfg, folded=True, precision=c['precision'])
+    assert model.precision == c['precision']
+    steps = []
+    for batch, size in c['seq']:
+        out = model(_input(batch, size), 2, False)
+        torch.cuda.synchronize()
+        steps.append(dict({k: _sha(out[k]) for k in HEADS}, flops=repr(model.last_flops())))
+    del model
+    return {'steps': steps}
+
+
+def run_case(name, setenv, delenv, tmpdir):
+    """The forward(s) of case ``name`` -> the record the fence file holds for it."""
+    import torch
+    from empanada_napari_amd.engines import HipPanopticDeepLab
+    c = CASES[name]
     for k in FP16_SWITCHES + X3_SWITCHES + OTHER:
         delenv(k, raising=False)
     for k, v in c['env'].items():
         setenv(k, v)
+    if 'seq' in c:
+        return run_seq(c)
+    cfg, P = _weights(c['net'], c['ncls'])
     log = os.path.join(str(tmpdir), name + '.layers.log')
     fp16 = c['precision'] == 'fp16'
     if fp16:
@@ -102,10 +146,9 @@ def run_case(name, setenv, delenv, tmpdir):
     model = HipPanopticDeepLab(P, cfg, folded=True, precision=c['precision'])      # the switches are read here
     delenv('EMP_LAYER_LOG', raising=False)
     assert model.precision == c['precision']
-    x = torch.from_numpy(normalize(synth.em_tiles(c['batch'], c['size'], seed=5), 0.57571, 0.12765))[:, None].cuda()
-    out = model(x, 2, c['interp'])
+    out = model(_input(c['batch'], c['size']), c['steps'], c['interp'])
     torch.cuda.synchronize()
-    rec = {k: _sha(out[k]) for k in ('sem_logits', 'ctr_hmp', 'offsets')}
+    rec = {k: _sha(out[k]) for k in HEADS}
     rec['flops'] = repr(model.last_flops())
     if fp16:
         with open(log, 'rb') as f:
@@ -134,9 +177,12 @@ def test_forward_equals_the_recorded_fence(name, monkeypatch, tmp_path):
             assert not diff, f'{name}: taps differ from the fence, first {diff[:5]} of {len(diff)}'
         else:
             assert got.get(field) == want[name].get(field), f'{name}: {field} differs from the fence'
+    if name == 'fp16-pdl-seq':      # the full batch in a fresh plan and again after a smaller one: the single-forward case's bits
+        single = {k: want['fp16-pdl-b2-256'][k] for k in HEADS + ('flops',)}
+        assert got['steps'][0] == single and got['steps'][2] == single, f'{name}: a batch-2 step differs from fp16-pdl-b2-256'
 
 
-def _record(out_path, parent):
+def _record(out_path, parent, add=False):
     import subprocess
     import tempfile
     import conftest  # noqa: F401  (imports the package the way the suite does)
@@ -150,10 +196,16 @@ def _record(out_path, parent):
     hipcc = [line for line in subprocess.run(['hipcc', '--version'], capture_output=True, text=True).stdout.splitlines()
              if 'HIP version' in line or 'clang version' in line]
     doc = {'parent_commit': parent, 'hipcc_version': ' | '.join(hipcc), 'cases': {}}
+    if add:      # cases added later: the entries the file holds stay as they are, the new ones are listed with their commit
+        doc = _fence()
+        new = [name for name in CASES if name not in doc['cases']]
+        doc.setdefault('added', []).append({'parent_commit': parent, 'hipcc_version': ' | '.join(hipcc), 'cases': new})
     with tempfile.TemporaryDirectory() as tmp:
         for name in CASES:
+            if name in doc['cases']:
+                continue
             doc['cases'][name] = run_case(name, setenv, delenv, tmp)
-            print('recorded', name, doc['cases'][name]['flops'], flush=True)
+            print('recorded', name, [r['flops'] for r in doc['cases'][name].get('steps', [doc['cases'][name]])], flush=True)
             with open(out_path, 'w') as f:      # (kept current: a recording that stops half-way leaves what it has)
                 json.dump(doc, f, indent=1, sort_keys=True)
                 f.write('\n')
@@ -163,9 +215,10 @@ if __name__ == '__main__':
     import argparse
     ap = argparse.ArgumentParser()
     ap.add_argument('--record', action='store_true')
+    ap.add_argument('--add', action='store_true', help='record only the cases the fence file does not hold yet')
     ap.add_argument('--out', default=FENCE)
     ap.add_argument('--parent', default='unknown', help='hash of the commit whose sources the library was built from')
     a = ap.parse_args()
     if not a.record:
         sys.exit('run under pytest, or with --record')
-    _record(a.out, a.parent)
+    _record(a.out, a.parent, a.add)
