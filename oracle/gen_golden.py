@@ -2,6 +2,7 @@
 
     python oracle/gen_golden.py            # needs /root/reference, CPU only
     python oracle/gen_golden.py exports    # the TorchScript export fixtures of tests/test_load_export.py
+    python oracle/gen_golden.py exports pdl_single bifpn_single    # ... only the named cases (the others stay untouched)
     python oracle/gen_golden.py postprocess_edges    # the post-processing edge cases of tests/postprocess_case.py
 
 The reference cannot travel to the GPU box, so its outputs on seeded inputs are
@@ -286,6 +287,8 @@ def gen_median():
 
 if __name__ == '__main__':
     which = sys.argv[1:] or ['model', 'bifpn', 'postprocess', 'median']
+    if 'exports' in which:      # what follows 'exports' names export cases ('bifpn' is one), not generators
+        which = which[:which.index('exports') + 1]
     if 'bifpn' in which:
         gen_bifpn()
     torch.manual_seed(0)
@@ -561,14 +564,27 @@ def export_cases():
         'regnet_bifpn_y': ('PanopticBiFPNPR', dict(EXPORT_BIFPN_KW, encoder='regnety_6p4gf', num_classes=3), 128),
         'regnet_pdl_x': ('PanopticDeepLabPR', dict(pdl, encoder='regnetx_6p4gf'), 64),
         'regnet_pdl_y': ('PanopticDeepLabPR', dict(pdl, encoder='regnety_6p4gf'), 64),
+        # the networks of tests/test_gpu_net_configs.py: one decoder (the training widget's ins_decoder=False for a model
+        # without thing classes, empanada_napari/_train.py:203-205) and the reference class's own constructor defaults
+        'pdl_single': ('PanopticDeepLabPR', dict(pdl, ins_decoder=False, num_classes=2), 64),
+        'bifpn_single': ('PanopticBiFPNPR', dict(EXPORT_BIFPN_KW, fpn_layers=3, ins_decoder=False, num_classes=3,
+                                                 subdivision_num_points=8192), 128),
+        'pdl_stages321': ('PanopticDeepLabPR', dict(pdl, low_level_stages=[3, 2, 1], low_level_channels_project=[128, 64, 32],
+                                                    stage4_stride=32), 64),
     }
 
 
-def gen_exports():
+def gen_exports(only=None):
+    """``only``: the case names to write (None: all).  A case's seed is its position in ``export_cases()``, so writing a
+    subset leaves the other fixtures as they are and gives each new case the values a full run would."""
     sys.path.insert(0, os.path.join(ROOT, 'tests'))
     import export_case
     from empanada.models import quantization as quant_models
+    unknown = sorted(set(only or ()) - set(export_cases()))
+    assert not unknown, f'no such export case: {unknown}'
     for i, (case, (arch, kw, size)) in enumerate(export_cases().items()):
+        if only and case not in only:
+            continue
         torch.manual_seed(0)
         model = quant_models.__dict__['Quantizable' + arch](**kw, quantize=False)
         model.eval()
@@ -585,7 +601,7 @@ def gen_exports():
 
 
 if __name__ == '__main__' and 'exports' in sys.argv[1:]:
-    gen_exports()
+    gen_exports(sys.argv[sys.argv.index('exports') + 1:] or None)
 
 
 # ----------------------------------------------------------------------------

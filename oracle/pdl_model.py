@@ -576,7 +576,12 @@ def _tf_sepconv(P, xin, pre, pad, precise, wsplit=False):
 
 
 def _tf_encoder(P, cfg, x, tap):
-    """ResNet-50 part of the teacher-forced check (both network families); returns the pyramid's tap names."""
+    """ResNet-50 part of the teacher-forced check (both network families); returns the pyramid's tap names.  A block's
+    projection shortcut is part of its last launch (conv3 and the shortcut as one GEMM over the concatenated K: one rounding
+    per block) unless EMP_FUSE_DS=0 asks the engine for the two launches: then the shortcut is a map of its own, ``<block>.ds``,
+    rounded to fp16 where it is stored, and conv3 adds it as a residual."""
+    fuse_ds = os.environ.get('EMP_FUSE_DS', '1')[:1] != '0'
+
     def conv(xin, name, stride=1, padding=0, dilation=1, groups=1):
         return _tf_conv(P, xin, name, stride, padding, dilation, groups)
 
@@ -595,7 +600,12 @@ def _tf_encoder(P, cfg, x, tap):
             xin = tap(xname)
             yield pre + '.c1', F.relu(conv(xin, pre + '.conv1')), True
             yield pre + '.c2', F.relu(conv(tap(pre + '.c1'), pre + '.conv2', s, dil, dil)), True
-            idn = conv(xin, pre + '.downsample.0', s) if bidx == 0 else xin
+            idn = xin
+            if bidx == 0 and fuse_ds:
+                idn = conv(xin, pre + '.downsample.0', s)
+            elif bidx == 0:
+                yield pre + '.ds', conv(xin, pre + '.downsample.0', s), True
+                idn = tap(pre + '.ds')
             yield pre, F.relu(conv(tap(pre + '.c2'), pre + '.conv3') + idn), True
             xname = pre
         pyr.append(xname)
@@ -605,12 +615,14 @@ def _tf_encoder(P, cfg, x, tap):
 def _tf_heads(P, semx, insx, tap, ins_decoder=True, wsplit=False, bifpn=False):
     """heads.py:12-19 on the engine's decoder outputs: 5x5 separable conv + ReLU + fp32 1x1.  The engine fuses the
     whole head into one launch when it has at most two output planes (the 256-channel map then never leaves the CU,
-    fp32); a wider head (multi-class semantic) stores that map in fp16 as ``<head>.pw`` and runs the 1x1 from it."""
+    fp32); a wider head (multi-class semantic) stores that map in fp16 as ``<head>.pw`` and runs the 1x1 from it -- and so
+    does every head when EMP_FUSE_SEPCONV=0 takes the fused kernels away (``sepblock``'s depthwise launch + conv pair)."""
+    fused = os.environ.get('EMP_FUSE_SEPCONV', '1')[:1] != '0'
     for head, xin in (('semantic_head', semx), ('ins_center', insx), ('ins_xy', insx)):
         w, b = _tf_weights(P, f'{head}.head.1', fp32=True)
-        prec = precise_block(f'{head}.head.0.0', ins_decoder, bifpn) and w.shape[0] <= 2
+        prec = precise_block(f'{head}.head.0.0', ins_decoder, bifpn) and w.shape[0] <= 2 and fused
         y = F.relu(_tf_sepconv(P, xin, f'{head}.head.0.0', 2, prec, wsplit))
-        if w.shape[0] > 2:
+        if w.shape[0] > 2 or not fused:
             yield head + '.pw', y, True
             y = tap(head + '.pw')
         yield head + '.out', F.conv2d(y, w, b), False

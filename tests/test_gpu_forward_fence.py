@@ -33,9 +33,13 @@ X3_OFF = {k: '0' for k in X3_SWITCHES}
 PLANES1 = {'EMP_X3_PLANES_MIN_TILES': '1'}
 
 
-def _case(net, precision, batch, size, env=None, interp=False, ncls=None, steps=2):
-    return dict(net=net, precision=precision, batch=batch, size=size, env=env or {}, interp=interp, ncls=ncls, steps=steps)
+def _case(net, precision, batch, size, env=None, interp=False, ncls=None, steps=2, cfg=None):
+    """cfg: changes to the network's configuration (the seeded parameters follow it)"""
+    return dict(net=net, precision=precision, batch=batch, size=size, env=env or {}, interp=interp, ncls=ncls, steps=steps, cfg=cfg or {})
 
+
+SINGLE = {'ins_decoder': False}
+STAGES321 = {'low_level_stages': [3, 2, 1], 'low_level_channels_project': [128, 64, 32], 'stage4_stride': 32}
 
 # one model, four forwards: a smaller batch in the planned layout, the full batch again, then another size (a re-plan)
 SEQ = ((2, 256), (1, 256), (2, 256), (1, 384))
@@ -78,15 +82,22 @@ CASES = {
     'fp16-pdl-seq': _seq('pdl', 'fp16'),                                   # rebatch() and the re-plan path
     'x3-regnety-seq': _seq('regnety', 'fp16x3'),                           # buffer reuse, row tails cleared for a new geometry
     'fp32-regnety-seq': _seq('regnety', 'fp32'),
+    # ---- one decoder, and more than one fuse stage (change detectors; the evidence is tests/test_gpu_net_configs.py) ----
+    'fp16-pdl-single-b2-256': _case('pdl', 'fp16', 2, 256, ncls=2, cfg=SINGLE),          # semantic_decoder. is the precise site, one stream
+    'fp16-mini-single-b2-256': _case('mini', 'fp16', 2, 256, ncls=3, cfg=SINGLE),        # precise hi + lo semantic nodes, the .pw head
+    'x3-pdl-single-b1-384': _case('pdl', 'fp16x3', 1, 384, ncls=2, cfg=SINGLE),          # no merged projection, no merged ASPP
+    'fp32-pdl-single-b2-256': _case('pdl', 'fp32', 2, 256, ncls=2, cfg=SINGLE),
+    'fp16-pdl-stages321-b2-256': _case('pdl', 'fp16', 2, 256, cfg=STAGES321),            # three stages, layer4 at stride 2
 }
 
 HEADS = ('sem_logits', 'ctr_hmp', 'offsets')
 _WEIGHTS = {}
 
 
-def _weights(net, ncls):
+def _weights(net, ncls, change=None):
     """(cfg, folded parameters) of a case's network, built once per process"""
-    key = (net, ncls)
+    change = change or {}
+    key = (net, ncls, repr(sorted(change.items())))
     if key not in _WEIGHTS:
         from empanada_napari_amd import weights
         if net in ('regnetx', 'regnety'):
@@ -96,6 +107,7 @@ def _weights(net, ncls):
             cfg = dict(weights.MITONET_PDL_CFG if net == 'pdl' else weights.MITONET_MINI_CFG)
             if ncls is not None:
                 cfg['num_classes'] = ncls
+            cfg.update(change)
             _WEIGHTS[key] = cfg, weights.fold_state_dict(weights.seeded_state_dict(cfg, seed=0 if net == 'pdl' else 3), cfg)
     return _WEIGHTS[key]
 
@@ -138,7 +150,7 @@ def run_case(name, setenv, delenv, tmpdir):
         setenv(k, v)
     if 'seq' in c:
         return run_seq(c)
-    cfg, P = _weights(c['net'], c['ncls'])
+    cfg, P = _weights(c['net'], c['ncls'], c.get('cfg'))
     log = os.path.join(str(tmpdir), name + '.layers.log')
     fp16 = c['precision'] == 'fp16'
     if fp16:

@@ -30,6 +30,8 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_common import teacher_forced_rows as _teacher_forced_rows
+
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-3          # BASELINE.json north_star: "within 1e-3 on the float semantic/center heatmaps"
@@ -320,31 +322,6 @@ def test_bifpn_512_tile_vs_fp32_forward(ncls):
     print(f'BiFPN ({ncls} class) 512^2 vs fp32 oracle:', rep)
     _report(f'bifpn_512_ncls{ncls}', rep)
     assert rep['prob']['frac_over_1e2'] < 2e-2          # PointRend selection flips only
-
-
-def _teacher_forced_rows(gen, tap, fp32_heads):
-    """Shared assertion loop of the teacher-forced checks: one fp16 ulp (+1e-4 of the map's scale for the rounded
-    depthwise intermediate) where the engine stores fp16, 1e-4 of the scale on the fp32 heads."""
-    from oracle import pdl_model
-    rows = []
-    for name, want, rounds in gen:
-        rms = float(want.pow(2).mean().sqrt())
-        if rounds:
-            got = tap(name)[:, :want.shape[1]]
-            w16 = pdl_model.Fp16Emu.r16(want)
-            d = (got - w16).abs()
-            ulp = torch.maximum(want.abs(), torch.tensor(2.0 ** -14)) * 2.0 ** -10
-            excess = float((d - ulp - 1e-4 * max(1.0, rms)).max())
-            flips = float((got != w16).float().mean())
-            rows.append((name, rms, float(d.max()), flips, float((d / (ulp + 1e-4 * max(1.0, rms))).max())))
-            assert excess <= 0, f'{name}: off by more than one fp16 ulp (max |d| {float(d.max()):.3e}, rms {rms:.3f})'
-            assert flips < 0.05, f'{name}: {flips:.3%} of the elements differ from the correctly rounded result'
-        else:
-            got = fp32_heads[name]
-            d = float((got - want).abs().max())
-            rows.append((name, rms, d, 0.0, 0.0))
-            assert d < 1e-4 * max(1.0, rms), f'{name}: fp32 head off by {d:.3e} (rms {rms:.3f})'
-    return rows
 
 
 @pytest.mark.parametrize('ncls', [1, 4])

@@ -31,7 +31,7 @@ PDL_KW = dict(encoder='resnet50', num_classes=1, stage4_stride=16, decoder_chann
               importance_sample_ratio=0.75, subdivision_steps=2, subdivision_num_points=8192)
 
 
-@pytest.mark.parametrize('variant', ['default', 'odd', 'ratio'])
+@pytest.mark.parametrize('variant', ['default', 'odd', 'ratio', 'single', 'stages321'])
 def test_panoptic_deeplab_export_is_loaded_without_arch(tmp_path, variant):
     from empanada_napari_amd import inference, weights
     kw = dict(PDL_KW)
@@ -41,6 +41,10 @@ def test_panoptic_deeplab_export_is_loaded_without_arch(tmp_path, variant):
         kw.update(num_classes=3, decoder_channels=128, aspp_channels=192, low_level_stages=[2, 1],
                   low_level_channels_project=[64, 32], atrous_rates=[3, 6, 9], stage4_stride=32, num_fc=2,
                   subdivision_num_points=4096)
+    if variant == 'single':   # a model without thing classes (empanada_napari/_train.py:203-205): no instance decoder in the export
+        kw.update(ins_decoder=False, num_classes=2)
+    if variant == 'stages321':   # the reference class's own constructor defaults: three fuse stages, layer4 at stride 2
+        kw.update(low_level_stages=[3, 2, 1], low_level_channels_project=[128, 64, 32], stage4_stride=32)
     path, x, want = _export(f'pdl_{variant}', tmp_path)
     sd, cfg = inference.load_model_spec({'model': path})
     assert cfg['arch'] == 'PanopticDeepLabPR' and cfg['encoder'] == 'resnet50'
@@ -48,8 +52,11 @@ def test_panoptic_deeplab_export_is_loaded_without_arch(tmp_path, variant):
               'stage4_stride', 'ins_decoder', 'num_fc', 'subdivision_num_points'):
         assert cfg[k] == kw[k], (k, cfg[k], kw[k])
     assert (cfg['aspp_channels'] or cfg['decoder_channels']) == (kw['aspp_channels'] or kw['decoder_channels'])
-    assert variant == 'ratio' or cfg['ins_ratio'] == 0.5
-    assert weights.ins_projection_widths(cfg) == [int(s * kw['ins_ratio']) for s in kw['low_level_channels_project']]
+    if variant == 'single':   # nothing of an instance decoder: not in the export, not in the spec the loader builds from it
+        assert not any(k.startswith('instance_') for k in list(sd) + list(weights.fold_state_dict(sd, cfg)))
+    else:
+        assert variant == 'ratio' or cfg['ins_ratio'] == 0.5
+        assert weights.ins_projection_widths(cfg) == [int(s * kw['ins_ratio']) for s in kw['low_level_channels_project']]
     P = weights.fold_state_dict(sd, cfg)          # strict: every layer of the spec is found with the spec's shape
     assert len(P) == len(weights.model_spec(cfg))
     # and the folded parameters reproduce the export: oracle forward (pinned by tests/golden) == the scripted model
@@ -60,16 +67,28 @@ def test_panoptic_deeplab_export_is_loaded_without_arch(tmp_path, variant):
 
 
 def test_panoptic_bifpn_export_is_loaded_without_arch(tmp_path):
+    _bifpn_export_is_loaded_without_arch(tmp_path, 'bifpn')
+
+
+def test_single_decoder_bifpn_export_is_loaded_without_arch(tmp_path):
+    """MitoNet_v1_mini's layers and points, three classes, no instance FPN / decoder"""
+    _bifpn_export_is_loaded_without_arch(tmp_path, 'bifpn_single', num_classes=3, fpn_layers=3, ins_decoder=False,
+                                         subdivision_num_points=8192)
+
+
+def _bifpn_export_is_loaded_without_arch(tmp_path, case, **changes):
     from empanada_napari_amd import inference, weights
     kw = dict(encoder='resnet50', num_classes=4, fpn_dim=128, fpn_layers=2, ins_decoder=True, depthwise=True, num_fc=3,
               train_num_points=1024, oversample_ratio=3, importance_sample_ratio=0.75, subdivision_steps=2,
               subdivision_num_points=2048)
-    path, x, want = _export('bifpn', tmp_path)
+    kw.update(changes)
+    path, x, want = _export(case, tmp_path)
     sd, cfg = inference.load_model_spec({'model': path})
     assert cfg['arch'] == 'PanopticBiFPNPR'
     for k in ('num_classes', 'fpn_dim', 'fpn_layers', 'ins_decoder', 'num_fc', 'subdivision_num_points'):
         assert cfg[k] == kw[k], (k, cfg[k], kw[k])
     P = weights.fold_state_dict(sd, cfg)
+    assert kw['ins_decoder'] or not any(k.startswith('instance_') for k in list(sd) + list(P))
     assert len(P) == len(weights.model_spec(cfg))
     from oracle import pdl_model
     got = pdl_model.model_forward(P, x, cfg, 2, False)
