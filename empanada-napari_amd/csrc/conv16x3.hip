@@ -5,9 +5,12 @@
 // within 1e-4 in the max norm but runs on the exact fp32 matrix pipe at 1/16 of the fp16 rate.  This kernel is the fp32
 // mode's convolution on the FP16 matrix pipe: same operands (NHWC fp32 maps, fp32 weights [Cout][KH*KW][Cin16]), same
 // epilogue, same launch contract (`Conv32`); every operand is split into an fp16 pair,
-//     x = hi + lo,   hi = fp16(x),   lo = fp16(x - hi)          (22 significant bits: 2^-22 relative)
-// and every product is three MFMAs into one fp32 accumulator:  w_lo . x_hi  +  w_hi . x_lo  +  w_hi . x_hi  (the
-// w_lo . x_lo term is 2^-22 of the product: dropped).  3 x 1/16 of the fp32 pipe's time for the same result to ~1e-6
+//     x = hi + lo,   hi = fp16(x),   lo = fp16(x - hi)
+// (the pair holds x to 2^-22 RELATIVE for 2^-3 <= |x| < 65520; below 2^-3 lo is an fp16 subnormal and the pair is off by up
+// to an ABSOLUTE 2^-25; from 2^-25 down it is zero; at and above 65520 hi is infinite.  The matrix pipe keeps fp16 subnormals:
+// tests/test_gpu_x3_range.py, FINDINGS 99.)
+// Every product is three MFMAs into one fp32 accumulator:  w_lo . x_hi  +  w_hi . x_lo  +  w_hi . x_hi  (the
+// w_lo . x_lo term is at most 2^-22 of the product: dropped).  3 x 1/16 of the fp32 pipe's time for the same result to ~1e-6
 // relative per term -- the heads stay within 1e-3 of the fp32 forward in the MAX norm (tests/test_gpu_fp16x3.py: 2e-5).
 //
 // Tile: 128 pixels x BN couts (128 or 64), K walked tap-major in steps of 32 channels (two
@@ -17,7 +20,9 @@
 // XOR chunk swizzle: conflict-free ds_read_b128 fragments and 128 contiguous bytes per ds_write_b128 lane group).  Activations are split in the kernel (5 vector ops per element); weights arrive either as fp32 (the C ABI's
 // emp_conv2d_nhwc_f16x3) or already split -- `Conv32::wpair`, one uint32 per weight = hi | lo << 16, made once at
 // emp_pdl_finalize by split_pairs -- and then only change lanes (v_perm).
-// Values must fit fp16's range (|x| <= 65504), as every map of the fp16 engine does.
+// Values must fit fp16's range (|x| < 65520; beyond it the pair is inf - inf, the product NaN, and ReLU's fmaxf turns that into
+// a silent 0), as every map of the fp16 engine does -- and the result keeps its relative accuracy only while operands stay
+// above ~2^-3 in magnitude: the error of a term is max(2^-22 |x|, 2^-25) |w| + |x| max(2^-22 |w|, 2^-25).
 #include <type_traits>
 
 #include "igemm_common.h"

@@ -4,7 +4,7 @@
 //
 // The reference computes this path in fp32 (empanada/inference/engines.py:248-255; the convolutions that dominate:
 // models/decoders/aspp.py:51-103, models/encoders/resnet.py:109-129).  conv16x3.hip (round 5) computes every product as
-//     w_lo . x_hi  +  w_hi . x_hi  +  w_hi . x_lo        (x = hi + lo, hi = fp16(x), lo = fp16(x - hi): 22 significant bits)
+//     w_lo . x_hi  +  w_hi . x_hi  +  w_hi . x_lo        (x = hi + lo, hi = fp16(x), lo = fp16(x - hi): 2^-22 relative from 2^-3 up, 2^-25 absolute below -- conv16x3.hip)
 // on the fp16 matrix pipe from fp32 maps that every workgroup loads to registers, splits and stores to LDS: 96 fp16 flops per
 // L2 byte on a 128 x 128 tile, 0.28 of the fp16 pipe whole-step.  Here the SPLIT IS DONE BY THE PRODUCER: a map of the
 // stride-16 region (layer3, layer4, ASPP) is kept in HBM as "hl32" rows -- per pixel and per block of 32 channels 64 B of hi

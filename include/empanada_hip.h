@@ -229,9 +229,12 @@ EMP_API int emp_conv2d_nhwc_f32(const float* d_in, int N, int H, int W, int Cin,
 /* The same convolution in the `fp16x3` precision mode (round 5, csrc/conv16x3.hip; emp_pdl_set_precision(net, 2)): the
  * same fp32 operands, every operand split into an fp16 pair x = hi + lo on its way into LDS and every product computed as
  * w_lo.x_hi + w_hi.x_lo + w_hi.x_hi on the FP16 matrix pipe into an fp32 accumulator -- the reference's fp32 result
- * (engines.py:248-255) to ~2^-22 relative per term at three fp16 MFMAs per product instead of sixteen fp16-MFMA times on
- * the fp32 pipe.  groups > 1: Cout and Cin are per group (Cin = cin_g padded to 16), as emp_conv2d_grouped_nhwc_f32;
- * groups == 1: cin_g = 0.  Values must fit fp16's range. */
+ * (engines.py:248-255) at three fp16 MFMAs per product instead of sixteen fp16-MFMA times on the fp32 pipe.  Operand range: a
+ * pair holds its operand to 2^-22 relative for 2^-3 <= |x| < 65520, to an absolute 2^-25 below 2^-3 (lo is an fp16 subnormal;
+ * the matrix pipe keeps subnormals), is zero from 2^-25 down and not finite at and above 65520; a term w x is therefore off by
+ * at most max(2^-22 |x|, 2^-25) |w| + |x| max(2^-22 |w|, 2^-25) + 2^-22 |w x| (tests/test_gpu_x3_range.py holds every output
+ * element of every entry below to the sum of these).  groups > 1: Cout and Cin are per group (Cin = cin_g padded to 16), as emp_conv2d_grouped_nhwc_f32;
+ * groups == 1: cin_g = 0.  Values at or above 65520 in magnitude give NaN (0 behind a ReLU). */
 EMP_API int emp_conv2d_nhwc_f16x3(const float* d_in, int N, int H, int W, int Cin, int in_ld,
                         const float* d_w, const float* d_bias, const float* d_bias_n,
                         const float* d_res, int res_ld,
@@ -263,8 +266,9 @@ EMP_API int emp_conv2d_nhwc_f16x3_ex(const float* d_in, int N, int H, int W, int
                         void* stream);
 
 /* Round 6 -- the `hl32` map format and the 256 x 256 fp16x3 convolution over it (csrc/conv16x3p.hip).  An hl32 map keeps a
- * value x of the fp32 graph as the fp16 pair the fp16x3 product needs -- hi = fp16(x), lo = fp16(x - hi), x ~ hi + lo to 22
- * bits -- split ONCE by the producer: a row of C channels (C % 32 == 0) is C / 32 blocks of 128 bytes, each 32 hi halfs
+ * value x of the fp32 graph as the fp16 pair the fp16x3 product needs -- hi = fp16(x), lo = fp16(x - hi); hi + lo is x to
+ * 2^-22 |x| for 2^-3 <= |x| < 65520, to 2^-25 absolute below 2^-3 (subnormal lo halves are kept, -0.0 keeps its sign), exactly 0
+ * for |x| <= 2^-25, not finite from 65520 -- split ONCE by the producer: a row of C channels (C % 32 == 0) is C / 32 blocks of 128 bytes, each 32 hi halfs
  * followed by 32 lo halfs; rows are 2 * ld halfs apart (the fp32 map's 4 bytes per element).  The networks of precision 2 keep
  * the stride-16 region (ResNet layer3 / layer4, ASPP: resnet.py:109-129, aspp.py:51-103) in this format, so that the 128 bytes a
  * pixel contributes to a K step of 32 channels are one cache line and one LDS row, fetched by LDS-DMA.
