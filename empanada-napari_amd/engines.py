@@ -19,9 +19,10 @@ import torch
 import torch.nn.functional as F
 
 from . import _abi, weights
+from .preprocess import RawPlan, padded_hw
 
 __all__ = ['HipPanopticDeepLab', 'PanopticDeepLabRenderEngine', 'PanopticDeepLabRenderEngine3d',
-           'factor_pad', 'logits_to_prob']
+           'factor_pad', 'logits_to_prob', 'recursive_median']
 
 IMG_DTYPES = {torch.float32: 0, torch.uint8: 1, torch.int16: 2, torch.uint16: 2}
 
@@ -229,6 +230,18 @@ def logits_to_prob(logits, out=None):
     return out
 
 
+@torch.no_grad()
+def recursive_median(lib, hist, raw, ks, n_out, out):
+    """The recursive median filter (engines.py:76-84) of ``n_out`` consecutive slices in one launch: ``hist`` holds the
+    ``mid`` filtered maps before the first of them, ``raw`` the slices themselves and at least ``mid`` after them;
+    ``out`` (n_out maps) may be ``raw`` itself."""
+    mid = (ks - 1) // 2
+    assert raw.shape[0] >= n_out + mid and hist.shape[0] == mid and hist.is_contiguous() and raw.is_contiguous()
+    fn = lib.emp_median_recursive
+    _abi.check(fn(_abi.ptr(hist), _abi.ptr(raw), raw.shape[0], ks, n_out, _abi.ptr(out), raw[0].numel(),
+                  _abi.stream_ptr(raw.device)), fn.__name__)
+
+
 class _Engine:
     def __init__(self, model):
         self.model = model.eval()
@@ -306,6 +319,23 @@ class PanopticDeepLabRenderEngine(_Engine):
         model_out['sem'] = logits_to_prob(model_out['sem_logits'])
         return model_out
 
+    @torch.no_grad()
+    def forward_raw(self, x, raw, render_steps=2):
+        """The model's dict for raw integer images ``x`` (N,1,h,w) under the ``preprocess.RawPlan`` ``raw``."""
+        return self.model(x, render_steps, interpolate_ins=not self.coarse_boundaries, sub=raw.sub, mul=raw.mul,
+                          pad_to=raw.pad_to)
+
+    @torch.no_grad()
+    def segment(self, sem, ctr_hmp, offsets, size=None, upsampling=1):
+        """sem (N,C,H,W) probabilities, centres, offsets -> pan (N,H,W) int64, cropped to ``size`` = (h, w) if given."""
+        cells, _, _, kmax = self.instance_cells_int(ctr_hmp, offsets, upsampling)
+        pan = self.panoptic_merge_int(sem, cells, kmax)
+        return pan if size is None else pan[..., :size[0], :size[1]]
+
+    def heads_to_labels(self, model_out, size=None, upsampling=1):
+        return self.segment(logits_to_prob(model_out['sem_logits']), model_out['ctr_hmp'], model_out['offsets'], size,
+                            upsampling)
+
     # ---- batched building blocks (N images per launch group) ----
     @torch.no_grad()
     def instance_cells_int(self, ctr_hmp, offsets, upsampling=1):
@@ -381,16 +411,17 @@ class PanopticDeepLabRenderEngine(_Engine):
         max_ids = int(cells.max().item())
         return self.panoptic_merge_int(sem, cells, max_ids)
 
-    def __call__(self, image, size, upsampling=1):
+    def _infer_padded(self, image, upsampling):
+        """``__call__``'s way to the heads: one (1,1,h,w) float image, padded, on the model's device, inferred."""
         assert math.log(upsampling, 2).is_integer(), 'Upsampling factor not log base 2!'
         assert image.ndim == 4 and image.size(0) == 1
-        h, w = size
         image = factor_pad(image, self.padding_factor)
         image = self.to_model_device(image)
-        model_out = self.infer(image, int(2 + math.log(upsampling, 2)))
-        cells, _, _, kmax = self.instance_cells_int(model_out['ctr_hmp'], model_out['offsets'], upsampling)
-        pan_seg = self.panoptic_merge_int(model_out['sem'], cells, kmax)
-        return pan_seg[..., :h, :w]
+        return self.infer(image, int(2 + math.log(upsampling, 2)))
+
+    def __call__(self, image, size, upsampling=1):
+        model_out = self._infer_padded(image, upsampling)
+        return self.segment(model_out['sem'], model_out['ctr_hmp'], model_out['offsets'], size, upsampling)
 
     @torch.no_grad()
     def call_raw(self, image, sub, mul):
@@ -399,23 +430,15 @@ class PanopticDeepLabRenderEngine(_Engine):
         instead of 4).  Same result as ``self(preprocessor(image), (h, w))``."""
         assert image.ndim == 4 and image.size(0) == 1
         h, w = image.shape[-2:]
-        pf = self.padding_factor
-        pad_to = (-(-h // pf) * pf, -(-w // pf) * pf)
-        out = self.model(self.to_model_device(image), 2, interpolate_ins=not self.coarse_boundaries, sub=float(sub),
-                         mul=float(mul), pad_to=pad_to)
-        sem = logits_to_prob(out['sem_logits'])
-        cells, _, _, kmax = self.instance_cells_int(out['ctr_hmp'], out['offsets'], 1)
-        return self.panoptic_merge_int(sem, cells, kmax)[..., :h, :w]
+        raw = RawPlan(float(sub), float(mul), padded_hw(h, w, self.padding_factor))
+        return self.heads_to_labels(self.forward_raw(self.to_model_device(image), raw), (h, w))
 
     # ---- batched extension (config 2: "equal to N sequential reference calls") ----
     @torch.no_grad()
     def infer_batch(self, images, sizes=None, upsampling=1, sub=0.0, mul=1.0):
         """images (N,1,H,W) already padded to ``padding_factor``; returns pan (N,H,W) int64."""
         rs = int(2 + math.log(upsampling, 2))
-        out = self.model(images, rs, interpolate_ins=not self.coarse_boundaries, sub=sub, mul=mul)
-        sem = logits_to_prob(out['sem_logits'])
-        cells, _, _, kmax = self.instance_cells_int(out['ctr_hmp'], out['offsets'], upsampling)
-        return self.panoptic_merge_int(sem, cells, kmax)
+        return self.heads_to_labels(self.forward_raw(images, RawPlan(sub, mul, None), rs), upsampling=upsampling)
 
 
 class PanopticDeepLabRenderEngine3d(_MedianQueue, PanopticDeepLabRenderEngine):
@@ -429,27 +452,15 @@ class PanopticDeepLabRenderEngine3d(_MedianQueue, PanopticDeepLabRenderEngine):
                          confidence_thr=confidence_thr, median_kernel_size=median_kernel_size,
                          padding_factor=padding_factor, coarse_boundaries=coarse_boundaries)
 
-    def _segment(self, model_out, upsampling):
-        cells, _, _, kmax = self.instance_cells_int(model_out['ctr_hmp'], model_out['offsets'], upsampling)
-        return self.panoptic_merge_int(model_out['sem'], cells, kmax)
-
     def end(self, upsampling=1):
-        final_segs = []
-        for model_out in list(self.median_queue)[self.mid_idx + 1:]:
-            h, w = model_out['size']
-            final_segs.append(self._segment(model_out, upsampling)[..., :h, :w])
-        return final_segs
+        return [self.segment(mo['sem'], mo['ctr_hmp'], mo['offsets'], mo['size'], upsampling)
+                for mo in list(self.median_queue)[self.mid_idx + 1:]]
 
     def __call__(self, image, size, upsampling=1):
-        assert math.log(upsampling, 2).is_integer(), 'Upsampling factor not log base 2!'
-        assert image.ndim == 4 and image.size(0) == 1
-        h, w = size
-        image = factor_pad(image, self.padding_factor)
-        image = self.to_model_device(image)
-        model_out = self.infer(image, int(2 + math.log(upsampling, 2)))
+        model_out = self._infer_padded(image, upsampling)
         model_out['size'] = size
         self.enqueue(model_out)
         median_out = self.get_next(keys=['sem'])
         if median_out is None:
             return None
-        return self._segment(median_out, upsampling)[..., :h, :w]
+        return self.segment(median_out['sem'], median_out['ctr_hmp'], median_out['offsets'], size, upsampling)

@@ -23,8 +23,8 @@ import torch
 
 from . import sparse, weights, zstore
 from .engines import (HipPanopticDeepLab, PanopticDeepLabRenderEngine, PanopticDeepLabRenderEngine3d,
-                      factor_pad, logits_to_prob)
-from .preprocess import Preprocessor, resize_by_factor
+                      factor_pad, logits_to_prob, recursive_median)
+from .preprocess import Preprocessor, is_raw_input, padded_hw, plan_raw, resize_by_factor
 
 try:  # the widgets run these generators in a Qt worker thread
     from napari.qt.threading import thread_worker
@@ -233,13 +233,11 @@ class Engine2d:
             return self._infer_tiled(image)
         _require_scale_one(self.inference_scale)
         size = image.shape
-        if (isinstance(image, np.ndarray) and image.ndim == 2 and image.dtype in (np.uint8, np.uint16)
-                and self.inference_scale == 1):
+        if is_raw_input(image, self.inference_scale) and image.ndim == 2:
             # raw integers go up (1-2 B/pixel); normalisation + factor_pad are fused into the stem kernel
-            from .preprocess import normalize_params
-            sub, mul = normalize_params(self.preprocessor.mean, self.preprocessor.std, np.iinfo(image.dtype).max)
+            raw = plan_raw(self.preprocessor, image.dtype, size, self.padding_factor)
             x = torch.from_numpy(np.ascontiguousarray(image))[None, None]
-            return self.force_connected(self.engine.call_raw(x, sub, mul).squeeze(0))
+            return self.force_connected(self.engine.heads_to_labels(self.engine.forward_raw(x, raw), size).squeeze(0))
         x = self.preprocessor(resize_by_factor(image, self.inference_scale))['image'].unsqueeze(0)
         pan_seg = self.engine(x, size, upsampling=self.inference_scale)
         return self.force_connected(pan_seg.squeeze(0))
@@ -254,18 +252,15 @@ class Engine2d:
         that block).  On the fp16 engine bit-identical to the per-image calls (batch invariance, DESIGN.md finding 13); in the
         default fp16x3 precision the kernels a layer runs on depend on the batch (hl32 plane region from 128 pixel tiles, split-K
         below half the chip), so the float heads of a tile agree between batch sizes to fp32 rounding (~1e-6), not to the bit."""
-        from .preprocess import normalize_params
         images = list(images)
         if not images:
             return []
         h, w = images[0].shape
         dt = images[0].dtype
         assert all(im.ndim == 2 and im.shape == (h, w) and im.dtype == dt for im in images), 'one size and dtype per call'
-        assert dt in (np.uint8, np.uint16) and self.inference_scale == 1 and not (self.tile_size > 0 and max(h, w) > self.tile_size)
-        sub, mul = normalize_params(self.preprocessor.mean, self.preprocessor.std, np.iinfo(dt).max)
+        assert is_raw_input(images[0], self.inference_scale) and not (self.tile_size > 0 and max(h, w) > self.tile_size)
+        raw = plan_raw(self.preprocessor, dt, (h, w), self.padding_factor)
         eng, dev = self.engine, self.device
-        pf = self.padding_factor
-        pad_to = (-(-h // pf) * pf, -(-w // pf) * pf)
         n = len(images)
         tdt = torch.uint8 if dt == np.uint8 else torch.uint16
         # staging: two pinned input and two pinned output blocks + their device twins, kept on the engine (pinning
@@ -319,15 +314,12 @@ class Engine2d:
             b, m = k & 1, i1 - i0
             pending_up.result()
             main.wait_event(ev_in[b])
-            mo = eng.model(d_in[b][:m], 2, interpolate_ins=not eng.coarse_boundaries, sub=float(sub), mul=float(mul),
-                           pad_to=pad_to)
+            mo = eng.forward_raw(d_in[b][:m], raw)
             ev_free[b] = torch.cuda.Event()
             ev_free[b].record(main)
             if k + 1 < len(chunks):      # the other input buffer's last reader (forward k-1) is already recorded
                 pending_up = uploader.submit(upload, k + 1)
-            sem = logits_to_prob(mo['sem_logits'])
-            cells, _, _, kmax = eng.instance_cells_int(mo['ctr_hmp'], mo['offsets'], 1)
-            pan = eng.panoptic_merge_int(sem, cells, kmax)[:, :h, :w]
+            pan = eng.heads_to_labels(mo, (h, w))
             if ev_back[b] is not None:
                 main.wait_event(ev_back[b])
             sparse.force_connected(pan.contiguous(), list(eng.thing_list), self.label_divisor, d_out[b][:m])
@@ -363,23 +355,15 @@ class Engine2d:
         tiler = Tiler(image.shape, tile_size=self.tile_size, overlap_width=min(128, int(self.tile_size * 0.1)))
         self.last_tiler = tiler
         rle_segs = []
-        raw = (batched and isinstance(image, np.ndarray) and image.dtype in (np.uint8, np.uint16) and
-               self.inference_scale == 1)
-        if raw:
-            from .preprocess import normalize_params
+        if batched and is_raw_input(image, self.inference_scale):
             eng = self.engine
-            sub, mul = normalize_params(self.preprocessor.mean, self.preprocessor.std, np.iinfo(image.dtype).max)
             th, tw = tiler(image, 0).shape
-            pf = self.padding_factor
-            pad_to = (-(-th // pf) * pf, -(-tw // pf) * pf)
-            bs = int(max(1, min(64, (1 << 25) // max(1, pad_to[0] * pad_to[1]))))       # about 32 Mpixel per batch
+            raw = plan_raw(self.preprocessor, image.dtype, (th, tw), self.padding_factor)
+            bs = int(max(1, min(64, (1 << 25) // max(1, raw.pad_to[0] * raw.pad_to[1]))))       # about 32 Mpixel per batch
             for i0 in range(0, len(tiler), bs):
                 idx = range(i0, min(len(tiler), i0 + bs))
                 x = torch.from_numpy(np.stack([tiler(image, i) for i in idx]))[:, None].to(self.device, non_blocking=True)
-                mo = eng.model(x, 2, interpolate_ins=not eng.coarse_boundaries, sub=float(sub), mul=float(mul), pad_to=pad_to)
-                sem = logits_to_prob(mo['sem_logits'])
-                cells, _, _, kmax = eng.instance_cells_int(mo['ctr_hmp'], mo['offsets'], 1)
-                pan = eng.panoptic_merge_int(sem, cells, kmax)[:, :th, :tw].to(torch.int32)
+                pan = eng.heads_to_labels(eng.forward_raw(x, raw), (th, tw)).to(torch.int32)
                 segs = sparse.pan_stack_to_rle_segs(pan.contiguous(), self.labels, self.label_divisor, eng.thing_list)
                 rle_segs += [tiler.translate_rle_seg(seg, i) for seg, i in zip(segs, idx)]
         else:
@@ -509,8 +493,6 @@ class Engine3d:
         consecutive slices goes through ONE recursive-median launch and ONE batched voting / merge
         launch group instead of a per-slice Python loop with a host sync each."""
         eng = self.engine
-        lib = eng.lib
-        from . import _abi
         if isinstance(volume, torch.Tensor):
             volume = volume.detach().cpu().numpy()
         elif not isinstance(volume, np.ndarray) and _is_chunked_store(volume) and \
@@ -528,12 +510,6 @@ class Engine3d:
         zp = 0                # global index of the first pending slice
         avail = 0
         size = None
-
-        def emit(sem_f, ctr, off):
-            cells, _, _, kmax = eng.instance_cells_int(ctr, off, ups)
-            pan = eng.panoptic_merge_int(sem_f, cells, kmax)
-            h, w = size
-            return list(pan[:, :h, :w].unbind(0))
 
         def process(upto):
             """emit slices zp .. upto-1 (their look-ahead is available or they are tail slices)"""
@@ -558,13 +534,11 @@ class Engine3d:
                 hist = torch.cat(fhist[-mid:]).contiguous()
                 raw = sem[loc:loc + run + mid].contiguous()
                 res = torch.empty((run,) + tuple(sem.shape[1:]), dtype=sem.dtype, device=sem.device)
-                cntpx = sem[0].numel()
-                _abi.check(lib.emp_median_recursive(_abi.ptr(hist), _abi.ptr(raw), raw.shape[0], ks, run, _abi.ptr(res),
-                                                    cntpx, _abi.stream_ptr(sem.device)), 'emp_median_recursive')
+                recursive_median(eng.lib, hist, raw, ks, run, res)
                 filt.append(res)
                 fhist = (fhist + list(res[-mid:].split(1)))[-mid:]
                 z += run
-            chunk = emit(torch.cat(filt), ctr[:cnt], off[:cnt])
+            chunk = list(eng.segment(torch.cat(filt), ctr[:cnt], off[:cnt], size, ups).unbind(0))
             rest = sem.shape[0] - cnt
             pend = [(sem[cnt:], ctr[cnt:], off[cnt:])] if rest > 0 else []
             zp = upto
@@ -573,10 +547,8 @@ class Engine3d:
         # Fast path for integer numpy volumes at native scale: the batch is cut out of the volume in one strided copy,
         # uploaded as raw integers (1-2 bytes per pixel instead of 4) and normalised + zero-padded inside the stem
         # kernel -- the same (x - mean*max) * 1/(std*max) arithmetic as Preprocessor + factor_pad.
-        raw_path = (isinstance(volume, np.ndarray) and volume.dtype in (np.uint8, np.uint16) and ups == 1)
+        raw_path = is_raw_input(volume, ups)
         if raw_path:
-            from .preprocess import normalize_params
-            sub, mul = normalize_params(self.preprocessor.mean, self.preprocessor.std, np.iinfo(volume.dtype).max)
             # one upload of the whole volume (1-2 bytes per voxel; chunks of up to 8 GiB stay on the host path), the
             # per-axis transposition happens on the device: a yz stack is a stride-1 gather on the host
             # (tried: an xy stack's batches uploaded one by one behind the previous forward instead of the whole volume
@@ -603,23 +575,18 @@ class Engine3d:
             if not on_dev:
                 moved = volume
             moved = moved.movedim(axis, 0) if on_dev else np.moveaxis(volume, axis, 0)
-            staged = None if on_dev else self._staged_batches(moved, n, self.slice_batch(
-                (-(-moved.shape[1] // eng.padding_factor) * eng.padding_factor,
-                 -(-moved.shape[2] // eng.padding_factor) * eng.padding_factor)), eng.model.device)
-            pf = eng.padding_factor
-            vh, vw = moved.shape[1:]
-            pad_to = (-(-vh // pf) * pf, -(-vw // pf) * pf)
-            size = (vh, vw)
-        if raw_path:
-            bs = self.slice_batch(pad_to)
+            size = tuple(moved.shape[1:])
+            plan = plan_raw(self.preprocessor, volume.dtype, size, eng.padding_factor)
+            bs = self.slice_batch(plan.pad_to)
+            staged = None if on_dev else self._staged_batches(moved, n, bs, eng.model.device)
         else:
             shp = [s for i, s in enumerate(volume.shape) if i != axis]
-            bs = self.slice_batch((math.ceil(shp[0] / ups), math.ceil(shp[1] / ups)))
+            bs = self.slice_batch(padded_hw(math.ceil(shp[0] / ups), math.ceil(shp[1] / ups), eng.padding_factor))
         held = None           # post_stream mode: the group computed last, handed out after the next forward is enqueued
         for i0 in range(0, n, bs):
             if raw_path:
                 xb = (moved[i0:i0 + bs].contiguous() if on_dev else next(staged))[:, None]
-                mo = eng.model(xb, rs, interpolate_ins=not eng.coarse_boundaries, sub=float(sub), mul=float(mul), pad_to=pad_to)
+                mo = eng.forward_raw(xb, plan, rs)
                 nb = xb.shape[0]
             else:
                 raws = [np.asarray(take(volume, i, axis)) for i in range(i0, min(n, i0 + bs))]

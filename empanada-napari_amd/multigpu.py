@@ -1145,13 +1145,10 @@ class HipSlabBackend:
             raise Exception('MultiGPU inference runs at inference_scale = 1 only (empanada_napari/multigpu.py:83-87)')
         shp = [s for i, s in enumerate(volume.shape) if i != axis]
         self.size = (int(shp[0]), int(shp[1]))
-        pf = self.eng.padding_factor
-        self.pad_to = (-(-self.size[0] // pf) * pf, -(-self.size[1] // pf) * pf)
-        vdt = np.dtype(volume.dtype)
-        self.raw = vdt in (np.dtype(np.uint8), np.dtype(np.uint16))
-        if self.raw:
-            from .preprocess import normalize_params
-            self.sub, self.mul = normalize_params(e3.preprocessor.mean, e3.preprocessor.std, np.iinfo(vdt).max)
+        from .preprocess import padded_hw, plan_raw
+        self.pad_to = padded_hw(*self.size, self.eng.padding_factor)
+        # uint8 / uint16 volumes (numpy, chunked store or procedural): raw blocks go up, the stem kernel normalises and pads
+        self.raw = plan_raw(e3.preprocessor, volume.dtype, self.size, self.eng.padding_factor)
 
     @property
     def block_slices(self):
@@ -1179,9 +1176,8 @@ class HipSlabBackend:
         for i0 in range(lo, hi, bs):
             i1 = min(hi, i0 + bs)
             xb = self._block(i0, i1)
-            if self.raw:   # raw integers go up, normalisation + factor_pad run inside the stem kernel
-                mo = eng.model(xb, 2, interpolate_ins=not eng.coarse_boundaries, sub=float(self.sub), mul=float(self.mul),
-                               pad_to=self.pad_to)
+            if self.raw is not None:
+                mo = eng.forward_raw(xb, self.raw)
             else:
                 imgs = [e3.preprocessor(np.asarray(x[0].cpu()))['image'] for x in xb]
                 mo = eng.model(eng.to_model_device(factor_pad(torch.stack(imgs), eng.padding_factor)), 2,
@@ -1197,7 +1193,7 @@ class HipSlabBackend:
 
     @torch.no_grad()
     def median_inplace(self, sem, n_own, hist, n_ahead, first, last, ks):
-        from . import _abi
+        from .engines import recursive_median
         mid = (ks - 1) // 2
         if mid == 0:
             return
@@ -1207,9 +1203,7 @@ class HipSlabBackend:
             return
         h = sem[:mid] if first else hist        # on the first slab the history is its own (unfiltered) head
         raw = sem[a:]
-        assert raw.shape[0] >= (b - a) + mid and h.shape[0] == mid and h.is_contiguous() and raw.is_contiguous()
-        _abi.check(self.eng.lib.emp_median_recursive(_abi.ptr(h), _abi.ptr(raw), raw.shape[0], ks, b - a, _abi.ptr(raw),
-                                                     sem[0].numel(), _abi.stream_ptr(sem.device)), 'emp_median_recursive')
+        recursive_median(self.eng.lib, h, raw, ks, b - a, raw)
 
     @torch.no_grad()
     def runs_iter(self, sem, stash):
@@ -1218,11 +1212,9 @@ class HipSlabBackend:
         from . import sparse
         e3, eng = self.e3, self.eng
         ctr, off = stash
-        h, w = self.size
         for i0 in range(0, sem.shape[0], 64):
             sl = slice(i0, i0 + 64)
-            cells, _, _, kmax = eng.instance_cells_int(ctr[sl], off[sl], 1)
-            pan = eng.panoptic_merge_int(sem[sl], cells, kmax)[:, :h, :w]
+            pan = eng.segment(sem[sl], ctr[sl], off[sl], self.size)
             per_label = sparse.pan_stack_to_runs(pan, e3.labels, e3.label_divisor, e3.thing_list, force_connected=True)
             yield [{label: (rl[j], o) for label, (rl, o) in per_label.items()} for j in range(pan.shape[0])]
 

@@ -4,8 +4,11 @@
 in, ``{'image': FloatTensor (1,H,W)}`` out, float input rejected with the same
 exception.  The GPU engine can also take the raw integer tile and fuse the
 same arithmetic into its stem kernel (``normalize_params`` gives it the two
-constants), which is the path ``bench.py`` times.
+constants), which is the path ``bench.py`` times.  ``is_raw_input`` says which
+inputs take that route and ``plan_raw`` what the engines hand the kernel for them.
 """
+from typing import NamedTuple, Optional, Tuple
+
 import numpy as np
 
 
@@ -14,6 +17,35 @@ def normalize_params(mean, std, max_pixel_value):
     m = np.float32(np.array(mean, dtype=np.float32) * max_pixel_value)
     s = np.float32(np.array(std, dtype=np.float32) * max_pixel_value)
     return m, np.reciprocal(s, dtype=np.float32)
+
+
+def padded_hw(h, w, pf):
+    """(h, w) rounded up to multiples of the padding factor: the size ``factor_pad`` gives an image."""
+    return tuple(-(-s // pf) * pf for s in (h, w))
+
+
+class RawPlan(NamedTuple):
+    """What the stem kernel needs to take a raw integer image: out = (img - sub) * mul, zero-padded to ``pad_to``."""
+    sub: float
+    mul: float
+    pad_to: Optional[Tuple[int, int]]
+
+
+def is_raw_input(image, inference_scale=1):
+    """Does ``image`` qualify for the raw route (integers uploaded, normalisation + ``factor_pad`` fused into the stem
+    kernel)?  A numpy uint8 / uint16 array at native scale does."""
+    return isinstance(image, np.ndarray) and image.dtype in (np.uint8, np.uint16) and inference_scale == 1
+
+
+def plan_raw(preprocessor, dtype, hw, pf):
+    """-> the ``RawPlan`` of (h, w) images of ``dtype`` under ``preprocessor``'s norms and padding factor ``pf`` -- the
+    same (x - mean*max) * 1/(std*max) arithmetic as ``Preprocessor`` + ``factor_pad``; None if the stem kernel does not
+    read ``dtype``."""
+    dtype = np.dtype(dtype)
+    if dtype not in (np.uint8, np.uint16):
+        return None
+    sub, mul = normalize_params(preprocessor.mean, preprocessor.std, np.iinfo(dtype).max)
+    return RawPlan(float(sub), float(mul), padded_hw(int(hw[0]), int(hw[1]), pf))
 
 
 def normalize(img, mean, std, max_pixel_value=255.0):

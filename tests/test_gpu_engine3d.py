@@ -110,11 +110,18 @@ def test_engine2d_force_connected(model_config):
     np.testing.assert_array_equal(eng.infer(img16), osp.force_connected_pan(raw16.copy(), [1], DIV))
 
 
-def test_batched_slices_equal_single_slice_calls(model_config):
-    """predict_slices (batched forward) == calling the 3d engine slice by slice like the reference loop"""
+@pytest.mark.parametrize('dtype', [np.uint8, np.int16])
+def test_batched_slices_equal_single_slice_calls(model_config, dtype):
+    """predict_slices (batched forward) == calling the 3d engine slice by slice like the reference loop.  uint8 takes
+    iter_slice_chunks' raw route (integers uploaded, normalised in the stem kernel); int16 its Preprocessor route."""
     from empanada_napari_amd import synth
     from empanada_napari_amd.inference import Engine3d
+    from empanada_napari_amd.preprocess import is_raw_input
     vol = synth.blob_volume(9, 32, 48, seed=4)
+    assert vol.dtype == np.uint8
+    if dtype is np.int16:
+        vol = vol.astype(np.int16) * 128      # the same picture on int16's range (255 * 128 < 2^15)
+    assert is_raw_input(vol) == (dtype is np.uint8)
     eng = Engine3d(model_config, label_divisor=DIV, median_kernel_size=3, confidence_thr=0.5, batch_size=4)
     a = [p.cpu().numpy() for p in eng.predict_slices(vol, 0)]
     e = eng.engine
