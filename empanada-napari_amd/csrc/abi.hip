@@ -97,6 +97,70 @@ int emp_conv2d_nhwc_f16(const void* d_in, int N, int H, int W, int Cin, int in_l
   return launch_conv_igemm(p, variant, (hipStream_t)stream);
 }
 
+// Test and tuning entry of every ConvParams feature that the network reaches and emp_conv2d_nhwc_f16 / emp_conv1x1_dual_nhwc_f16
+// cannot express: the K-concatenated second source next to a residual / per-image bias, the pixel-shuffle store, the second and
+// third destination, the back-to-back 1x1 fused into the 256 x 256 tile.  Fills ConvParams and calls launch_conv_igemm -- what the
+// launchers refuse comes back as THEIR error.  Not a hot-path call.
+int emp_conv2d_nhwc_f16_ex(const void* d_in, int N, int H, int W, int Cin, int in_ld, const void* d_w, const float* d_bias,
+                           const float* d_bias_n, const void* d_res, int res_ld, void* d_out, int out_ld, int Cout, int KH, int KW,
+                           int stride, int pad, int dil, int act, int variant, const void* d_in2, int H2, int W2, int Cin2, int in2_ld,
+                           int stride2, int ps_cout, void* d_out2, int out2_ld, int split, void* d_out3, int out3_ld, int split3,
+                           const void* d_next_w, const float* d_next_b, void* d_next_out, int next_cout, int next_ld, void* stream) {
+  EMP_REQUIRE(d_in && d_w && d_out, "conv2d_ex: null pointer");
+  EMP_REQUIRE(d_next_w == nullptr || (d_next_b && d_next_out), "conv2d_ex: the fused next convolution needs its bias and its output");
+  EMP_REQUIRE(N > 0 && H > 0 && W > 0 && KH > 0 && KW > 0 && stride > 0 && dil > 0 && pad >= 0, "conv2d_ex: bad geometry");
+  EMP_REQUIRE(variant >= 0 && (variant & 15) <= 3 && ((variant >> 4) & 15) <= 7 && ((variant >> 8) & 255) <= 64 && (variant >> 16) <= 31, "conv2d_ex: bad variant %d", variant);
+  ConvParams p{};
+  p.in = (const half_t*)d_in;
+  p.wgt = (const half_t*)d_w;
+  p.bias = d_bias;
+  p.bias_n = d_bias_n;
+  p.res = (const half_t*)d_res;
+  p.res_ld = res_ld;
+  p.out = (half_t*)d_out;
+  p.zero = (const half_t*)zero_page();
+  EMP_REQUIRE(p.zero != nullptr, "conv2d_ex: could not allocate the zero page");
+  p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.in_ld = in_ld;
+  p.Cout = Cout; p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.dil = dil;
+  p.Ho = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
+  p.Wo = (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
+  EMP_REQUIRE(p.Ho > 0 && p.Wo > 0, "conv2d_ex: empty output");
+  p.out_ld = out_ld;
+  p.act = act;
+  p.ps_cout = ps_cout;
+  p.M = N * p.Ho * p.Wo;
+  if (d_in2) { p.in2 = (const half_t*)d_in2; p.H2 = H2; p.W2 = W2; p.Cin2 = Cin2; p.in2_ld = in2_ld; p.stride2 = stride2; }
+  if (d_out2) { p.out2 = (half_t*)d_out2; p.out2_ld = out2_ld; p.split = split; }
+  if (d_out3) { p.out3 = (half_t*)d_out3; p.out3_ld = out3_ld; p.split3 = split3; }
+  if (d_next_w) { p.next_w = (const half_t*)d_next_w; p.next_b = d_next_b; p.next_out = (half_t*)d_next_out; p.next_cout = next_cout; p.next_ld = next_ld; }
+  return launch_conv_igemm(p, variant, (hipStream_t)stream);
+}
+
+// Test and tuning entry of the grouped generic tile (conv_igemm_grouped.hip; the network's RegNet 3x3): one group's ConvParams, the
+// groups' strides, and `tile` to force either instantiation.  Not a hot-path call.
+int emp_conv2d_grouped_nhwc_f16(const void* d_in, int N, int H, int W, int Cin, int in_ld, const void* d_w, const float* d_bias,
+                                void* d_out, int out_ld, int Cout, int KH, int KW, int stride, int pad, int dil, int act, int groups,
+                                int gs_in, long long gs_w, int gs_out, int tile, void* stream) {
+  EMP_REQUIRE(d_in && d_w && d_out, "conv2d_grouped: null pointer");
+  EMP_REQUIRE(N > 0 && H > 0 && W > 0 && KH > 0 && KW > 0 && stride > 0 && dil > 0 && pad >= 0, "conv2d_grouped: bad geometry");
+  ConvParams p{};
+  p.in = (const half_t*)d_in;
+  p.wgt = (const half_t*)d_w;
+  p.bias = d_bias;
+  p.out = (half_t*)d_out;
+  p.zero = (const half_t*)zero_page();
+  EMP_REQUIRE(p.zero != nullptr, "conv2d_grouped: could not allocate the zero page");
+  p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.in_ld = in_ld;
+  p.Cout = Cout; p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.dil = dil;
+  p.Ho = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
+  p.Wo = (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
+  EMP_REQUIRE(p.Ho > 0 && p.Wo > 0, "conv2d_grouped: empty output");
+  p.out_ld = out_ld;
+  p.act = act;
+  p.M = N * p.Ho * p.Wo;
+  return launch_conv_igemm_grouped(p, groups, gs_in, gs_w, gs_out, (hipStream_t)stream, tile);
+}
+
 int emp_conv256_pack_weights(const void* d_w, void* d_packed, int Cout, int KT, int Cin, int Cin2, void* stream) {
   return conv256_pack_weights((const half_t*)d_w, (half_t*)d_packed, Cout, KT, Cin, Cin2, (hipStream_t)stream);
 }

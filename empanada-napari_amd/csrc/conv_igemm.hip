@@ -431,8 +431,9 @@ int launch_grouped_tpl(ConvParams p, int groups, int gs_in, long long gs_w, int 
 
 // p describes ONE group (Cin = the group's input channels padded to 64 with zero weights, Cout = its output channels);
 // group g reads p.in + g * gs_in, weights p.wgt + g * gs_w, writes p.out + g * gs_out (bias likewise).  Plain conv only.
-int launch_conv_igemm_grouped(const ConvParams& p, int groups, int gs_in, long long gs_w, int gs_out, hipStream_t stream) {
+int launch_conv_igemm_grouped(const ConvParams& p, int groups, int gs_in, long long gs_w, int gs_out, hipStream_t stream, int tile) {
   EMP_REQUIRE(groups >= 1 && groups < 65536, "grouped conv: bad group count %d", groups);
+  EMP_REQUIRE(tile >= 0 && tile <= 2, "grouped conv: tile must be 0 (automatic), 1 (128x128) or 2 (128x64), got %d", tile);
   EMP_REQUIRE(p.Cin % BK == 0 && p.Cin > 0 && p.in_ld % 8 == 0 && (groups - 1) * gs_in + p.Cin <= p.in_ld && gs_in % 8 == 0,
               "grouped conv: Cin=%d (multiple of 64), channel step %d (multiple of 8), row %d", p.Cin, gs_in, p.in_ld);
   EMP_REQUIRE(p.Cout % 8 == 0 && p.Cout > 0 && gs_out % 8 == 0 && gs_out >= p.Cout && p.out_ld % 8 == 0 &&
@@ -450,7 +451,9 @@ int launch_conv_igemm_grouped(const ConvParams& p, int groups, int gs_in, long l
     q.kgroup = kg;
   }
   // 64-wide cout tiles when they pad less (56 -> 64, 72 -> 128 either way: the 128 x 64 tile then has twice the workgroups)
-  if (p.Cout <= 64 || cdiv(p.Cout, 64) * 64 <= cdiv(p.Cout, 128) * 128)
+  // (the second condition holds for every Cout -- rounding up to 64 never exceeds rounding up to 128 -- so the automatic choice
+  //  is always the 128 x 64 tile and the 128 x 128 instantiation is reached through `tile` = 1 only: FINDINGS 101)
+  if (tile == 2 || (tile == 0 && (p.Cout <= 64 || cdiv(p.Cout, 64) * 64 <= cdiv(p.Cout, 128) * 128)))
     return launch_grouped_tpl<128, 64, 2, 2, true, true, 3>(q, groups, gs_in, gs_w, gs_out, stream);
   return launch_grouped_tpl<128, 128, 2, 2, true, true>(q, groups, gs_in, gs_w, gs_out, stream);
 }

@@ -197,7 +197,9 @@ EMP_API const char* emp_pdl_tap_name(const emp_pdl_t* net, int i);
  *   variant: 0 = automatic.  Otherwise staging (bits 0-3: 1 registers | 2 LDS-DMA | 3 LDS-DMA + LDS-transposed epilogue)
  *     + 16 * tile (1 128x128 | 2 128x64 | 3 64x64 | 4 256x256 | 5 half tile 128x256 / 256x128 | 6 64->64 3x3 with
  *     register weights | 7 64x64 with a deep LDS-DMA ring, the batch-1 path) + 256 * K-walk group; every tile gives
- *     bit-identical results (same K order), the parity tests force each one.
+ *     bit-identical results (same K order) at the default K-walk group, the parity tests force each one.  A K-walk group of
+ *     its own is another summation order: the same bounds, not the same bits (tests/test_gpu_f16_range.py: 512 -> 128 3x3,
+ *     groups of 2 slabs against the default 4).
  *     + (1 << 20): d_w is the 256x256 tile's PACKED weight image (emp_conv256_pack_weights, round 5) -- that tile, its
  *     default K walk, the same bits out. */
 EMP_API int emp_conv2d_nhwc_f16(const void* d_in, int N, int H, int W, int Cin, int in_ld,
@@ -206,6 +208,41 @@ EMP_API int emp_conv2d_nhwc_f16(const void* d_in, int N, int H, int W, int Cin, 
                         void* d_out, int out_ld, int Cout,
                         int KH, int KW, int stride, int pad, int dil, int relu,
                         int variant, void* stream);
+
+/* Every ConvParams feature that the network reaches and emp_conv2d_nhwc_f16 / emp_conv1x1_dual_nhwc_f16 cannot express, for
+ * op-level tests and tuning (replaces the same nn.Conv2d + folded BN + activation, encoders/resnet.py:109-129; the store variants
+ * replace the transposed convolutions of blocks.py:154-171 and the launches the scheduler merges).  Everything
+ * emp_conv2d_nhwc_f16 takes (act: 0 none, 1 ReLU, 2 SiLU; `variant` unchanged: staging + 16 * tile, K-walk group << 8,
+ * 256-tile DMA mode << 16, packed image << 20), plus
+ *   d_in2 .. : optional second source K-concatenated behind the first, as emp_conv1x1_dual_nhwc_f16 (d_w rows [KH*KW*Cin | Cin2])
+ *   ps_cout  : > 0: Cout == 4 * ps_cout, cout block q = dy * 2 + dx of pixel (y, x) is stored at pixel (2y + dy, 2x + dx) of a
+ *              (N, 2Ho, 2Wo, out_ld) map -- a k2 s2 transposed convolution as four 1x1 convolutions
+ *   d_out2 ..: optional second destination: couts [split, Cout) go to d_out2 (channel 0 = cout `split`); with d_out3 couts
+ *              [split, split3) go to d_out2 and [split3, Cout) to d_out3; split, split3 % 8 == 0 (% 256 on the 256x256 tile)
+ *   d_next_w : optional back-to-back 1x1 fused into the 256x256 tile (Cout == 256, >= 192 pixel tiles): (next_cout, Cout) fp16,
+ *              d_next_out (N,Ho,Wo,next_ld) = relu(d_next_w . out + d_next_b), computed from the stored fp16 tile; next_cout == 64
+ * A combination the launchers refuse returns their error (emp_last_error).  Not a hot-path call. */
+EMP_API int emp_conv2d_nhwc_f16_ex(const void* d_in, int N, int H, int W, int Cin, int in_ld,
+                        const void* d_w, const float* d_bias, const float* d_bias_n,
+                        const void* d_res, int res_ld,
+                        void* d_out, int out_ld, int Cout,
+                        int KH, int KW, int stride, int pad, int dil, int act, int variant,
+                        const void* d_in2, int H2, int W2, int Cin2, int in2_ld, int stride2,
+                        int ps_cout,
+                        void* d_out2, int out2_ld, int split, void* d_out3, int out3_ld, int split3,
+                        const void* d_next_w, const float* d_next_b, void* d_next_out, int next_cout, int next_ld,
+                        void* stream);
+
+/* The same convolution with `groups` groups on the fp16 engine (nn.Conv2d(groups=g), the 3x3 of a RegNet bottleneck:
+ * encoders/regnet.py:51-77), for op-level tests and tuning: Cin / Cout describe ONE group -- Cin the group's input channels padded
+ * to a multiple of 64, the padding meeting zero weights -- group g reads channels [g * gs_in, g * gs_in + Cin) of d_in, the
+ * weights d_w + g * gs_w halfs ((Cout, KH*KW, Cin) each), and writes channels [g * gs_out, g * gs_out + Cout) of d_out (bias
+ * likewise); no residual, per-image bias or second source.  tile: 0 the launcher's choice, 1 the 128x128 instantiation,
+ * 2 the 128x64 one (same K order: the same bits).  Not a hot-path call. */
+EMP_API int emp_conv2d_grouped_nhwc_f16(const void* d_in, int N, int H, int W, int Cin, int in_ld,
+                        const void* d_w, const float* d_bias, void* d_out, int out_ld, int Cout,
+                        int KH, int KW, int stride, int pad, int dil, int act,
+                        int groups, int gs_in, long long gs_w, int gs_out, int tile, void* stream);
 
 /* Packed weight image for the 256x256 convolution tile (round 5; csrc/conv_igemm256.hip pack256_kernel): the network
  * (emp_pdl_*) makes one per layer at the first launch that takes the tile.  Every 1 KiB piece an LDS-DMA instruction moves
