@@ -1,0 +1,360 @@
+"""The host planning of Morph Labels, Fill holes and Split Labels: pure numpy, no device, no library.
+
+``labels.py`` holds the device drivers of the three tools; what they decide on the host before and between the launches lives
+here, as functions over plain arrays and a ``LabelTable`` (anything with its ``labels``, ``areas``, ``boxes``, ``shape``):
+
+* Morph Labels / Fill holes: the footprints, the turns with their boxes (``_morph_turns``), the levels (``morph_schedule``), the
+  tile lists (``_morph_tiles``) and where a turn's entries lie inside its level's work arrays (``fill_placement``);
+* Split Labels: the turns (``split_turns``), the rule that gives the largest label a pass of its own (``split_passes``), the
+  screening of the boxes (``split_screen``), the boxes of a launch (``_split_batches``, ``split_boxes``), the markers of every box
+  (``split_point_markers`` / ``split_peak_markers`` with ``split_spacing``, then ``split_marker_array`` with ``split_marker_ids``)
+  and the ids the reference's loop hands out turn by turn (``split_ids``).
+
+This module imports numpy only, so all of it is tested without a device (tests/test_labelplan_host.py)."""
+import numpy as np
+
+MORPH_OPS = {'Dilate': 0, 'Erode': 1, 'Close': 2, 'Open': 3}      # the widget's strings (_merge_split_widget.py:48-53) -> EMP_MORPH_*
+MORPH_MAX_RADIUS = 7      # the widget's slider (:73)
+_MORPH_GROWS = ('Dilate', 'Close')
+
+FILL_MAX_HOLE_SIZE = (1 << 31) - 1      # no component can have more voxels: a level's boxes hold fewer (FILL_MAX_LEVEL_VOXELS)
+FILL_MAX_LEVEL_VOXELS = (1 << 31) - 1      # emp_fill_holes_labels: int32 entries of the parent / size arrays
+
+SPLIT_MAX_DISTANCE = 100      # the widget's slider (_merge_split_widget.py:461)
+SPLIT_MAX_BOXES = 65535      # emp_split_*: boxes per launch
+SPLIT_MAX_ENTRIES = (1 << 31) - 2      # ... and their voxels
+SPLIT_MAX_DIAGONAL2 = 1 << 30      # nz^2 + ny^2 + nx^2 of a box stays below EMP_SPLIT_INF
+SPLIT_MAX_MARKERS = 0x3fffffff      # emp_split_flood: a marker's id in a label
+
+
+# ----------------------------------------------------------------------------
+# shared by the three tools
+# ----------------------------------------------------------------------------
+def dims3(shape):
+    """(D, H, W) of a 2-D or 3-D shape: an image is a volume of one slice"""
+    return (1,) * (3 - len(shape)) + tuple(shape)
+
+
+def box3(lo, hi):
+    """a 2-D or 3-D box (exclusive upper ends) on three axes: an image's box has the one slice [0, 1)"""
+    pad = 3 - len(lo)
+    return np.concatenate([np.zeros(pad, np.int64), lo]), np.concatenate([np.ones(pad, np.int64), hi])
+
+
+def table_rows(table, ids):
+    """per id its row of the whole-array ``table``, -1 where the id does not occur (0 is the background: never a row)"""
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    if not len(table.labels) or not len(ids):
+        return np.full(len(ids), -1, np.int64)
+    pos = np.minimum(np.searchsorted(table.labels, ids), len(table.labels) - 1)
+    return np.where((ids > 0) & (table.labels[pos] == ids), pos, -1)
+
+
+# ----------------------------------------------------------------------------
+# Morph Labels and Fill holes
+# ----------------------------------------------------------------------------
+def _morph_args(operation, radius, what):
+    if operation not in MORPH_OPS:
+        raise ValueError(f"{what}: operation must be one of {list(MORPH_OPS)}, got {operation!r} ('Fill holes' is fill_label_holes)")
+    if isinstance(radius, bool) or int(radius) != radius or not 1 <= int(radius) <= MORPH_MAX_RADIUS:
+        raise ValueError(f'{what}: radius must be an integer in 1..{MORPH_MAX_RADIUS}, got {radius!r}')
+    return int(radius)
+
+
+def morph_footprint_rows(radius, ball):
+    """The footprint as the kernel walks it: rows (dz, dy, h) of ``disk(radius)`` (``ball`` false: dz = 0 only) or
+    ``ball(radius)``, each the x-interval [-h, h] with h = floor(sqrt(r^2 - dy^2 - dz^2)) in integers."""
+    r = _morph_args('Dilate', radius, 'morph_footprint_rows')
+    rows = []
+    for dz in (range(-r, r + 1) if ball else (0,)):
+        for dy in range(-r, r + 1):
+            rem = r * r - dz * dz - dy * dy
+            if rem < 0:
+                continue
+            h = 0
+            while (h + 1) * (h + 1) <= rem:
+                h += 1
+            rows.append((dz, dy, h))
+    return np.asarray(rows, dtype=np.int64).reshape(-1, 3)
+
+
+def morph_footprint_offsets(radius, ndim):
+    """the offsets (k, ndim) of ``disk(radius)`` (ndim 2) / ``ball(radius)`` (ndim 3), sorted: ``morph_footprint_rows`` expanded"""
+    if ndim not in (2, 3):
+        raise ValueError('morph_footprint_offsets: ndim 2 (disk) or 3 (ball)')
+    offs = [(dz, dy, dx) for dz, dy, h in morph_footprint_rows(radius, ndim == 3).tolist() for dx in range(-h, h + 1)]
+    offs = np.asarray(sorted(offs), dtype=np.int64).reshape(-1, 3)
+    return offs if ndim == 3 else offs[:, 1:]
+
+
+def _morph_turns(table, turns, radius, operation):
+    """(ids, rows, lo, hi): per turn its label, its row of the table (-1: the id does not occur) and the box that holds the
+    label's voxels when the turn comes (exclusive upper ends, not clipped): the table's box, grown by the radius for every
+    earlier turn of the same id where the operation can grow a label."""
+    if table.per_slice:
+        raise ValueError('morph_schedule: a whole-array table is needed')
+    ids = np.asarray(turns, dtype=np.int64).reshape(-1)
+    nd = table.boxes.shape[1] // 2
+    rows = table_rows(table, ids)
+    lo = np.zeros((len(ids), nd), np.int64)
+    hi = np.zeros((len(ids), nd), np.int64)
+    earlier = {}
+    for i, (l, row) in enumerate(zip(ids.tolist(), rows.tolist())):
+        if row < 0:
+            continue
+        k = earlier.get(l, 0)
+        earlier[l] = k + 1
+        grow = radius * k if operation in _MORPH_GROWS else 0
+        lo[i] = table.boxes[row, :nd] - grow
+        hi[i] = table.boxes[row, nd:] + grow
+    return ids, rows, lo, hi
+
+
+def morph_schedule(table, turns, radius, operation):
+    """The loop of Morph Labels over ``turns`` (label ids in the loop's order, a repeat being a second turn) as levels: a list
+    of lists of turn indices.  The turns of a level can run in any order or at once, the levels in order, with the result of
+    the sequential loop (_merge_split_widget.py:123-134).  Ids that do not occur in ``table`` are in no level.
+
+    ``Erode`` / ``Open`` never leave a label's own voxels: every label is independent of every other, and everything is one
+    level -- but for a repeated id, whose turns follow each other.  ``Dilate`` / ``Close`` write into the box padded by the
+    radius: two turns conflict when their padded boxes intersect, and a turn's level is 1 + the highest level of an earlier
+    turn it conflicts with.  A turn's box is the ``LabelTable``'s; a repeated id's later turns take it grown by the radius per
+    earlier turn, which is where that label can have got to by then."""
+    radius = _morph_args(operation, radius, 'morph_schedule')
+    ids, rows, lo, hi = _morph_turns(table, turns, radius, operation)
+    grows = operation in _MORPH_GROWS
+    level = np.zeros(len(ids), np.int64)      # 0: in no level
+    plo, phi = lo - radius, hi + radius
+    for i in range(len(ids)):
+        if rows[i] < 0:
+            continue
+        if grows:
+            hit = (rows[:i] >= 0) & (plo[:i] < phi[i]).all(axis=1) & (plo[i] < phi[:i]).all(axis=1)
+        else:
+            hit = ids[:i] == ids[i]
+        level[i] = 1 + (level[:i][hit].max() if hit.any() else 0)
+    return [np.flatnonzero(level == l).tolist() for l in range(1, int(level.max()) + 1 if len(level) else 1)]
+
+
+def _morph_tiles(table, turns, radius, operation, ball, levels, core):
+    """(tiles (n, 4) int32 {turn, z0, y0, x0}, level offsets (len(levels) + 1) int64, boxes (turns, 6) uint32, frames (turns, 6)
+    int64 {z0, y0, x0, nz, ny, nx}): the tile lists of emp_morph_labels / emp_fill_holes_labels.  A turn's tiles cover its frame:
+    the box its label can lie in, padded by the radius and clipped to the array."""
+    ids, rows, lo, hi = _morph_turns(table, turns, radius, operation)
+    shape = np.asarray(dims3(table.shape), np.int64)
+    pad = np.asarray([radius if (ball or a > 0) else 0 for a in range(3)], np.int64)
+    boxes = np.zeros((len(ids), 6), np.uint32)
+    boxes[:, :3] = 0xffffffff
+    frames = np.zeros((len(ids), 6), np.int64)
+    tiles, offsets, n = [], [0], 0
+    for k, lvl in enumerate(levels):
+        for i in lvl:
+            l3, h3 = box3(lo[i], hi[i])
+            if k == 0:      # nothing has been written yet: the table's box is the label's box
+                boxes[i, :3], boxes[i, 3:] = l3, h3 - 1
+            a = np.maximum(l3 - pad, 0)
+            b = np.minimum(h3 + pad, shape)
+            frames[i, :3], frames[i, 3:] = a, b - a
+            grid = np.meshgrid(*[np.arange(a[d], b[d], core[d]) for d in range(3)], indexing='ij')
+            tiles.append(np.stack([np.full(grid[0].size, i, np.int64)] + [g.reshape(-1) for g in grid], axis=1))
+            n += grid[0].size
+        offsets.append(n)
+    tiles = np.concatenate(tiles).astype(np.int32) if tiles else np.zeros((0, 4), np.int32)
+    return np.ascontiguousarray(tiles), np.asarray(offsets, np.int64), boxes, frames
+
+
+def fill_placement(frames, levels):
+    """Where the entries of Fill holes' parent and size arrays lie: ``frames`` (turns, 6) and the ``levels`` of ``_morph_tiles``
+    -> (placed (turns, 7) int64: a frame and its offset, the number of entries).  A turn's entries follow those of the turns
+    before it in its level, and the arrays are as large as the largest level."""
+    placed = np.zeros((len(frames), 7), np.int64)
+    placed[:, :6] = frames
+    entries = 0
+    for k, lvl in enumerate(levels):
+        voxels = frames[lvl, 3:].prod(axis=1)
+        if int(voxels.sum()) >= FILL_MAX_LEVEL_VOXELS:
+            raise ValueError(f'fill_label_holes: the padded boxes of the turns of level {k} hold {int(voxels.sum())} voxels; a level '
+                             'must hold fewer than 2^31 - 1 (pass fewer or smaller labels as ids=)')
+        placed[lvl, 6] = np.cumsum(voxels) - voxels
+        entries = max(entries, int(voxels.sum()))
+    return placed, entries
+
+
+# ----------------------------------------------------------------------------
+# Split Labels
+# ----------------------------------------------------------------------------
+def split_spacing(coords, values, min_distance):
+    """``ensure_spacing`` of ``peak_local_max``, restated: the candidates ``coords`` (n, ndim) with their ``values`` by value
+    descending, stable over the order given (raster order); one is kept unless a kept one lies at Euclidean distance
+    < ``min_distance`` (strictly) -> the indices kept, in the order they were kept.  Recalled from skimage's source, not pinned."""
+    if len(values) == 0:
+        return np.zeros(0, np.int64)
+    coords = np.asarray(coords, dtype=np.int64).reshape(len(values), -1)
+    order = np.argsort(-np.asarray(values, dtype=np.int64), kind='stable')
+    kept = np.zeros((len(order), coords.shape[1]), np.int64)
+    idx, n, d2 = [], 0, int(min_distance) ** 2
+    for i in order.tolist():
+        if n and (((kept[:n] - coords[i]) ** 2).sum(axis=1) < d2).any():
+            continue
+        kept[n] = coords[i]
+        n += 1
+        idx.append(i)
+    return np.asarray(idx, dtype=np.int64)
+
+
+def split_marker_ids(coords):
+    """``ndi.label(marker mask)[0]`` (connectivity 1, _merge_split_widget.py:446,454) at the voxels ``coords`` (n, ndim) without
+    the mask: voxels that are face neighbours share an id, and ids count the components in raster order of their first voxel
+    -> (ids (n,) int64 from 1, the number of components).  A voxel given twice is one voxel."""
+    coords = np.asarray(coords, dtype=np.int64)
+    if len(coords) == 0:
+        return np.zeros(0, np.int64), 0
+    where = {tuple(c): i for i, c in enumerate(coords.tolist())}
+    parent = list(range(len(coords)))
+
+    def find(i):
+        while parent[i] != i:
+            parent[i] = parent[parent[i]]
+            i = parent[i]
+        return i
+    for i, c in enumerate(coords.tolist()):
+        parent[i] = find(where[tuple(c)])      # a repeated voxel
+        for a in range(len(c)):
+            j = where.get(tuple(c[:a] + [c[a] - 1] + c[a + 1:]))
+            if j is not None:
+                ri, rj = find(i), find(j)
+                if ri != rj:
+                    parent[max(ri, rj)] = min(ri, rj)
+    ids, seen = np.zeros(len(coords), np.int64), {}
+    for i in np.lexsort(coords.T[::-1]).tolist():
+        ids[i] = seen.setdefault(find(i), len(seen) + 1)
+    return ids, len(seen)
+
+
+def split_turns(points, under, ids):
+    """The turns of the loop, in ``np.unique`` order, zeros dropped (:498-517): the labels ``under`` the ``points`` (those on the
+    background are dropped, :501-505), or ``ids`` -> (turns, the points kept, the labels under them); without points the last
+    two are None."""
+    if points is not None:
+        return np.unique(under[under != 0]), points[under != 0], under[under != 0]
+    turns = np.unique(np.asarray(ids, dtype=np.int64).reshape(-1))
+    return turns[turns > 0], None, None
+
+
+def split_passes(table, turns, start_label):
+    """The turns in the groups that can each be computed in full before anything is written: one, or two.
+
+    Computing everything first is the sequential loop as long as no turn writes an id that a later turn picks.  One can: a part
+    of a label that no marker reaches becomes max_label itself (:544), the array's largest label, and when that label has a turn
+    of its own -- the last one, the turns being sorted -- the loop lets it see those voxels.  So that turn is a second group,
+    which runs on the array as the first left it."""
+    if len(turns) > 1 and len(table.labels) and turns[-1] == table.labels.max() and (start_label is None or int(start_label) - 1 == turns[-1]):
+        return [turns[:-1], turns[-1:]]
+    return [turns]
+
+
+def split_screen(table, turns, points_as_markers):
+    """Which turns have something to compute -> (report, todo): the report with 'label absent' and 'nothing to split' filled in
+    and None for the turns still open; per open turn a row of ``todo`` (m, 7) int64 {its index among the turns, the start z0, y0,
+    x0 and the sides nz, ny, nx of its label's box on three axes}.  A label that fills its box has no background: nothing to
+    split by distance.  A box the kernels cannot index raises a ``ValueError``."""
+    nd = len(table.shape)
+    report, todo = [None] * len(turns), []
+    for i, row in enumerate(table_rows(table, turns).tolist()):
+        if row < 0:
+            report[i] = 'label absent'
+            continue
+        l3, h3 = box3(table.boxes[row, :nd], table.boxes[row, nd:])
+        n3 = h3 - l3
+        if not points_as_markers and int(n3.prod()) == int(table.areas[row]):
+            report[i] = 'nothing to split'
+            continue
+        if int((n3 ** 2).sum()) >= SPLIT_MAX_DIAGONAL2 or int(n3.prod()) > SPLIT_MAX_ENTRIES:
+            raise ValueError(f'split_labels: the box of label {int(turns[i])}, {tuple(n3[3 - nd:].tolist())}, is too large: the squares of its '
+                             'sides must add up to less than 2^30 and it must hold fewer than 2^31 - 1 voxels')
+        todo.append([i, *l3, *n3])
+    return report, np.asarray(todo, np.int64).reshape(-1, 7)
+
+
+def _split_batches(voxels):
+    """consecutive turns per launch: at most SPLIT_MAX_BOXES of them with at most SPLIT_MAX_ENTRIES voxels"""
+    batches, cur, n = [], [], 0
+    for i, v in enumerate(voxels):
+        if cur and (len(cur) == SPLIT_MAX_BOXES or n + v > SPLIT_MAX_ENTRIES):
+            batches.append(cur)
+            cur, n = [], 0
+        cur.append(i)
+        n += v
+    return batches + ([cur] if cur else [])
+
+
+def split_boxes(turns, todo):
+    """the boxes of a launch as emp_split_* read them, from its rows of ``split_screen``'s ``todo``: (n, 8) int64 {z0, y0, x0, nz,
+    ny, nx, offset of the box's first voxel among the launch's entries, label}"""
+    boxes = np.zeros((len(todo), 8), np.int64)
+    boxes[:, :6], boxes[:, 7] = todo[:, 1:], turns[todo[:, 0]]
+    voxels = boxes[:, 3:6].prod(axis=1)
+    boxes[:, 6] = np.cumsum(voxels) - voxels
+    return boxes
+
+
+def split_point_markers(points, under, boxes):
+    """points mode: per box the marker voxels (z, y, x) inside it, each once: the points on the box's label"""
+    points3 = np.concatenate([np.zeros((len(points), 3 - points.shape[1]), np.int64), points], axis=1)
+    return [np.unique(points3[under == box[7]] - box[:3], axis=0) for box in boxes]
+
+
+def split_peak_markers(cand, counts, boxes, min_distance):
+    """distance mode: per box the marker voxels (z, y, x) inside it: of the box's candidates {box, linear index, value} -- the
+    rows of ``cand`` box after box, ``counts`` of them each -- those that ``split_spacing`` keeps"""
+    per_box = []
+    for box, mine in zip(boxes, np.split(cand, np.cumsum(counts)[:-1])):
+        coords = np.stack(np.unravel_index(mine[:, 1], tuple(box[3:6])), axis=1).reshape(-1, 3)
+        per_box.append(coords[split_spacing(coords, mine[:, 2], min_distance)])
+    return per_box
+
+
+def split_marker_array(per_box, boxes):
+    """The markers of a launch from the marker voxels of its boxes -> (markers (m, 3) int32 {box, linear index in the box, id from
+    1}, the number of markers per box).  Face neighbours are one marker (``split_marker_ids``); a box with fewer than two has
+    nothing to split and nothing to flood, and none of its voxels are listed."""
+    markers, n_markers = [], np.zeros(len(boxes), np.int64)
+    for k, coords in enumerate(per_box):
+        mids, n_markers[k] = split_marker_ids(coords)
+        if n_markers[k] >= 2:
+            lin = np.ravel_multi_index(tuple(coords.T), tuple(boxes[k, 3:6]))
+            markers.append(np.stack([np.full(len(lin), k, np.int64), lin, mids], axis=1))
+    if len(n_markers) and n_markers.max() > SPLIT_MAX_MARKERS:
+        raise ValueError(f'split_labels: more than 2^30 - 1 markers in one label')
+    markers = np.ascontiguousarray(np.concatenate(markers).astype(np.int32)) if markers else np.zeros((0, 3), np.int32)
+    return markers, n_markers
+
+
+def split_ids(turns, report, launches, cur_max, start_label, eb):
+    """The ids, turn by turn as the loop would hand them out (:533-545), before anything is written.  ``report``: that of
+    ``split_screen``; ``launches``: per launch (the indices of its turns, their numbers of markers); ``cur_max``: the array's
+    largest label; ``eb``: the array's element size in bytes, negative for a signed type: the new ids must fit it.
+    -> (the report completed: per turn the new ids, 'nothing to split' or 'ids in use'; per launch the ``bases`` of its boxes:
+    max_label, or -1 where nothing is written).  ``max_label`` is the array's maximum when the turn comes -- it moves with every
+    split -- or ``start_label - 1``, and the write is refused when the maximum is >= the smallest new id (:540)."""
+    top = min((1 << (8 * abs(eb) - (1 if eb < 0 else 0))) - 1, (1 << 63) - 1)
+    report, all_bases = list(report), []
+    for which, n_markers in launches:
+        bases = np.full(len(which), -1, np.int64)
+        all_bases.append(bases)
+        for k, i in enumerate(which):
+            n = int(n_markers[k])
+            if n < 2:
+                report[i] = 'nothing to split'
+                continue
+            max_label = cur_max if start_label is None else int(start_label) - 1
+            if cur_max >= max_label + 1:
+                report[i] = 'ids in use'
+                continue
+            if max_label + n > top:
+                raise ValueError(f'split_labels: the new ids of label {int(turns[i])}, up to {max_label + n}, do not fit the '
+                                 f'array\'s {abs(eb)}-byte {"signed" if eb < 0 else "unsigned"} type; nothing was written')
+            bases[k] = max_label
+            cur_max = max_label + n
+            report[i] = max_label + np.arange(1, n + 1, dtype=np.int64)
+    return report, all_bases

@@ -19,7 +19,14 @@ levels whose turns touch disjoint parts of the array; a level is two or three la
 6-connected components of the background of every crop, by union-find over the same levels and tile lists.
 ``split_labels`` (csrc/split.hip) is Split Labels (_merge_split_widget.py:422-634): per label an exact distance transform, the
 candidates of ``peak_local_max`` and a marker flood inside the label's tight box, batched over the labels of a call; the greedy
-spacing of the peaks (``split_spacing``), ``ndi.label`` of the few survivors (``split_marker_ids``) and the id bookkeeping run here.
+spacing of the peaks (``split_spacing``), ``ndi.label`` of the few survivors (``split_marker_ids``) and the id bookkeeping run on
+the host.
+
+What these three tools decide on the host lives in ``_labelplan.py``, which imports numpy only: the footprints, ``morph_schedule``
+and the tile lists, the placement of Fill holes' work arrays, and of Split Labels the turns, the rule that gives the largest label
+a second pass, the screening of the boxes, the boxes and markers of a launch and the loop that hands out the new ids.  This module
+keeps their device drivers (``_morph_device``, ``_fill_device``, ``_split_device``: allocate, upload, call the library) and
+re-exports the public names.
 
 Inputs are those of ``metrics.label_overlap``: device tensors (read in place), numpy arrays and chunked stores
 (``zstore.DirArray``, zarr arrays) streamed in leading-axis slabs through pinned staging buffers.  An edit returns the kind of
@@ -46,7 +53,10 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _abi
+from . import _abi, _labelplan as P
+from ._labelplan import (FILL_MAX_HOLE_SIZE, FILL_MAX_LEVEL_VOXELS, MORPH_MAX_RADIUS, MORPH_OPS, SPLIT_MAX_BOXES, SPLIT_MAX_DIAGONAL2,  # noqa: F401
+                         SPLIT_MAX_DISTANCE, SPLIT_MAX_ENTRIES, _MORPH_GROWS, _morph_args, _morph_tiles, _morph_turns, _split_batches, dims3,
+                         morph_footprint_offsets, morph_footprint_rows, morph_schedule, split_marker_ids, split_spacing)
 from ._labelstream import GrowableTable, RawSource, ebytes, hp, initial_capacity, need_device, pick_device, slab_plan, source, stream_slabs
 
 __all__ = ['LabelTable', 'label_table', 'table_from_arrays', 'LabelMeasures', 'measure_labels', 'measures_from_arrays', 'small_labels', 'boundary_labels', 'count_labels', 'class_label_lists',
@@ -647,41 +657,52 @@ def remove_boundary_labels(labels, whole_labels=False, per_slice=False, device=N
                              f'{shape}; use whole_labels=True (removes whole labels by their boxes, slab by slab)')
         # what the call cannot do is said before any work: nothing is written, on the device or to the caller's array, by then
         target = _edit_target(labels, out, inplace, shape, labels.dtype, what)
-        on_device = isinstance(labels, torch.Tensor)      # a tensor that passed the check is on the device
-        if on_device:
-            t = labels if labels.is_contiguous() else labels.contiguous()
-        else:
-            host = np.ascontiguousarray(np.asarray(labels[...] if not _is_numpy(labels) else labels))
-            t = torch.from_numpy(host.view(np.uint8).reshape(-1)).to(device)      # as bytes: torch has no arithmetic on uint16 / uint32
-        eb = ebytes(t.dtype if on_device else host.dtype)
-        before = _table_of_source(RawSource(t, eb, shape), shape, per_slice, device, None, None)
-        # the largest label of any row: a per-slice table is sorted by slice first, its last row is only the last slice's
-        top = int(before.labels.max()) if len(before.labels) else 0
-        if top > CCL_MAX_LABEL:
-            raise ValueError(f'{what}: the connected components of the reference mode need labels below 2^31 - 1, the array holds '
-                             f'{top}; use whole_labels=True')
-        lib = _abi.load()
-        # component ids: per image (8-connected) or of the one volume (26-connected)
-        images = len(shape) == 2 or per_slice
-        N, depth, cH, cW = (shape[0] if len(shape) == 3 else 1, 0, shape[-2], shape[-1]) if images else (1, shape[0], shape[1], shape[2])
-        wide = _as_ccl_input(t, eb, shape)
-        comps = torch.empty((N if images else depth, cH, cW), dtype=torch.int32, device=device)
-        work = torch.empty(int(lib.emp_ccl8_work_bytes(N, cH, cW) if images else lib.emp_ccl8_work_bytes(1, depth * cH, cW)),
-                           dtype=torch.uint8, device=device)
-        _abi.check(lib.emp_ccl_range(_abi.ptr(wide), 8 if wide.dtype == torch.int64 else 4, N, depth, cH, cW, 1, CCL_MAX_LABEL + 1,
-                                     _abi.ptr(comps), None, _abi.ptr(work), _abi.stream_ptr(device)), 'emp_ccl_range')
-        del wide, work
-        # components are numbered per image: their key is slice << 32 | id there
-        ctable = _table_of_source(RawSource(comps, -4, tuple(comps.shape)), tuple(comps.shape), images, device, None, None)
-        cids = boundary_labels(ctable)
-        m = _Map(_map_keys(cids, images), np.zeros(len(cids), np.int64), device)
-        res = t if (inplace and on_device) else torch.empty_like(t)
-        m.apply(comps.data_ptr(), -4, t.data_ptr(), eb, res.data_ptr(), 0, comps.shape[0], cH, cW, images, device)
-        after = _table_of_source(RawSource(res, eb, shape), shape, per_slice, device, None, None)
-        n_removed = _vanished(before, after)
-        if on_device:
-            return res, n_removed
-        return _write_back(target, 0, shape[0], res.cpu(), host.dtype, shape), n_removed
+        edit_own = bool(inplace) and isinstance(labels, torch.Tensor)      # the result replaces the caller's tensor
+        return _whole_array(labels, target, device, False, lambda t, eb: _clear_border(t, eb, shape, per_slice, edit_own, device))
+
+
+def _whole_array(labels, target, device, clone, run):
+    """The way of a whole array to the device and back, for the tools that need all of it there at once.  ``labels``: a device
+    tensor or host data that passed ``_edit_target``, which chose ``target``.  ``run(t, eb)`` gets it as one contiguous device
+    buffer -- the tensor itself, a clone of it with ``clone``, or host data uploaded as bytes (torch has no arithmetic on uint16 /
+    uint32) -- and returns (the device buffer that holds the result, anything else) -> (the result as the kind that was given: that
+    buffer for a device tensor, else downloaded into the target, anything else)."""
+    if isinstance(labels, torch.Tensor):      # a tensor that passed the check is on the device
+        t = labels if labels.is_contiguous() else labels.contiguous()
+        return run(t.clone() if clone else t, ebytes(t.dtype))
+    host = np.ascontiguousarray(labels if _is_numpy(labels) else labels[...])
+    res, rest = run(torch.from_numpy(host.view(np.uint8).reshape(-1)).to(device), ebytes(host.dtype))
+    return _write_back(target, 0, host.shape[0], res.cpu(), host.dtype, host.shape), rest
+
+
+def _clear_border(t, eb, shape, per_slice, edit_own, device):
+    """``clear_border`` on the contiguous device buffer ``t`` -> (the device buffer with the result -- ``t`` itself with
+    ``edit_own`` --, the number of labels that vanished)"""
+    before = _table_of_source(RawSource(t, eb, shape), shape, per_slice, device, None, None)
+    # the largest label of any row: a per-slice table is sorted by slice first, its last row is only the last slice's
+    top = int(before.labels.max()) if len(before.labels) else 0
+    if top > CCL_MAX_LABEL:
+        raise ValueError('remove_boundary_labels: the connected components of the reference mode need labels below 2^31 - 1, the array '
+                         f'holds {top}; use whole_labels=True')
+    lib = _abi.load()
+    # component ids: per image (8-connected) or of the one volume (26-connected)
+    images = len(shape) == 2 or per_slice
+    N, depth, cH, cW = (shape[0] if len(shape) == 3 else 1, 0, shape[-2], shape[-1]) if images else (1, shape[0], shape[1], shape[2])
+    wide = _as_ccl_input(t, eb, shape)
+    comps = torch.empty((N if images else depth, cH, cW), dtype=torch.int32, device=device)
+    work = torch.empty(int(lib.emp_ccl8_work_bytes(N, cH, cW) if images else lib.emp_ccl8_work_bytes(1, depth * cH, cW)),
+                       dtype=torch.uint8, device=device)
+    _abi.check(lib.emp_ccl_range(_abi.ptr(wide), 8 if wide.dtype == torch.int64 else 4, N, depth, cH, cW, 1, CCL_MAX_LABEL + 1,
+                                 _abi.ptr(comps), None, _abi.ptr(work), _abi.stream_ptr(device)), 'emp_ccl_range')
+    del wide, work
+    # components are numbered per image: their key is slice << 32 | id there
+    ctable = _table_of_source(RawSource(comps, -4, tuple(comps.shape)), tuple(comps.shape), images, device, None, None)
+    cids = boundary_labels(ctable)
+    m = _Map(_map_keys(cids, images), np.zeros(len(cids), np.int64), device)
+    res = t if edit_own else torch.empty_like(t)
+    m.apply(comps.data_ptr(), -4, t.data_ptr(), eb, res.data_ptr(), 0, comps.shape[0], cH, cW, images, device)
+    after = _table_of_source(RawSource(res, eb, shape), shape, per_slice, device, None, None)
+    return res, _vanished(before, after)
 
 
 def _as_ccl_input(t, eb, shape):
@@ -701,126 +722,6 @@ def _as_ccl_input(t, eb, shape):
 # ----------------------------------------------------------------------------
 # Morph Labels
 # ----------------------------------------------------------------------------
-MORPH_OPS = {'Dilate': 0, 'Erode': 1, 'Close': 2, 'Open': 3}      # the widget's strings (_merge_split_widget.py:48-53) -> EMP_MORPH_*
-MORPH_MAX_RADIUS = 7      # the widget's slider (:73)
-_MORPH_GROWS = ('Dilate', 'Close')
-
-
-def _morph_args(operation, radius, what):
-    if operation not in MORPH_OPS:
-        raise ValueError(f"{what}: operation must be one of {list(MORPH_OPS)}, got {operation!r} ('Fill holes' is fill_label_holes)")
-    if isinstance(radius, bool) or int(radius) != radius or not 1 <= int(radius) <= MORPH_MAX_RADIUS:
-        raise ValueError(f'{what}: radius must be an integer in 1..{MORPH_MAX_RADIUS}, got {radius!r}')
-    return int(radius)
-
-
-def morph_footprint_rows(radius, ball):
-    """The footprint as the kernel walks it: rows (dz, dy, h) of ``disk(radius)`` (``ball`` false: dz = 0 only) or
-    ``ball(radius)``, each the x-interval [-h, h] with h = floor(sqrt(r^2 - dy^2 - dz^2)) in integers."""
-    r = _morph_args('Dilate', radius, 'morph_footprint_rows')
-    rows = []
-    for dz in (range(-r, r + 1) if ball else (0,)):
-        for dy in range(-r, r + 1):
-            rem = r * r - dz * dz - dy * dy
-            if rem < 0:
-                continue
-            h = 0
-            while (h + 1) * (h + 1) <= rem:
-                h += 1
-            rows.append((dz, dy, h))
-    return np.asarray(rows, dtype=np.int64).reshape(-1, 3)
-
-
-def morph_footprint_offsets(radius, ndim):
-    """the offsets (k, ndim) of ``disk(radius)`` (ndim 2) / ``ball(radius)`` (ndim 3), sorted: ``morph_footprint_rows`` expanded"""
-    if ndim not in (2, 3):
-        raise ValueError('morph_footprint_offsets: ndim 2 (disk) or 3 (ball)')
-    offs = [(dz, dy, dx) for dz, dy, h in morph_footprint_rows(radius, ndim == 3).tolist() for dx in range(-h, h + 1)]
-    offs = np.asarray(sorted(offs), dtype=np.int64).reshape(-1, 3)
-    return offs if ndim == 3 else offs[:, 1:]
-
-
-def _morph_turns(table, turns, radius, operation):
-    """(ids, rows, lo, hi): per turn its label, its row of the table (-1: the id does not occur) and the box that holds the
-    label's voxels when the turn comes (exclusive upper ends, not clipped): the table's box, grown by the radius for every
-    earlier turn of the same id where the operation can grow a label."""
-    if table.per_slice:
-        raise ValueError('morph_schedule: a whole-array table is needed')
-    ids = np.asarray(turns, dtype=np.int64).reshape(-1)
-    nd = table.boxes.shape[1] // 2
-    rows = np.full(len(ids), -1, np.int64)
-    if len(table.labels):
-        pos = np.minimum(np.searchsorted(table.labels, ids), len(table.labels) - 1)
-        rows = np.where((ids > 0) & (table.labels[pos] == ids), pos, -1)
-    lo = np.zeros((len(ids), nd), np.int64)
-    hi = np.zeros((len(ids), nd), np.int64)
-    earlier = {}
-    for i, (l, row) in enumerate(zip(ids.tolist(), rows.tolist())):
-        if row < 0:
-            continue
-        k = earlier.get(l, 0)
-        earlier[l] = k + 1
-        grow = radius * k if operation in _MORPH_GROWS else 0
-        lo[i] = table.boxes[row, :nd] - grow
-        hi[i] = table.boxes[row, nd:] + grow
-    return ids, rows, lo, hi
-
-
-def morph_schedule(table, turns, radius, operation):
-    """The loop of Morph Labels over ``turns`` (label ids in the loop's order, a repeat being a second turn) as levels: a list
-    of lists of turn indices.  The turns of a level can run in any order or at once, the levels in order, with the result of
-    the sequential loop (_merge_split_widget.py:123-134).  Ids that do not occur in ``table`` are in no level.
-
-    ``Erode`` / ``Open`` never leave a label's own voxels: every label is independent of every other, and everything is one
-    level -- but for a repeated id, whose turns follow each other.  ``Dilate`` / ``Close`` write into the box padded by the
-    radius: two turns conflict when their padded boxes intersect, and a turn's level is 1 + the highest level of an earlier
-    turn it conflicts with.  A turn's box is the ``LabelTable``'s; a repeated id's later turns take it grown by the radius per
-    earlier turn, which is where that label can have got to by then."""
-    radius = _morph_args(operation, radius, 'morph_schedule')
-    ids, rows, lo, hi = _morph_turns(table, turns, radius, operation)
-    grows = operation in _MORPH_GROWS
-    level = np.zeros(len(ids), np.int64)      # 0: in no level
-    plo, phi = lo - radius, hi + radius
-    for i in range(len(ids)):
-        if rows[i] < 0:
-            continue
-        if grows:
-            hit = (rows[:i] >= 0) & (plo[:i] < phi[i]).all(axis=1) & (plo[i] < phi[:i]).all(axis=1)
-        else:
-            hit = ids[:i] == ids[i]
-        level[i] = 1 + (level[:i][hit].max() if hit.any() else 0)
-    return [np.flatnonzero(level == l).tolist() for l in range(1, int(level.max()) + 1 if len(level) else 1)]
-
-
-def _morph_tiles(table, turns, radius, operation, ball, levels, core):
-    """(tiles (n, 4) int32 {turn, z0, y0, x0}, level offsets (len(levels) + 1) int64, boxes (turns, 6) uint32, frames (turns, 6)
-    int64 {z0, y0, x0, nz, ny, nx}): the tile lists of emp_morph_labels / emp_fill_holes_labels.  A turn's tiles cover its frame:
-    the box its label can lie in, padded by the radius and clipped to the array."""
-    ids, rows, lo, hi = _morph_turns(table, turns, radius, operation)
-    nd = lo.shape[1]
-    shape = np.asarray((1,) * (3 - nd) + tuple(table.shape), np.int64)
-    pad = np.asarray([radius if (ball or a > 0) else 0 for a in range(3)], np.int64)
-    boxes = np.zeros((len(ids), 6), np.uint32)
-    boxes[:, :3] = 0xffffffff
-    frames = np.zeros((len(ids), 6), np.int64)
-    tiles, offsets, n = [], [0], 0
-    for k, lvl in enumerate(levels):
-        for i in lvl:
-            l3 = np.concatenate([np.zeros(3 - nd, np.int64), lo[i]])
-            h3 = np.concatenate([np.ones(3 - nd, np.int64), hi[i]])
-            if k == 0:      # nothing has been written yet: the table's box is the label's box
-                boxes[i, :3], boxes[i, 3:] = l3, h3 - 1
-            a = np.maximum(l3 - pad, 0)
-            b = np.minimum(h3 + pad, shape)
-            frames[i, :3], frames[i, 3:] = a, b - a
-            grid = np.meshgrid(*[np.arange(a[d], b[d], core[d]) for d in range(3)], indexing='ij')
-            tiles.append(np.stack([np.full(grid[0].size, i, np.int64)] + [g.reshape(-1) for g in grid], axis=1))
-            n += grid[0].size
-        offsets.append(n)
-    tiles = np.concatenate(tiles).astype(np.int32) if tiles else np.zeros((0, 4), np.int32)
-    return np.ascontiguousarray(tiles), np.asarray(offsets, np.int64), boxes, frames
-
-
 def _morph_plan(t, eb, shape, ids, radius, operation, ball, core, device):
     """What a device loop over the labels of the contiguous buffer ``t`` starts from: the turns (``ids``, or every label
     ascending), their levels under ``operation``'s scheduling rule, the tile lists for tiles of ``core`` and the statistics"""
@@ -837,91 +738,77 @@ def _morph_plan(t, eb, shape, ids, radius, operation, ball, core, device):
     return turns, levels, tiles, offsets, boxes, frames, stats
 
 
-def _timed_launches(stats, events, call):
-    """``call()`` launches the levels and returns the number of launches; with ``events`` a pair of HIP events around it"""
+def _stage(events, name, entry, *args):
+    """the library's ``entry(*args)``; with a list ``events``, between a pair of HIP events that is appended to it under ``name``"""
+    pair = None if events is None else (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+    if pair:
+        pair[0].record()
+    _abi.check(getattr(_abi.load(), entry)(*args), entry)
+    if pair:
+        pair[1].record()
+        events.append((name, *pair))
+
+
+def _timed_launches(stats, events, entry, *args):
+    """The launches of the levels: the library's ``entry(*args, launch counter)`` -> ``stats`` with the number of launches and,
+    with ``events``, a pair of HIP events around them"""
+    launches, pair = C.c_int(0), ([] if events else None)
+    _stage(pair, entry, entry, *args, C.byref(launches))
+    stats['launches'] = launches.value
     if events:
-        stats['events'] = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        stats['events'][0].record()
-    stats['launches'] = call()
-    if events:
-        stats['events'][1].record()
+        stats['events'] = pair[0][1:]
     return stats
+
+
+def _upload_turns(turns, boxes, tiles, device):
+    """what both device loops upload: the labels of the turns, their boxes and the tile list"""
+    return [torch.from_numpy(a).to(device) for a in (turns.astype(np.int64), boxes.view(np.int32), tiles)]
 
 
 def _morph_device(t, eb, shape, operation, radius, ball, ids, device, events=False):
     """Morph Labels in place on the contiguous device buffer ``t`` (element size ``eb``, a 2-D or 3-D ``shape``) -> statistics:
     turns, levels, tiles, launches and, with ``events``, a pair of HIP events around the launches (for tools/morph_labels_bench.py)"""
-    lib = _abi.load()
     op = MORPH_OPS[operation]
     cz, cy, cx = C.c_int(0), C.c_int(0), C.c_int(0)
-    _abi.check(lib.emp_morph_tile_shape(radius, int(ball), op, C.byref(cz), C.byref(cy), C.byref(cx)), 'emp_morph_tile_shape')
+    _abi.check(_abi.load().emp_morph_tile_shape(radius, int(ball), op, C.byref(cz), C.byref(cy), C.byref(cx)), 'emp_morph_tile_shape')
     turns, levels, tiles, offsets, boxes, _, stats = _morph_plan(t, eb, shape, ids, radius, operation, ball, (cz.value, cy.value, cx.value),
                                                                  device)
     if len(tiles) == 0:
         return stats
-    D, H, W = (1,) * (3 - len(shape)) + tuple(shape)
-    d_labels = torch.from_numpy(turns.astype(np.int64)).to(device)
-    d_boxes = torch.from_numpy(boxes.view(np.int32)).to(device)
-    d_tiles = torch.from_numpy(tiles).to(device)
+    d_labels, d_boxes, d_tiles = _upload_turns(turns, boxes, tiles, device)
     words = int(np.diff(offsets).max()) * cz.value * cy.value
     scratch = torch.empty(words, dtype=torch.int64, device=device)
-
-    def call():
-        launches = C.c_int(0)
-        _abi.check(lib.emp_morph_labels(C.c_void_p(t.data_ptr()), eb, D, H, W, radius, int(ball), op, _abi.ptr(d_labels), _abi.ptr(d_boxes),
-                                        len(turns), _abi.ptr(d_tiles), hp(offsets), len(levels), _abi.ptr(scratch), words,
-                                        _abi.stream_ptr(device), C.byref(launches)), 'emp_morph_labels')
-        return launches.value
-    return _timed_launches(stats, events, call)
-
-
-FILL_MAX_HOLE_SIZE = (1 << 31) - 1      # no component can have more voxels: a level's boxes hold fewer (FILL_MAX_LEVEL_VOXELS)
-FILL_MAX_LEVEL_VOXELS = (1 << 31) - 1      # emp_fill_holes_labels: int32 entries of the parent / size arrays
+    return _timed_launches(stats, events, 'emp_morph_labels', C.c_void_p(t.data_ptr()), eb, *dims3(shape), radius, int(ball), op,
+                           _abi.ptr(d_labels), _abi.ptr(d_boxes), len(turns), _abi.ptr(d_tiles), hp(offsets), len(levels), _abi.ptr(scratch),
+                           words, _abi.stream_ptr(device))
 
 
 def _fill_device(t, eb, shape, radius, hole_size, ball, ids, device, events=False):
     """Fill holes in place on the contiguous device buffer ``t`` -> the statistics of ``_morph_device`` and ``scratch_entries``.
     A turn writes only inside its padded box and reads only ``== label``: the levels are those of a dilation.  The parent and
     size arrays hold one entry per voxel of the frames (padded, clipped boxes) of the largest level, not of the array."""
-    lib = _abi.load()
     cz, cy, cx = C.c_int(0), C.c_int(0), C.c_int(0)
-    _abi.check(lib.emp_fill_holes_tile_shape(int(ball), C.byref(cz), C.byref(cy), C.byref(cx)), 'emp_fill_holes_tile_shape')
+    _abi.check(_abi.load().emp_fill_holes_tile_shape(int(ball), C.byref(cz), C.byref(cy), C.byref(cx)), 'emp_fill_holes_tile_shape')
     turns, levels, tiles, offsets, boxes, frames, stats = _morph_plan(t, eb, shape, ids, radius, 'Dilate', ball,
                                                                       (cz.value, cy.value, cx.value), device)
     stats['scratch_entries'] = 0
     if len(tiles) == 0:
         return stats
-    # a turn's entries follow those of the turns before it in its level
-    placed = np.zeros((len(turns), 7), np.int64)
-    placed[:, :6] = frames
-    entries = 0
-    for k, lvl in enumerate(levels):
-        voxels = frames[lvl, 3:].prod(axis=1)
-        if int(voxels.sum()) >= FILL_MAX_LEVEL_VOXELS:
-            raise ValueError(f'fill_label_holes: the padded boxes of the turns of level {k} hold {int(voxels.sum())} voxels; a level '
-                             'must hold fewer than 2^31 - 1 (pass fewer or smaller labels as ids=)')
-        placed[lvl, 6] = np.cumsum(voxels) - voxels
-        entries = max(entries, int(voxels.sum()))
-    stats['scratch_entries'] = entries
-    D, H, W = (1,) * (3 - len(shape)) + tuple(shape)
-    d_labels = torch.from_numpy(turns.astype(np.int64)).to(device)
-    d_boxes = torch.from_numpy(boxes.view(np.int32)).to(device)
+    placed, stats['scratch_entries'] = P.fill_placement(frames, levels)
+    d_labels, d_boxes, d_tiles = _upload_turns(turns, boxes, tiles, device)
     d_frames = torch.from_numpy(placed).to(device)
-    d_tiles = torch.from_numpy(tiles).to(device)
-    parent = torch.empty(entries, dtype=torch.int32, device=device)
-    size = torch.empty(entries, dtype=torch.int32, device=device)
-
-    def call():
-        launches = C.c_int(0)
-        _abi.check(lib.emp_fill_holes_labels(C.c_void_p(t.data_ptr()), eb, D, H, W, radius, int(ball), hole_size, _abi.ptr(d_labels),
-                                             _abi.ptr(d_boxes), _abi.ptr(d_frames), len(turns), _abi.ptr(d_tiles), hp(offsets), len(levels),
-                                             _abi.ptr(parent), _abi.ptr(size), entries, _abi.stream_ptr(device), C.byref(launches)),
-                   'emp_fill_holes_labels')
-        return launches.value
-    return _timed_launches(stats, events, call)
+    parent, size = (torch.empty(stats['scratch_entries'], dtype=torch.int32, device=device) for _ in range(2))
+    return _timed_launches(stats, events, 'emp_fill_holes_labels', C.c_void_p(t.data_ptr()), eb, *dims3(shape), radius, int(ball), hole_size,
+                           _abi.ptr(d_labels), _abi.ptr(d_boxes), _abi.ptr(d_frames), len(turns), _abi.ptr(d_tiles), hp(offsets), len(levels),
+                           _abi.ptr(parent), _abi.ptr(size), stats['scratch_entries'], _abi.stream_ptr(device))
 
 
 _RAW_DTYPE = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}      # an element of that size, whatever it means
+
+
+def _elements(t, eb):
+    """the bytes of the buffer ``t`` as elements of their size ``abs(eb)``"""
+    return t.reshape(-1).view(torch.uint8).view(_RAW_DTYPE[abs(eb)])
 
 
 @torch.no_grad()
@@ -973,28 +860,22 @@ def _morph_call(labels, what, run, apply3d, plane, axis, device, out, inplace):
             raise ValueError(f'{what}: a 3-D array needs apply3d=True (the ball) or plane=k (the disk on one image)')
         if axis not in (0, 1, 2) or not 0 <= int(plane) < shape[axis]:
             raise ValueError(f'{what}: plane {plane} of axis {axis} is not in an array of shape {shape}')
-    eb = ebytes(labels.dtype)
+    ebytes(labels.dtype)      # a dtype that is not supported is refused here, before any work
     need_device()
     device = pick_device(device, labels)
     with torch.cuda.device(device):
         target = _edit_target(labels, out, inplace, shape, labels.dtype, what)
-        on_device = isinstance(labels, torch.Tensor)
-        if on_device:
-            res = labels if inplace else labels.contiguous().clone()
-            t = res
-        else:
-            host = np.ascontiguousarray(labels)
-            t = torch.from_numpy(host.view(np.uint8).reshape(-1)).to(device)
-        if len(shape) == 3 and not ball:
-            vol = t.reshape(-1).view(torch.uint8).view(_RAW_DTYPE[abs(eb)]).reshape(shape)
-            img = vol.select(axis, int(plane)).contiguous()
-            run(img, eb, tuple(img.shape), False, device)
-            vol.select(axis, int(plane)).copy_(img)
-        else:
-            run(t, eb, shape, ball, device)
-        if on_device:
-            return res
-        return _write_back(target, 0, shape[0], t.cpu(), host.dtype, shape)
+
+        def whole(t, eb):
+            if len(shape) == 3 and not ball:
+                vol = _elements(t, eb).reshape(shape)
+                img = vol.select(axis, int(plane)).contiguous()
+                run(img, eb, tuple(img.shape), False, device)
+                vol.select(axis, int(plane)).copy_(img)
+            else:
+                run(t, eb, shape, ball, device)
+            return t, None
+        return _whole_array(labels, target, device, not inplace, whole)[0]
 
 
 @torch.no_grad()
@@ -1034,237 +915,113 @@ def fill_label_holes(labels, hole_size=64, radius=1, apply3d=False, ids=None, pl
 # ----------------------------------------------------------------------------
 # Split Labels
 # ----------------------------------------------------------------------------
-SPLIT_MAX_DISTANCE = 100      # the widget's slider (_merge_split_widget.py:461)
-SPLIT_MAX_BOXES = 65535      # emp_split_*: boxes per launch
-SPLIT_MAX_ENTRIES = (1 << 31) - 2      # ... and their voxels
-SPLIT_MAX_DIAGONAL2 = 1 << 30      # nz^2 + ny^2 + nx^2 of a box stays below EMP_SPLIT_INF
+def _labels_under(t, eb, shape, points, device):
+    """the labels at ``points`` (n, ndim) of the device buffer ``t``, as int64 (labels lie below 2^63)"""
+    under = _elements(t, eb)[torch.from_numpy(np.ravel_multi_index(tuple(points.T), shape)).to(device)].cpu().numpy()
+    return (under.view(under.dtype.str.replace('i', 'u')) if eb > 0 else under).astype(np.int64)
 
 
-def split_spacing(coords, values, min_distance):
-    """``ensure_spacing`` of ``peak_local_max``, restated: the candidates ``coords`` (n, ndim) with their ``values`` by value
-    descending, stable over the order given (raster order); one is kept unless a kept one lies at Euclidean distance
-    < ``min_distance`` (strictly) -> the indices kept, in the order they were kept.  Recalled from skimage's source, not pinned."""
-    if len(values) == 0:
-        return np.zeros(0, np.int64)
-    coords = np.asarray(coords, dtype=np.int64).reshape(len(values), -1)
-    order = np.argsort(-np.asarray(values, dtype=np.int64), kind='stable')
-    kept = np.zeros((len(order), coords.shape[1]), np.int64)
-    idx, n, d2 = [], 0, int(min_distance) ** 2
-    for i in order.tolist():
-        if n and (((kept[:n] - coords[i]) ** 2).sum(axis=1) < d2).any():
-            continue
-        kept[n] = coords[i]
-        n += 1
-        idx.append(i)
-    return np.asarray(idx, dtype=np.int64)
+def _split_edt(t, eb, shape, boxes, N, device, events):
+    """emp_split_edt: the squared distance to the crop's background at the ``N`` voxels of ``boxes`` -> (the boxes on the device, d2)"""
+    d_boxes = torch.empty(8 * len(boxes), dtype=torch.int64, device=device)
+    d2 = torch.empty(N, dtype=torch.int32, device=device)
+    work = torch.empty(int(_abi.load().emp_split_edt_work_bytes(N)), dtype=torch.uint8, device=device)
+    _stage(events, 'edt', 'emp_split_edt', _abi.ptr(t), eb, *dims3(shape), hp(boxes), len(boxes), _abi.ptr(d_boxes), _abi.ptr(d2), N, _abi.ptr(work),
+           _abi.stream_ptr(device))
+    return d_boxes, d2
 
 
-def split_marker_ids(coords):
-    """``ndi.label(marker mask)[0]`` (connectivity 1, _merge_split_widget.py:446,454) at the voxels ``coords`` (n, ndim) without
-    the mask: voxels that are face neighbours share an id, and ids count the components in raster order of their first voxel
-    -> (ids (n,) int64 from 1, the number of components).  A voxel given twice is one voxel."""
-    coords = np.asarray(coords, dtype=np.int64)
-    if len(coords) == 0:
-        return np.zeros(0, np.int64), 0
-    where = {tuple(c): i for i, c in enumerate(coords.tolist())}
-    parent = list(range(len(coords)))
-
-    def find(i):
-        while parent[i] != i:
-            parent[i] = parent[parent[i]]
-            i = parent[i]
-        return i
-    for i, c in enumerate(coords.tolist()):
-        parent[i] = find(where[tuple(c)])      # a repeated voxel
-        for a in range(len(c)):
-            j = where.get(tuple(c[:a] + [c[a] - 1] + c[a + 1:]))
-            if j is not None:
-                ri, rj = find(i), find(j)
-                if ri != rj:
-                    parent[max(ri, rj)] = min(ri, rj)
-    ids, seen = np.zeros(len(coords), np.int64), {}
-    for i in np.lexsort(coords.T[::-1]).tolist():
-        ids[i] = seen.setdefault(find(i), len(seen) + 1)
-    return ids, len(seen)
+def _split_peaks(shape, boxes, d_boxes, d2, N, min_distance, device, events):
+    """emp_split_peaks: the candidates of ``peak_local_max`` -> (cand (total, 3) int64 {box, linear index, value}, box after box;
+    their number per box)"""
+    work = torch.empty(int(_abi.load().emp_split_peaks_work_bytes(N, len(boxes))), dtype=torch.uint8, device=device)
+    counts = torch.empty(len(boxes), dtype=torch.int32, device=device)
+    cap = max(4096, N // 64)
+    while True:
+        cand = torch.empty(3 * cap, dtype=torch.int32, device=device)
+        _stage(events, 'peaks', 'emp_split_peaks', hp(boxes), len(boxes), _abi.ptr(d_boxes), *dims3(shape), _abi.ptr(d2), N, min_distance,
+               _abi.ptr(cand), cap, _abi.ptr(counts), _abi.ptr(work), _abi.stream_ptr(device))
+        h_counts = counts.cpu().numpy().astype(np.int64)
+        total = int(h_counts.sum())
+        if total <= cap:
+            break
+        cap = total      # a ridge of equal distances: once more with room for all of them
+    return cand[:3 * total].cpu().numpy().reshape(-1, 3).astype(np.int64), h_counts
 
 
-def _split_batches(voxels):
-    """consecutive turns per launch: at most SPLIT_MAX_BOXES of them with at most SPLIT_MAX_ENTRIES voxels"""
-    batches, cur, n = [], [], 0
-    for i, v in enumerate(voxels):
-        if cur and (len(cur) == SPLIT_MAX_BOXES or n + v > SPLIT_MAX_ENTRIES):
-            batches.append(cur)
-            cur, n = [], 0
-        cur.append(i)
-        n += v
-    return batches + ([cur] if cur else [])
+def _split_flood(shape, boxes, d_boxes, d2, N, plateau, markers, device, events):
+    """emp_split_flood: per voxel of the boxes the marker whose basin it lies in -> (that, the number of sweeps); without markers
+    there is nothing to flood: (None, 0)"""
+    if len(markers) == 0:
+        return None, 0
+    new = torch.empty(N, dtype=torch.int32, device=device)
+    work = torch.empty(int(_abi.load().emp_split_flood_work_bytes(N, len(markers))), dtype=torch.uint8, device=device)
+    sweeps = C.c_int64(0)
+    _stage(events, 'flood', 'emp_split_flood', hp(boxes), len(boxes), _abi.ptr(d_boxes), *dims3(shape), _abi.ptr(d2), N, int(plateau), hp(markers),
+           len(markers), _abi.ptr(new), _abi.ptr(work), _abi.stream_ptr(device), C.byref(sweeps))
+    return new, int(sweeps.value)
+
+
+def _split_write(t, eb, shape, boxes, d_boxes, new, bases, device, events):
+    """emp_split_write: the label's voxels in every box with a base become base + marker"""
+    d_bases = torch.from_numpy(bases).to(device)
+    _stage(events, 'write', 'emp_split_write', _abi.ptr(t), eb, *dims3(shape), hp(boxes), len(boxes), _abi.ptr(d_boxes), _abi.ptr(new),
+           int(boxes[:, 3:6].prod(axis=1).sum()), _abi.ptr(d_bases), _abi.stream_ptr(device))
+
+
+def _split_pass(t, eb, shape, table, turns, points, under, min_distance, points_as_markers, start_label, device, stats, events):
+    """One group of turns on the buffer ``t`` whose table is ``table``: everything is computed, launch by launch, before
+    anything is written -> the report of these turns; ``stats`` is added to"""
+    report, todo = P.split_screen(table, turns, points_as_markers)
+    done = []      # per launch: (the turns, the boxes, their device copy, the markers of every voxel, the number of markers per box)
+    for batch in _split_batches(todo[:, 4:].prod(axis=1).tolist()):
+        boxes = P.split_boxes(turns, todo[batch])
+        N = int(boxes[:, 3:6].prod(axis=1).sum())
+        d_boxes, d2 = _split_edt(t, eb, shape, boxes, N, device, events)
+        if points_as_markers:
+            per_box = P.split_point_markers(points, under, boxes)
+        else:
+            cand, counts = _split_peaks(shape, boxes, d_boxes, d2, N, min_distance, device, events)
+            stats['candidates'] += len(cand)
+            per_box = P.split_peak_markers(cand, counts, boxes, min_distance)
+        markers, n_markers = P.split_marker_array(per_box, boxes)
+        new, sweeps = _split_flood(shape, boxes, d_boxes, d2, N, points_as_markers, markers, device, events)
+        del d2
+        for key, more in (('boxes', len(boxes)), ('entries', N), ('markers', int(n_markers.sum())), ('sweeps', sweeps)):
+            stats[key] += more
+        done.append((todo[batch, 0], boxes, d_boxes, new, n_markers))
+    cur_max = int(table.labels.max()) if len(table.labels) else 0
+    report, all_bases = P.split_ids(turns, report, [(mine, n_markers) for mine, _, _, _, n_markers in done], cur_max, start_label, eb)
+    for (_, boxes, d_boxes, new, _), bases in zip(done, all_bases):
+        if new is not None and (bases >= 0).any():
+            _split_write(t, eb, shape, boxes, d_boxes, new, bases, device, events)
+    return [(int(l), r) for l, r in zip(turns.tolist(), report)]
 
 
 def _split_device(t, eb, shape, points, ids, min_distance, points_as_markers, start_label, device, stages=None):
     """Split Labels in place on the contiguous device buffer ``t`` (an image, or a volume as a whole) -> (the report, statistics).
     ``stages``: a dict that receives the device time of every stage in ms (tools/split_labels_bench.py)."""
-    what = 'split_labels'
-    lib = _abi.load()
-    stream = _abi.stream_ptr(device)
-    nd = len(shape)
-    D, H, W = (1,) * (3 - nd) + tuple(shape)
-    table = _table_of_source(RawSource(t, eb, shape), shape, False, device, None, None)
-    raw = t.reshape(-1).view(torch.uint8).view(_RAW_DTYPE[abs(eb)])
-    if points is not None:
-        lin = np.ravel_multi_index(tuple(points.T), shape)
-        under = raw[torch.from_numpy(lin).to(device)].cpu().numpy()
-        under = (under.view(under.dtype.str.replace('i', 'u')) if eb > 0 else under).astype(np.int64)      # labels lie below 2^63
-        points, under = points[under != 0], under[under != 0]
-        turns = np.unique(under)
-    else:
-        turns = np.unique(np.asarray(ids, dtype=np.int64).reshape(-1))
-        turns = turns[turns > 0]
-    # Everything is computed before anything is written, which is the sequential loop as long as no turn writes an id that a
-    # later turn picks.  One can: a part of a label that no marker reaches becomes max_label itself (:544), the array's largest
-    # label, and when that label has a turn of its own -- the last one, the turns being sorted -- the loop lets it see those
-    # voxels.  So that turn runs as a second pass on the array as the others left it.
-    if len(turns) > 1 and len(table.labels) and turns[-1] == table.labels.max() and (start_label is None or int(start_label) - 1 == turns[-1]):
-        parts, before = [], t.clone()      # new ids that do not fit raise before their pass writes: then the first pass is undone
-        try:
-            for mine in (turns[:-1], turns[-1:]):
-                sub = dict(points=points[np.isin(under, mine)], ids=None) if points is not None else dict(points=None, ids=mine)
-                parts.append(_split_device(t, eb, shape, sub['points'], sub['ids'], min_distance, points_as_markers, start_label, device, stages))
-        except ValueError:
-            t.copy_(before)
-            raise
-        return parts[0][0] + parts[1][0], {k: parts[0][1][k] + parts[1][1][k] for k in parts[0][1]}
+    first = _table_of_source(RawSource(t, eb, shape), shape, False, device, None, None)
+    turns, points, under = P.split_turns(points, None if points is None else _labels_under(t, eb, shape, points, device), ids)
+    passes = P.split_passes(first, turns, start_label)
     stats = {'turns': int(len(turns)), 'boxes': 0, 'entries': 0, 'candidates': 0, 'markers': 0, 'sweeps': 0}
-    report = [None] * len(turns)
-    rows = np.full(len(turns), -1, np.int64)
-    if len(table.labels) and len(turns):
-        pos = np.minimum(np.searchsorted(table.labels, turns), len(table.labels) - 1)
-        rows = np.where(table.labels[pos] == turns, pos, -1)
-    todo = []      # (turn, box as 6 numbers); a label that fills its box has no background: nothing to split by distance
-    for i, row in enumerate(rows.tolist()):
-        if row < 0:
-            report[i] = 'label absent'
-            continue
-        lo = np.concatenate([np.zeros(3 - nd, np.int64), table.boxes[row, :nd]])
-        n3 = np.concatenate([np.ones(3 - nd, np.int64), table.boxes[row, nd:] - table.boxes[row, :nd]])
-        if not points_as_markers and int(n3.prod()) == int(table.areas[row]):
-            report[i] = 'nothing to split'
-            continue
-        if int((n3 ** 2).sum()) >= SPLIT_MAX_DIAGONAL2 or int(n3.prod()) > SPLIT_MAX_ENTRIES:
-            raise ValueError(f'{what}: the box of label {int(turns[i])}, {tuple(n3[3 - nd:].tolist())}, is too large: the squares of its '
-                             'sides must add up to less than 2^30 and it must hold fewer than 2^31 - 1 voxels')
-        todo.append((i, lo, n3))
-    events = []
-
-    def stage(name, call):
-        if stages is None:
-            return call()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        res = call()
-        b.record()
-        events.append((name, a, b))
-        return res
-
-    done = []      # per launch: (the turns, the boxes, their device copy, the markers of every voxel, the number of markers per box)
-    for batch in _split_batches([int(n3.prod()) for _, _, n3 in todo]):
-        n = len(batch)
-        boxes = np.zeros((n, 8), np.int64)
-        for k, j in enumerate(batch):
-            boxes[k, :3], boxes[k, 3:6], boxes[k, 7] = todo[j][1], todo[j][2], turns[todo[j][0]]
-        vox = boxes[:, 3:6].prod(axis=1)
-        boxes[:, 6] = np.cumsum(vox) - vox
-        N = int(vox.sum())
-        stats['boxes'] += n
-        stats['entries'] += N
-        d_boxes = torch.empty(8 * n, dtype=torch.int64, device=device)
-        d2 = torch.empty(N, dtype=torch.int32, device=device)
-        work = torch.empty(int(lib.emp_split_edt_work_bytes(N)), dtype=torch.uint8, device=device)
-        stage('edt', lambda: _abi.check(lib.emp_split_edt(_abi.ptr(t), eb, D, H, W, hp(boxes), n, _abi.ptr(d_boxes), _abi.ptr(d2), N,
-                                                           _abi.ptr(work), stream), 'emp_split_edt'))
-        del work
-        per_box = [np.zeros((0, 3), np.int64)] * n      # the marker voxels of a box, as (z, y, x) in the box
-        if points_as_markers:
-            for k, j in enumerate(batch):
-                mine = points[under == turns[todo[j][0]]]
-                mine = np.concatenate([np.zeros((len(mine), 3 - nd), np.int64), mine], axis=1) - boxes[k, :3]
-                per_box[k] = np.unique(mine, axis=0)
-        else:
-            work = torch.empty(int(lib.emp_split_peaks_work_bytes(N, n)), dtype=torch.uint8, device=device)
-            counts = torch.empty(n, dtype=torch.int32, device=device)
-            cap = max(4096, N // 64)
-            while True:
-                cand = torch.empty(3 * cap, dtype=torch.int32, device=device)
-                stage('peaks', lambda: _abi.check(lib.emp_split_peaks(hp(boxes), n, _abi.ptr(d_boxes), D, H, W, _abi.ptr(d2), N, min_distance,
-                                                                      _abi.ptr(cand), cap, _abi.ptr(counts), _abi.ptr(work), stream),
-                                                  'emp_split_peaks'))
-                h_counts = counts.cpu().numpy().astype(np.int64)
-                total = int(h_counts.sum())
-                if total <= cap:
-                    break
-                cap = total      # a ridge of equal distances: once more with room for all of them
-            del work
-            stats['candidates'] += total
-            cand = cand[:3 * total].cpu().numpy().reshape(-1, 3).astype(np.int64)
-            ends = np.cumsum(h_counts)
-            for k in range(n):
-                mine = cand[ends[k] - h_counts[k]:ends[k]]
-                coords = np.stack(np.unravel_index(mine[:, 1], tuple(boxes[k, 3:6])), axis=1).reshape(-1, 3)
-                per_box[k] = coords[split_spacing(coords, mine[:, 2], min_distance)]
-        markers, n_markers = [], np.zeros(n, np.int64)
-        for k in range(n):
-            mids, n_markers[k] = split_marker_ids(per_box[k])
-            if n_markers[k] >= 2:      # fewer: nothing to split, and nothing to flood
-                lin = np.ravel_multi_index(tuple(per_box[k].T), tuple(boxes[k, 3:6]))
-                markers.append(np.stack([np.full(len(lin), k, np.int64), lin, mids], axis=1))
-        if n_markers.max() > 0x3fffffff:
-            raise ValueError(f'{what}: more than 2^30 - 1 markers in one label')
-        markers = np.ascontiguousarray(np.concatenate(markers).astype(np.int32)) if markers else np.zeros((0, 3), np.int32)
-        stats['markers'] += int(n_markers.sum())
-        new = None
-        if len(markers):
-            new = torch.empty(N, dtype=torch.int32, device=device)
-            work = torch.empty(int(lib.emp_split_flood_work_bytes(N, len(markers))), dtype=torch.uint8, device=device)
-            sweeps = C.c_int64(0)
-            stage('flood', lambda: _abi.check(lib.emp_split_flood(hp(boxes), n, _abi.ptr(d_boxes), D, H, W, _abi.ptr(d2), N,
-                                                                  int(points_as_markers), hp(markers), len(markers), _abi.ptr(new),
-                                                                  _abi.ptr(work), stream, C.byref(sweeps)), 'emp_split_flood'))
-            stats['sweeps'] += int(sweeps.value)
-            del work
-        del d2
-        done.append(([todo[j][0] for j in batch], boxes, d_boxes, new, n_markers))
-    # the ids, turn by turn as the loop would hand them out (:533-545); nothing is written before all of them are known
-    top = min((1 << (8 * abs(eb) - (1 if eb < 0 else 0))) - 1, (1 << 63) - 1)
-    cur_max = int(table.labels.max()) if len(table.labels) else 0
-    all_bases = []
-    for which, boxes, d_boxes, new, n_markers in done:
-        bases = np.full(len(which), -1, np.int64)
-        all_bases.append(bases)
-        for k, i in enumerate(which):
-            if n_markers[k] < 2:
-                report[i] = 'nothing to split'
-                continue
-            max_label = cur_max if start_label is None else int(start_label) - 1
-            if cur_max >= max_label + 1:
-                report[i] = 'ids in use'
-                continue
-            if max_label + int(n_markers[k]) > top:
-                raise ValueError(f'{what}: the new ids of label {int(turns[i])}, up to {max_label + int(n_markers[k])}, do not fit the '
-                                 f'array\'s {abs(eb)}-byte {"signed" if eb < 0 else "unsigned"} type; nothing was written')
-            bases[k] = max_label
-            cur_max = max_label + int(n_markers[k])
-            report[i] = max_label + np.arange(1, int(n_markers[k]) + 1, dtype=np.int64)
-    for (which, boxes, d_boxes, new, _), bases in zip(done, all_bases):
-        if new is None or (bases < 0).all():
-            continue
-        d_bases = torch.from_numpy(bases).to(device)
-        stage('write', lambda: _abi.check(lib.emp_split_write(_abi.ptr(t), eb, D, H, W, hp(boxes), len(boxes), _abi.ptr(d_boxes), _abi.ptr(new),
-                                                              int(boxes[:, 3:6].prod(axis=1).sum()), _abi.ptr(d_bases), stream),
-                                          'emp_split_write'))
+    events = None if stages is None else []
+    # two passes: each has the table of the array as it is then, and new ids that do not fit raise before their pass writes: then
+    # the first pass is undone
+    report, before = [], (t.clone() if len(passes) > 1 else None)
+    try:
+        for mine in passes:
+            table = first if before is None else _table_of_source(RawSource(t, eb, shape), shape, False, device, None, None)
+            report += _split_pass(t, eb, shape, table, mine, points, under, min_distance, points_as_markers, start_label, device, stats, events)
+    except ValueError:
+        if before is not None:
+            t.copy_(before)
+        raise
     if stages is not None:
         torch.cuda.synchronize(device)
         for name, a, b in events:
             stages[name] = stages.get(name, 0.0) + a.elapsed_time(b)
-    return [(int(l), r) for l, r in zip(turns.tolist(), report)], stats
+    return report, stats
 
 
 @torch.no_grad()

@@ -513,6 +513,36 @@ def test_return_kinds_arguments_and_reproducibility():
         L.split_labels(Store(), ids=ids)
 
 
+def test_the_statistics_of_the_device_loops():
+    """What only the callers of ``_split_device``, ``_morph_device`` and ``_fill_device`` see, the statistics, on shapes of a few
+    thousand voxels: the values are those recorded before the planning moved to _labelplan.py (the flood's sweeps are
+    reproducible: every sweep reads one buffer and writes the other)."""
+    import torch
+    import fill_holes_case as FC
+    import morph_case as MC
+    from empanada_napari_amd import labels as L
+    dev = torch.device('cuda', 0)
+    for name, want in (('image_d3', {'turns': 4, 'boxes': 4, 'entries': 4357, 'candidates': 22, 'markers': 12, 'sweeps': 39}),
+                       ('volume_d2', {'turns': 3, 'boxes': 3, 'entries': 2265, 'candidates': 6, 'markers': 5, 'sweeps': 9})):
+        arr, d = _case(name)
+        t = _dev(np.array(arr))
+        report, stats = L._split_device(t, -4, arr.shape, None, np.unique(arr)[1:], d, False, None, dev)
+        assert stats == want
+        _same_report(report, _want_distance(name)[1])
+        assert np.array_equal(t.cpu().numpy(), _want_distance(name)[0])
+    arr, d = _case('image_d3')
+    stats = L._split_device(_dev(np.array(arr)), -4, arr.shape, SC.case_points(arr, 3, 1), None, d, True, None, dev)[1]
+    assert stats == {'turns': 4, 'boxes': 4, 'entries': 4357, 'candidates': 0, 'markers': 12, 'sweeps': 53}
+    for shape, close, erode, fill in (((40, 50), (5, 12, 14), (1, 12, 2), {'turns': 15, 'levels': 6, 'tiles': 15, 'launches': 29, 'scratch_entries': 701}),
+                                      ((12, 30, 34), (9, 21, 26), (1, 21, 2), {'turns': 16, 'levels': 11, 'tiles': 25, 'launches': 54, 'scratch_entries': 3240})):
+        blobs = MC.blobs(shape, 12, 3)
+        for op, (levels, tiles, launches) in (('Close', close), ('Erode', erode)):
+            stats = L._morph_device(_dev(blobs.copy()), -4, shape, op, 2, len(shape) == 3, None, dev)
+            assert stats == {'turns': 12, 'turns_scheduled': 12, 'levels': levels, 'tiles': tiles, 'launches': launches}
+        stats = L._fill_device(_dev(FC.holes(shape, 12, 3)), -4, shape, 2, 64, len(shape) == 3, None, dev)
+        assert stats == {**fill, 'turns_scheduled': fill['turns']}
+
+
 def test_clean_labels_tool_split_mode(tmp_path, capsys):
     import importlib.util
     import json
