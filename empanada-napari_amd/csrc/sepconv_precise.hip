@@ -16,8 +16,16 @@
 //     as hi + lo pairs too 7.28e-4
 // so the kernel keeps
 //   * the depthwise taps in fp32 (they only ever meet the fp32 vector pipe: free), and
-//   * the depthwise output as an fp16 hi tile + an fp16 lo tile in LDS (hi = rtz(x), lo = rtz(x - hi): 21 significant
-//     bits; split ONCE by the depthwise wave that produced it -- a first build that stored fp32 and let each of the four
+//   * the depthwise output as an fp16 hi tile + an fp16 lo tile in LDS (hi = rtz(x), lo = rtz(x - hi).  Both conversions
+//     truncate, so hi + lo is short of x, on x's side of zero, by less than 2^-21 2^floor(log2 |x|) -- 22 significant bits, one
+//     more than the "21" the what-if above was named after -- for 2^-3 <= |x|; below 2^-3 lo is an fp16 subnormal and the
+//     pair is short by up to an absolute 2^-24, i.e. from |x| = 2^-13 down it is no better than one fp16, and below 2^-24 it is
+//     zero.  Subnormal halves are read as their values by the MFMA.  Overflow, measured on gfx950 (FINDINGS 102):
+//     v_cvt_pkrtz_f16_f32 follows IEEE's round-toward-zero rule, hi = +-65504 from 65520 on and NOT +-inf, and lo carries
+//     the rest: a depthwise value up to 131008 = 65504 + 65504 is held to within lo's own step (at most 32) and nothing turns
+//     into inf - inf = NaN as in the fp16x3 kernels' round-to-nearest split (FINDINGS 99); beyond 131008 the value would be
+//     clamped silently -- unreachable from fp16 activations unless the taps of a channel sum to more than 2 in magnitude.
+//     Split ONCE by the depthwise wave that produced it -- a first build that stored fp32 and let each of the four
 //     mma waves split its own B fragments spent 4x the conversions and ran at half the speed), multiplied as
 //     w*hi + w*lo: two MFMAs per product,
 // and leaves the pointwise weights in fp16: their hi + lo form (a third MFMA per product, twice the weight traffic, 32

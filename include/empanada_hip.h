@@ -407,7 +407,10 @@ EMP_API int emp_sepconv3x3_nhwc_f16(const void* d_in, int N, int H, int W, int C
  * distance to the fp32 reference forward (models/quantization/panoptic_deeplab.py:238-250 run in fp32).  Here the taps
  * stay fp32 on the vector pipe and the depthwise result goes to the matrix pipe as an fp16 hi + lo pair (two MFMAs per
  * product, fp32 accumulation); the pointwise weights stay fp16 (their hi + lo form bought 0.5 % of the error for a third
- * more matrix work: measured, removed).  x and y are fp16.
+ * more matrix work: measured, removed).  x and y are fp16.  Operand range: both halves are round-toward-zero conversions, so the
+ * pair is short of the depthwise value d by less than 2^-21 2^floor(log2 |d|) for |d| >= 2^-3, by less than an absolute 2^-24
+ * below (lo is an fp16 subnormal, kept; from 2^-13 down the pair is no better than one fp16), and zero below 2^-24; from 65520 on
+ * hi is +-65504, not inf, and lo carries the rest up to |d| = 131008 (gfx950's v_cvt_pkrtz_f16_f32, measured: FINDINGS 102).
  *   K       : depthwise kernel size, 5 or 3 (3: no head mode)
  *   d_dw_w  : the (K*K, C) fp32 taps re-ordered by emp_sepconvp_pack_dw (chunk-major [C/64][K*K][64] fp32)
  *   d_pw_w  : the (Cout, C) fp32 pointwise weights (row stride pw_ld) rounded to fp16 and re-ordered by

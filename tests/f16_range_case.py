@@ -350,8 +350,9 @@ def _gemm_bound(X, Wm, ex=None, ex2=None):
 
 
 @np.errstate(invalid='ignore', over='ignore')      # (inf - inf of the bounds next to an infinite reference value)
-def _epilogue(t, worst, rss, A, adds, act, to16, head=None):
-    """adds: the (M, Cout) float64 operands of the fp32 additions, in the kernels' order -> dict(ref, worst, rss, store16)"""
+def _epilogue(t, worst, rss, A, adds, act, to16, head=None, wave_couts=HEAD_WAVE_COUTS):
+    """adds: the (M, Cout) float64 operands of the fp32 additions, in the kernels' order -> dict(ref, worst, rss, store16).
+    wave_couts: couts per mma wave of the kernel whose head this is (sepp_range_case passes sepconv_precise.hip's)"""
     for v in adds:
         t, A = t + v, A + np.abs(v)
     ep = len(adds) * U * (A + worst)
@@ -373,7 +374,7 @@ def _epilogue(t, worst, rss, A, adds, act, to16, head=None):
         worst = worst @ np.abs(hw).T + n * U * Ah
         # head_store starts from the head bias and adds the mma waves' shares (HEAD_WAVE_COUTS couts each) one by one: that many
         # roundings of a partial sum bounded by |hb| + |y| . |hw|, not one (the x3 module's form, `+ U |hb|`, has one)
-        nw = out.shape[1] // HEAD_WAVE_COUTS
+        nw = out.shape[1] // wave_couts
         rss = (np.sqrt((rss ** 2) @ (hw ** 2).T + n * U * U * ((out ** 2) @ (hw ** 2).T))
                + math.sqrt(nw) * U * (np.abs(hb)[None] + np.abs(out) @ np.abs(hw).T))
         out = out @ hw.T + hb[None]
