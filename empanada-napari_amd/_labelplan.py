@@ -1,6 +1,6 @@
-"""The host planning of Morph Labels, Fill holes and Split Labels: pure numpy, no device, no library.
+"""The host planning of Morph Labels, Fill holes, Split Labels and the slab-by-slab components: pure numpy, no device, no library.
 
-``labels.py`` holds the device drivers of the three tools; what they decide on the host before and between the launches lives
+``labels.py`` holds the device drivers of these tools; what they decide on the host before and between the launches lives
 here, as functions over plain arrays and a ``LabelTable`` (anything with its ``labels``, ``areas``, ``boxes``, ``shape``):
 
 * Morph Labels / Fill holes: the footprints, the turns with their boxes (``_morph_turns``), the levels (``morph_schedule``), the
@@ -8,7 +8,10 @@ here, as functions over plain arrays and a ``LabelTable`` (anything with its ``l
 * Split Labels: the turns (``split_turns``), the rule that gives the largest label a pass of its own (``split_passes``), the
   screening of the boxes (``split_screen``), the boxes of a launch (``_split_batches``, ``split_boxes``), the markers of every box
   (``split_point_markers`` / ``split_peak_markers`` with ``split_spacing``, then ``split_marker_array`` with ``split_marker_ids``)
-  and the ids the reference's loop hands out turn by turn (``split_ids``).
+  and the ids the reference's loop hands out turn by turn (``split_ids``);
+* connected components slab by slab (``labels.label_components``): how an array is cut (``components_geometry``,
+  ``components_slab`` with the cap of the default slab) and what is refused, with the texts (``components_check_labels``,
+  ``components_check_count``).
 
 This module imports numpy only, so all of it is tested without a device (tests/test_labelplan_host.py)."""
 import numpy as np
@@ -25,6 +28,11 @@ SPLIT_MAX_BOXES = 65535      # emp_split_*: boxes per launch
 SPLIT_MAX_ENTRIES = (1 << 31) - 2      # ... and their voxels
 SPLIT_MAX_DIAGONAL2 = 1 << 30      # nz^2 + ny^2 + nx^2 of a box stays below EMP_SPLIT_INF
 SPLIT_MAX_MARKERS = 0x3fffffff      # emp_split_flood: a marker's id in a label
+
+COMPONENTS_MAX_LABEL = (1 << 31) - 2      # emp_ccl_range: labels below 2^31 - 1
+COMPONENTS_MAX_SLAB_VOXELS = 1 << 30      # emp_ccl_range: depth * H * W < 2^30, so one slice and an explicit slab must stay below
+COMPONENTS_SLAB_VOXELS = 1 << 28      # the default slab holds at most this many
+COMPONENTS_MAX_COUNT = (1 << 31) - 2      # int32 ids 1..count; also the provisional per-slab ids of emp_ccl_seam's parent array
 
 
 # ----------------------------------------------------------------------------
@@ -48,6 +56,49 @@ def table_rows(table, ids):
         return np.full(len(ids), -1, np.int64)
     pos = np.minimum(np.searchsorted(table.labels, ids), len(table.labels) - 1)
     return np.where((ids > 0) & (table.labels[pos] == ids), pos, -1)
+
+
+# ----------------------------------------------------------------------------
+# connected components, slab by slab
+# ----------------------------------------------------------------------------
+def components_geometry(shape, what='label_components'):
+    """(rows, H, W) of a 2-D or 3-D array as the slab stream cuts it: a volume by slices, an image (R, W) by rows, as R slices of
+    one row (the kernels' (z, y, x) = the image's (row, 0, column)).  One slice must be one the CCL can take."""
+    shape = tuple(int(s) for s in shape)
+    if len(shape) not in (2, 3):
+        raise ValueError(f'{what}: 2-D or 3-D label arrays, got shape {shape}')
+    rows, H, W = (shape[0], 1, shape[1]) if len(shape) == 2 else shape
+    if H * W >= COMPONENTS_MAX_SLAB_VOXELS:
+        raise ValueError(f'{what}: one slice of the array, {H} x {W}, holds 2^30 voxels or more; the components of a slab need fewer')
+    return rows, H, W
+
+
+def components_slab(rows, slice_voxels, slab, planned, what='label_components'):
+    """The slices per slab.  ``slab=None``: ``planned``, the slab stream's own choice (everything for a device tensor, about 64 MiB
+    of a host source), capped so that a slab holds at most 2^28 voxels -- about 4 GiB of CCL work memory at 16 bytes per voxel --
+    and never below one slice.  An explicit ``slab`` is taken as given (at most all rows) and refused, from the shape alone, when
+    its slab would hold 2^30 voxels or more."""
+    if slab is None:
+        return max(1, min(int(planned), COMPONENTS_SLAB_VOXELS // max(1, slice_voxels)))
+    if isinstance(slab, bool) or int(slab) != slab or int(slab) < 1:
+        raise ValueError(f'{what}: slab must be a positive number of slices, got {slab!r}')
+    slab = min(int(slab), max(rows, 1))
+    if slab * slice_voxels >= COMPONENTS_MAX_SLAB_VOXELS:
+        raise ValueError(f'{what}: a slab of {slab} slices of {slice_voxels} voxels holds 2^30 voxels or more; pass a smaller slab= '
+                         '(or none: the default slab holds at most 2^28)')
+    return slab
+
+
+def components_check_labels(top, what='label_components'):
+    """the largest label of the array against what emp_ccl_range reads as a label"""
+    if int(top) > COMPONENTS_MAX_LABEL:
+        raise ValueError(f'{what}: the connected components need labels below 2^31 - 1, the array holds {int(top)}')
+
+
+def components_check_count(n, what='label_components'):
+    """``n``: the components of all slabs so far, each a provisional id of the int32 union-find over them"""
+    if int(n) > COMPONENTS_MAX_COUNT:
+        raise ValueError(f'{what}: more than 2^31 - 2 components ({int(n)} over the slabs so far); nothing was written')
 
 
 # ----------------------------------------------------------------------------

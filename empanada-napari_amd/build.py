@@ -25,7 +25,7 @@ PER_FILE = {
     'pdl_net32.hip': ['-std=c++20'],
 }
 SOURCES = ['abi.hip', 'conv_igemm.hip', 'layers.hip', 'pointrend.hip', 'postprocess.hip', 'pdl_net.hip', 'pdl_net32.hip', 'sparse.hip',
-           'sepconv.hip', 'sepconv_precise.hip', 'conv_igemm256.hip', 'conv_igemm_s64.hip', 'conv3x3c64.hip', 'stem.hip', 'matcher.hip', 'ref32.hip', 'conv16x3.hip', 'conv_igemm_grouped.hip', 'conv16x3p.hip', 'sepconv_x3.hip', 'overlap.hip', 'labels.hip', 'measure.hip', 'morph.hip', 'split.hip']
+           'sepconv.hip', 'sepconv_precise.hip', 'conv_igemm256.hip', 'conv_igemm_s64.hip', 'conv3x3c64.hip', 'stem.hip', 'matcher.hip', 'ref32.hip', 'conv16x3.hip', 'conv_igemm_grouped.hip', 'conv16x3p.hip', 'sepconv_x3.hip', 'overlap.hip', 'labels.hip', 'measure.hip', 'morph.hip', 'split.hip', 'components.hip']
 # sources that #include another source: rebuilt when that one changes
 INCLUDES = {'conv_igemm_grouped.hip': ['conv_igemm.hip']}
 

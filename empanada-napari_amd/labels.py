@@ -45,6 +45,10 @@ The one deliberate difference: on an image without labels the reference's ``filt
 first and second moments of its voxel coordinates and its exposed voxel faces per axis, all integers; ``LabelMeasures`` derives
 centroids, volumes, face surfaces, covariances and principal axes from them as pure numpy.
 
+``label_components`` (csrc/components.hip) splits a label array of any size into its connected components, slab by slab: per slab
+``emp_ccl_range``, across the seams a union-find over the slabs' component ids, then one numbering in raster order.
+``remove_boundary_labels(streamed=True)`` is the reference mode on top of it, for arrays the one-call CCL cannot take.
+
 There is no numpy fallback: without the HIP library or a device the device entries raise like every other entry of the package.
 """
 import ctypes as C
@@ -61,7 +65,7 @@ from ._labelstream import GrowableTable, RawSource, ebytes, hp, initial_capacity
 
 __all__ = ['LabelTable', 'label_table', 'table_from_arrays', 'LabelMeasures', 'measure_labels', 'measures_from_arrays', 'small_labels', 'boundary_labels', 'count_labels', 'class_label_lists',
            'next_available_labels', 'next_available_label', 'label_bbox', 'delete_labels', 'merge_labels',
-           'filter_out_small_label_areas', 'remove_boundary_labels', 'morph_labels', 'fill_label_holes', 'morph_schedule',
+           'filter_out_small_label_areas', 'remove_boundary_labels', 'label_components', 'morph_labels', 'fill_label_holes', 'morph_schedule',
            'morph_footprint_rows', 'morph_footprint_offsets', 'split_labels', 'split_spacing', 'split_marker_ids']
 
 CCL_MAX_VOXELS = 1 << 30      # emp_ccl_range: D * H * W < 2^30
@@ -630,7 +634,8 @@ def _vanished(before, after):
 
 
 @torch.no_grad()
-def remove_boundary_labels(labels, whole_labels=False, per_slice=False, device=None, out=None, inplace=False, slab=None):
+def remove_boundary_labels(labels, whole_labels=False, per_slice=False, device=None, out=None, inplace=False, slab=None, streamed=False,
+                           components=None):
     """_filter_small_labels.py:43-60 -> (labels, number of labels removed).
 
     ``whole_labels=False`` reproduces the reference's ``clear_border``: the array is split into connected components (full
@@ -640,7 +645,13 @@ def remove_boundary_labels(labels, whole_labels=False, per_slice=False, device=N
     2^31 - 1 (int32 / int64 input; narrower types are converted on the device).  Outside those limits a ``ValueError`` names
     the alternative: ``whole_labels=True`` removes every voxel of a label whose box touches a face, needs the table only and
     works slab by slab on arrays of any size.  ``per_slice``: every image of a 3-D stack on its own; the number is then the
-    total over the images."""
+    total over the images.
+
+    ``streamed=True`` runs the reference mode slab by slab, on device tensors, numpy arrays and chunked stores of any size (one
+    image or one volume: not ``per_slice``): the components come from ``label_components`` into ``components=`` -- an int32 array
+    or store of the caller's, of the labels' shape; by default a new numpy array --, their boxes from ``label_table`` on them, and
+    the edit is one pass over labels and components together.  Its limits are ``label_components``'s: labels below 2^31 - 1 and
+    one slice (or an explicit ``slab``) of fewer than 2^30 voxels."""
     need_device()
     device = pick_device(device, labels)
     what = 'remove_boundary_labels'
@@ -650,11 +661,14 @@ def remove_boundary_labels(labels, whole_labels=False, per_slice=False, device=N
             ids = boundary_labels(table)
             res = _apply(labels, _map_keys(ids, per_slice), np.zeros(len(ids), np.int64), per_slice, device, out, inplace, slab, what)
             return res, len(ids)
+        if streamed:
+            return _clear_border_streamed(labels, per_slice, device, out, inplace, slab, components, what)
         shape = tuple(int(s) for s in labels.shape)
         _geometry(shape, per_slice, what)
         if int(np.prod(shape, dtype=np.int64)) >= CCL_MAX_VOXELS:
             raise ValueError(f'{what}: the connected components of the reference mode need fewer than 2^30 voxels, the array has '
-                             f'{shape}; use whole_labels=True (removes whole labels by their boxes, slab by slab)')
+                             f'{shape}; use whole_labels=True (removes whole labels by their boxes, slab by slab) or streamed=True '
+                             '(the same components, slab by slab)')
         # what the call cannot do is said before any work: nothing is written, on the device or to the caller's array, by then
         target = _edit_target(labels, out, inplace, shape, labels.dtype, what)
         edit_own = bool(inplace) and isinstance(labels, torch.Tensor)      # the result replaces the caller's tensor
@@ -717,6 +731,219 @@ def _as_ccl_input(t, eb, shape):
     if abs(eb) == 2:
         return raw.view(torch.int16).to(torch.int32) & 0xffff if eb > 0 else raw.view(torch.int16).to(torch.int32)
     return (raw if eb > 0 else raw.view(torch.int8)).to(torch.int32)
+
+
+# ----------------------------------------------------------------------------
+# connected components, slab by slab
+# ----------------------------------------------------------------------------
+COMPONENTS_CAPACITY = 1 << 16      # first size of the union-find over the slabs' components (entries; it doubles)
+
+
+def _components_target(src, out, device, what):
+    """Where the components go, every check of ``out`` included: ('device', tensor or None) or ('host', array / store or None).
+    None: a new device tensor for a device source, a new numpy array otherwise."""
+    if out is None:
+        return ('host' if src.is_host else 'device'), None
+    if isinstance(out, torch.Tensor):
+        if not out.is_cuda:
+            raise TypeError(f'{what}: a torch tensor given as out= must be on the device (pass host memory as a numpy array)')
+        if out.device != device:
+            raise ValueError(f'{what}: out= on {out.device}, the work on {device}')
+        if tuple(out.shape) != src.shape or out.dtype != torch.int32:
+            raise ValueError(f'{what}: out= must be int32 and have the shape of the labels')
+        if not out.is_contiguous():
+            raise ValueError(f'{what}: out= needs a contiguous tensor')
+        return 'device', out
+    if not (hasattr(out, 'shape') and hasattr(out, 'dtype') and hasattr(out, '__setitem__')):
+        raise TypeError(f'{what}: out= is an int32 device tensor, numpy array or chunked store')
+    if tuple(out.shape) != src.shape or np.dtype(out.dtype) != np.dtype(np.int32):
+        raise ValueError(f'{what}: out= must be int32 and have the shape of the labels')
+    return 'host', out
+
+
+def _slab_bytes(src, k, z0, z1):
+    """slab k = rows [z0, z1) of a source as the device bytes the stream handed out"""
+    if src.is_host:
+        return src.dev[k & 1][:(z1 - z0) * src.row_bytes]
+    return src.t.reshape(-1).view(torch.uint8)[z0 * src.row_bytes:z1 * src.row_bytes]
+
+
+def _components_of_source(src, out, slab, device, capacity, table, stats, what):
+    rows, H, W = P.components_geometry(src.shape, what)
+    HW = H * W
+    slab = P.components_slab(rows, HW, slab, slab_plan(rows, src.row_bytes if src.is_host else None, None)[0], what)
+    kind, target = _components_target(src, out, device, what)
+    if rows * HW == 0:
+        res = target if target is not None else (torch.zeros(src.shape, dtype=torch.int32, device=device) if kind == 'device'
+                                                 else np.zeros(src.shape, np.int32))
+        return res, 0
+    # the largest label, off the table as _clear_border reads it; the table's pass also refuses what is no label at all
+    if table is None:
+        table = _table_of_source(src, src.shape, False, device, slab, None)
+    P.components_check_labels(table.labels.max() if len(table.labels) else 0, what)
+
+    lib = _abi.load()
+    stream = torch.cuda.current_stream(device)
+    ids = torch.empty(slab * HW, dtype=torch.int32, device=device)
+    num = torch.empty(1, dtype=torch.int32, device=device)
+    work = torch.empty(int(lib.emp_ccl8_work_bytes(1, slab * H, W)), dtype=torch.uint8, device=device)
+    st = {'slabs': 0, 'ccl_runs': 0, 'doublings': 0, 'provisional': 0}
+
+    def ccl(k, z0, z1):
+        """the slab's local ids in ``ids`` -> the labels as the kernel read them"""
+        wide = _as_ccl_input(_slab_bytes(src, k, z0, z1), src.ebytes, None)
+        _abi.check(lib.emp_ccl_range(_abi.ptr(wide), 8 if wide.dtype == torch.int64 else 4, 1, z1 - z0, H, W, 1, CCL_MAX_LABEL + 1,
+                                     _abi.ptr(ids), _abi.ptr(num), _abi.ptr(work), _abi.stream_ptr(device)), 'emp_ccl_range')
+        st['ccl_runs'] += 1
+        return wide
+
+    # pass 1: per slab its components, as provisional ids base + local id, and the unions across the seam to the slab before
+    parent = torch.zeros(max(2, int(capacity)), dtype=torch.int32, device=device)
+    bases, G = [], 0
+    prev_vals = prev_ids = None
+    for k, z0, z1, _ in stream_slabs([src], slab, device):
+        wide = ccl(k, z0, z1)
+        K = int(num.item())      # synchronises
+        P.components_check_count(G + K, what)
+        if G + K + 1 > len(parent):
+            cap = len(parent)
+            while cap < G + K + 1:
+                cap *= 2
+                st['doublings'] += 1
+            grown = torch.zeros(min(cap, P.COMPONENTS_MAX_COUNT + 1), dtype=torch.int32, device=device)
+            grown[:G + 1] = parent[:G + 1]
+            parent = grown
+        if K:
+            parent[G + 1:G + K + 1] = torch.arange(G + 1, G + K + 1, dtype=torch.int32, device=device)
+        if k > 0:
+            _abi.check(lib.emp_ccl_seam(_abi.ptr(prev_vals), _abi.ptr(prev_ids), _abi.ptr(wide), _abi.ptr(ids), wide.element_size(), H, W,
+                                        bases[-1], G, _abi.ptr(parent), len(parent), _abi.stream_ptr(device)), 'emp_ccl_seam')
+        bases.append(G)
+        G += K
+        if z1 < rows:
+            # the last slice, values and ids, for the next seam: `ids` is written again by then, and a host source's staging
+            # slot is refilled while the next slab runs -- wait for the copies, or that refill could overtake them
+            n = (z1 - z0) * HW
+            prev_vals, prev_ids = wide[n - HW:n].clone(), ids[n - HW:n].clone()
+            if src.is_host:
+                stream.synchronize()
+        del wide
+    st['slabs'], st['provisional'] = len(bases), G
+
+    # the final numbers: the roots ranked in id order, which is raster order of the components' first voxels
+    single = len(bases) == 1
+    if single:
+        count = G      # no seam: the slab's own numbering is the result
+    else:
+        lut = torch.empty(G + 1, dtype=torch.int32, device=device)
+        rwork = torch.empty(int(lib.emp_ccl_rank_roots_work_bytes(G)), dtype=torch.uint8, device=device)
+        _abi.check(lib.emp_ccl_rank_roots(_abi.ptr(parent), G, _abi.ptr(lut), _abi.ptr(num), _abi.ptr(rwork), _abi.stream_ptr(device)),
+                   'emp_ccl_rank_roots')
+        count = int(num.item())
+        del rwork
+    del parent
+    if stats is not None:
+        stats.update(st, count=count)
+
+    # pass 2: nothing has been written so far
+    if kind == 'device':
+        if single:
+            res = ids.reshape(src.shape)
+            if target is not None:
+                target.copy_(res)
+            return (res if target is None else target), count
+        res = target if target is not None else torch.empty(src.shape, dtype=torch.int32, device=device)
+        flat = res.reshape(-1)
+    else:
+        res = target if target is not None else np.empty(src.shape, np.int32)
+        back = torch.empty(slab * HW, dtype=torch.int32).pin_memory()
+
+    def download(z0, z1):
+        n = (z1 - z0) * HW
+        back[:n].copy_(ids[:n], non_blocking=True)
+        stream.synchronize()
+        res[z0:z1] = back[:n].numpy().reshape((z1 - z0,) + src.shape[1:])
+
+    if single:
+        download(0, rows)
+        return res, count
+    for k, z0, z1, _ in stream_slabs([src], slab, device):
+        ccl(k, z0, z1)      # deterministic, numbered in raster order: the local ids of pass 1
+        n = (z1 - z0) * HW
+        dst = flat[z0 * HW:z1 * HW] if kind == 'device' else ids
+        _abi.check(lib.emp_ccl_lut(_abi.ptr(ids), _abi.ptr(lut), bases[k], G + 1, _abi.ptr(dst), n, _abi.stream_ptr(device)), 'emp_ccl_lut')
+        if kind == 'host':
+            download(z0, z1)
+        elif src.is_host:
+            stream.synchronize()      # the staging slot is refilled when the next slab is asked for
+    if stats is not None:
+        stats.update(ccl_runs=st['ccl_runs'])
+    return res, count
+
+
+@torch.no_grad()
+def label_components(labels, out=None, slab=None, device=None, return_count=True, _capacity=None, _table=None, _stats=None):
+    """The connected components of equal non-zero value of a 2-D or 3-D label array under full connectivity (8 neighbours in an
+    image, 26 in a volume) -> (components, count): int32, numbered 1..count in raster order of each component's first element,
+    background 0.  This is ``skimage.measure.label(labels)`` restated from its documented behaviour (skimage is not available here;
+    not pinned against it), and what ``sparse.ccl26`` gives for a volume that fits one call.  ``return_count=False``: the
+    components only.
+
+    ``labels``: a device tensor, a numpy array or a chunked store, of any integer dtype, of any size.  The array is cut into slabs
+    of ``slab`` leading-axis entries (slices of a volume, rows of an image); every slab is labelled on its own with
+    ``emp_ccl_range``, the pieces are joined across the seams by a union-find over the slabs' component ids
+    (csrc/components.hip) and numbered, and a second pass over the slabs writes the result.  The result does not depend on
+    ``slab``.  Default slab: the slab stream's choice (everything for a device tensor, about 64 MiB of a host source), capped at
+    2^28 voxels (about 4 GiB of work memory); with one slab there is no second pass.
+
+    ``out``: None -- a new device tensor for a device source, a new numpy array otherwise -- or an int32 device tensor, numpy array
+    or chunked store of the labels' shape, which is written and returned.
+
+    ``ValueError``, before anything is written: a label above 2^31 - 2, one slice (or an explicit slab) of 2^30 voxels or more, an
+    array that is not 2-D or 3-D, more than 2^31 - 2 components over the slabs."""
+    need_device()
+    device = pick_device(device, labels, out)
+    with torch.cuda.device(device):
+        src = source(labels, device)
+        res, count = _components_of_source(src, out, slab, device, _capacity or COMPONENTS_CAPACITY, _table, _stats, 'label_components')
+    return (res, count) if return_count else res
+
+
+def _clear_border_streamed(labels, per_slice, device, out, inplace, slab, components, what):
+    """``clear_border`` slab by slab -> (the result as ``_edit_target`` says, the number of labels that vanished)"""
+    if per_slice:
+        raise ValueError(f'{what}: streamed=True takes the array as one image or one volume; per_slice is not streamed')
+    src = source(labels, device)
+    rows, H, W = P.components_geometry(src.shape, what)
+    target = _edit_target(labels, out, inplace, src.shape, src.dtype, what)
+    if components is None:
+        components = np.empty(src.shape, np.int32)
+    before = _table_of_source(src, src.shape, False, device, slab, None)
+    comps, _ = label_components(labels, out=components, slab=slab, device=device, _table=before)
+    csrc = source(comps, device)
+    cids = boundary_labels(_table_of_source(csrc, csrc.shape, False, device, slab, None))
+    m = _Map(_map_keys(cids, False), np.zeros(len(cids), np.int64), device)
+    stream = torch.cuda.current_stream(device)
+    src, csrc = source(labels, device), source(comps, device)      # fresh staging for the pass over both
+    if not src.is_host:
+        res = src.t if inplace else torch.empty_like(src.t)
+        for _, z0, z1, (caddr, addr) in stream_slabs([csrc, src], slab, device):
+            m.apply(caddr, csrc.ebytes, addr, src.ebytes, res.data_ptr() + z0 * src.row_bytes, z0, z1 - z0, H, W, False, device)
+            if csrc.is_host:
+                stream.synchronize()      # the components' staging slot is refilled when the next slab is asked for
+    else:
+        res = target if target is not None else np.empty(src.shape, src.dtype)
+        host_rows = max(s.row_bytes for s in (src, csrc) if s.is_host)
+        eslab, _ = slab_plan(rows, host_rows, slab)
+        back = torch.empty(max(1, eslab * src.row_bytes), dtype=torch.uint8).pin_memory()
+        for k, z0, z1, (caddr, addr) in stream_slabs([csrc, src], eslab, device):
+            m.apply(caddr, csrc.ebytes, addr, src.ebytes, addr, z0, z1 - z0, H, W, False, device)
+            nbytes = (z1 - z0) * src.row_bytes
+            back[:nbytes].copy_(src.dev[k & 1][:nbytes], non_blocking=True)
+            stream.synchronize()
+            _write_back(res, z0, z1, back[:nbytes], src.dtype, src.shape)
+    after = _table_of_source(source(res, device), src.shape, False, device, slab, None)
+    return res, _vanished(before, after)
 
 
 # ----------------------------------------------------------------------------

@@ -674,6 +674,32 @@ EMP_API int emp_ccl_range(const void* d_in, int in_bytes, int N, int depth, int 
 EMP_API int emp_rle_extract_range(const void* d_labels, int in_bytes, int N, int H, int W, int64_t lo, int64_t hi,
                         int32_t* d_runs, int32_t* d_num_runs, int max_runs, void* d_work, void* stream);
 
+/* Connected components of an array too large for one emp_ccl_range call, slab by slab (csrc/components.hip): skimage.measure.label
+ * on the whole array (full connectivity, equal value, numbered in raster order of first voxels) -- the components clear_border
+ * clears (_filter_small_labels.py:45) -- from emp_ccl_range on slabs of leading-axis slices.  A slab's local ids 1..K plus the
+ * number of components of all slabs before it (its base) are provisional ids 1..G; d_parent (n_parent >= G + 1 int32, entry g
+ * initialised to g by the caller, entry 0 unused) is a union-find forest over them whose roots are the smallest ids of their sets.
+ *
+ * emp_ccl_seam: the unions across one seam.  d_prev_vals / d_prev_ids: the last slice (H, W) of the previous slab, its values and
+ * its local ids; d_cur_vals / d_cur_ids: the first slice of the current slab.  in_bytes: 4 (int32) or 8 (int64) values, as
+ * emp_ccl_range reads them; a voxel whose id is 0 (background, or a value outside the range the CCL kept) takes no part.  Every
+ * other voxel (y, x) of the current slice is united with the in-bounds voxels (y + dy, x + dx), dy, dx in {-1, 0, 1}, of the
+ * previous slice that hold the same value: parent entries base_cur + id and base_prev + id'.  H * W < 2^30; 0 <= base_prev <=
+ * base_cur < n_parent < 2^31; an id that would fall outside d_parent is skipped, never written.  Does not synchronise. */
+EMP_API int emp_ccl_seam(const void* d_prev_vals, const int32_t* d_prev_ids, const void* d_cur_vals, const int32_t* d_cur_ids,
+                         int in_bytes, int H, int W, int64_t base_prev, int64_t base_cur, int32_t* d_parent, int64_t n_parent,
+                         void* stream);
+/* The final numbers of the provisional ids: d_parent[1..G] is flattened in place, its roots are ranked in id order (the flatten /
+ * count / scan / rank steps of emp_ccl8 on ids instead of voxels) -> d_lut (G + 1) int32, d_lut[0] = 0 and d_lut[g] = the 1-based
+ * rank of g's root; *d_count (device int32) = the number of roots.  0 <= G <= 2^31 - 2; G = 0 gives d_lut[0] = 0 and a count of 0.
+ * Work buffer: emp_ccl_rank_roots_work_bytes(G) (0 for a G outside the domain).  Does not synchronise. */
+EMP_API size_t emp_ccl_rank_roots_work_bytes(int64_t G);
+EMP_API int emp_ccl_rank_roots(int32_t* d_parent, int64_t G, int32_t* d_lut, int32_t* d_count, void* d_work, void* stream);
+/* d_out[i] = d_ids[i] ? d_lut[base + d_ids[i]] : 0 over the n voxels of a slab: local ids -> final numbers.  d_out may be d_ids.
+ * 0 <= base < n_lut < 2^31, n_lut the entries of d_lut; an id that would fall outside it gives 0.  Does not synchronise. */
+EMP_API int emp_ccl_lut(const int32_t* d_ids, const int32_t* d_lut, int64_t base, int64_t n_lut, int32_t* d_out, int64_t n,
+                        void* stream);
+
 /* Run list -> dense volume of elem_bytes-wide integers.  replaces numpy_fill_instances,
  * array_utils.py:754-766 (runs must not overlap: later-overwrites-earlier is not defined here). */
 EMP_API int emp_rle_fill(const int64_t* d_starts, const int64_t* d_lens, const int64_t* d_vals,

@@ -1,11 +1,12 @@
 """Clean up a label volume on the device and print one JSON object: the plugin's Filter Small Labels, Delete Labels, Merge Labels,
 Count Labels, Morph Labels and Split Labels on a file.
-Usage: python tools/clean_labels.py IN [OUT] [--min-area N | --boundary [--whole-labels] | --delete IDS | --merge IDS [--into ID] |
+Usage: python tools/clean_labels.py IN [OUT] [--min-area N | --boundary [--whole-labels | --streamed] | --delete IDS | --merge IDS [--into ID] |
                                              --count --label-divisor D | --morph OP [--radius R] [--3d] |
                                              --fill-holes [HOLE_SIZE] [--radius R] [--3d] |
                                              --split IDS [--min-distance D] [--3d]] [--per-slice]
 IN / OUT: .npy files (IN is memory-mapped and streamed in slabs, OUT is created) or zarr array directories (OUT is created with
-IN's shape, dtype and chunks).  IDS: comma-separated label ids.  --count needs no OUT.  --morph OP: Dilate, Erode, Close or Open
+IN's shape, dtype and chunks).  IDS: comma-separated label ids.  --count needs no OUT.  --boundary --streamed: the reference mode
+(only the components that touch a face go) slab by slab, for volumes the one-call components cannot take.  --morph OP: Dilate, Erode, Close or Open
 of every label with a disk of radius R (a 2-D IN) or, with --3d, a ball (a 3-D IN); IN must be a .npy file (the whole array goes
 to the device); labels_affected is the number of labels that had a turn.  --fill-holes [HOLE_SIZE]: Morph Labels' 'Fill holes' on
 every label: the holes of fewer than HOLE_SIZE voxels (default 64) inside the label's box padded by R; same rules and the same JSON
@@ -65,6 +66,7 @@ def main(argv=None):
     ap.add_argument('--radius', type=int, default=1, help='--morph: radius of the disk / ball, 1..7; --fill-holes: the padding of the box')
     ap.add_argument('--3d', dest='apply3d', action='store_true', help='--morph / --fill-holes / --split: the ball / the volume\'s components / the volume\'s watershed on a 3-D array')
     ap.add_argument('--whole-labels', action='store_true')
+    ap.add_argument('--streamed', action='store_true', help='--boundary: the components slab by slab, for a volume of any size')
     ap.add_argument('--into', type=int, default=None, help='--merge: the id the others become (default: the smallest)')
     ap.add_argument('--label-divisor', type=int, default=0)
     ap.add_argument('--per-slice', action='store_true')
@@ -106,6 +108,14 @@ def main(argv=None):
             run(L.fill_label_holes, hole_size=args.fill_holes, radius=args.radius, apply3d=args.apply3d)
     elif args.min_area is not None:
         n = run(L.filter_out_small_label_areas, args.min_area, per_slice=args.per_slice)
+    elif args.boundary and args.streamed:
+        if args.whole_labels or args.per_slice:
+            ap.error('--streamed is the reference mode of --boundary on one image or volume: not with --whole-labels or --per-slice')
+        if isinstance(src, np.ndarray):      # slab by slab also for a .npy file: the output map is edited in place
+            dst[...] = src
+            n = L.remove_boundary_labels(dst, streamed=True, inplace=True)[1]
+        else:
+            n = L.remove_boundary_labels(src, streamed=True, out=dst)[1]
     elif args.boundary:
         n = run(L.remove_boundary_labels, whole_labels=args.whole_labels, per_slice=args.per_slice)
     else:      # the edits by id do not look at the volume's labels: the number of ids that occur comes from its table
