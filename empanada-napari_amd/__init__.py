@@ -13,6 +13,7 @@ Sub-modules
   inference -- Engine2d / Engine3d mirror (empanada_napari/inference.py)
   metrics   -- scoring of label volumes on the device (empanada_napari/_accuracy_metrics.py, empanada/evaluation)
   labels    -- label clean-up on the device: per-label table, filters, delete / merge (the plugin's label widgets)
-  _labelstream -- what metrics and labels share on the host: sources, the slab stream, the growable device table
+  _labelstream -- what metrics and labels share on the host: sources, the slab stream (it keeps its staging slots safe itself),
+                  the sink of a result, the growable device table
 """
 __version__ = '0.1.0'

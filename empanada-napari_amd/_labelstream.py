@@ -1,5 +1,10 @@
 """What the label tools (metrics.py, labels.py) share on the host: the sources a label array can come from, the double-buffered
-slab stream over them, and the device table that grows when it is too small.  Nothing here knows what a tool counts."""
+slab stream over them, the sink a result goes to row by row, and the device table that grows when it is too small.  Nothing here
+knows what a tool counts.
+
+The stream keeps the staging buffers safe by itself: a slot is refilled only after everything the consumer queued on the slab it
+held, so a consumer never synchronises the host for the stream's sake.  The staging buffers, their slots and the pinned download
+buffer are this module's alone: a consumer sees device addresses, ``slab_bytes`` and a ``Sink``."""
 import ctypes as C
 
 import numpy as np
@@ -68,14 +73,12 @@ class RawSource:
         self.row_elems = int(np.prod(self.shape[1:], dtype=np.int64)) if self.shape else 1
         self.row_bytes = self.row_elems * abs(ebytes)
 
-    def reserve(self, slab_rows, copy_stream):
-        pass
-
-    def stage(self, z0, z1, slot):
-        pass
-
     def address(self, z0, z1, slot, stream):
         return self.t.data_ptr() + z0 * self.row_bytes
+
+    def slab_bytes(self, k, z0, z1):
+        """slab k = rows [z0, z1) as the device bytes whose address the stream handed out"""
+        return self.t.reshape(-1).view(torch.uint8)[z0 * self.row_bytes:z1 * self.row_bytes]
 
 
 class DeviceSource(RawSource):
@@ -111,6 +114,8 @@ class HostSource(RawSource):
         block = self.x[z0:z1] if self.shape else self.x
         block = np.ascontiguousarray(np.asarray(block), dtype=self.dtype).reshape(-1)
         nbytes = block.size * abs(self.ebytes)
+        if self.events[slot] is not None:
+            self.events[slot].synchronize()      # the slot's last upload has read the pinned buffer (long ago, in practice)
         self.pinned[slot][:nbytes].numpy()[:] = block.view(np.uint8)
         with torch.cuda.stream(self.copy_stream):
             self.dev[slot][:nbytes].copy_(self.pinned[slot][:nbytes], non_blocking=True)
@@ -121,6 +126,9 @@ class HostSource(RawSource):
     def address(self, z0, z1, slot, stream):
         stream.wait_event(self.events[slot])
         return self.dev[slot].data_ptr()
+
+    def slab_bytes(self, k, z0, z1):
+        return self.dev[k & 1][:(z1 - z0) * self.row_bytes]
 
 
 def source(x, device):
@@ -152,9 +160,9 @@ def stream_slabs(sources, slab, device):
     current stream.  Host sources are double-buffered: slab k + 1 is read, copied into its pinned buffer and queued on a copy
     stream before slab k is handed out, so that the upload runs under whatever the consumer launches on slab k.
 
-    The contract: a slot (k & 1) is staged again when slab k + 1 is asked for, so by then the consumer must have synchronised
-    the compute stream on its work on slab k.  The tables' ``add`` does (it reads the overflow flag back); an edit does after its
-    download."""
+    The guarantee: slab k stays as it was handed out until everything the consumer queued on that stream before it asked for
+    slab k + 1 has run.  An event recorded then stands for that work, and the copy stream waits for it before it refills the slot
+    (k & 1) with slab k + 2: the consumer need not synchronise the host, and the host does not stall for it."""
     rows = sources[0].rows
     host = [s for s in sources if s.is_host]
     slab, bounds = slab_plan(rows, max(s.row_bytes for s in host) if host else None, slab)
@@ -163,15 +171,66 @@ def stream_slabs(sources, slab, device):
         copy_stream = torch.cuda.Stream(device=device)
         for s in host:
             s.reserve(slab, copy_stream)
+    consumed = [None, None]      # per slot: the consumer's work on the slab it held last
 
     def stage(k):
         if k < len(bounds):
-            for s in sources:
+            if consumed[k & 1] is not None:
+                copy_stream.wait_event(consumed[k & 1])
+            for s in host:
                 s.stage(*bounds[k], k & 1)
     stage(0)
     for k, (z0, z1) in enumerate(bounds):
-        stage(k + 1)      # that slot's last slab, k - 1, was consumed and waited for: the contract
+        stage(k + 1)
         yield k, z0, z1, [s.address(z0, z1, k & 1, stream) for s in sources]
+        if host:
+            consumed[k & 1] = stream.record_event()
+
+
+# ----------------------------------------------------------------------------
+# the sink
+# ----------------------------------------------------------------------------
+class Sink:
+    """Where a result of ``shape`` and ``dtype`` goes, rows [z0, z1) of the leading axis at a time.  ``dest``: a contiguous device
+    tensor, which a kernel writes through ``address``; or a numpy array or a chunked store (anything with ``__setitem__``), which
+    gets the rows a kernel left on the device through ``write``.  ``dest=None`` is a new array, made when it is first needed: a
+    tensor on ``device``, a numpy array without one."""
+
+    def __init__(self, dest, shape, dtype, device=None):
+        self.dest, self.shape, self.device = dest, tuple(int(s) for s in shape), device
+        self.dtype = dtype if isinstance(dtype, torch.dtype) else np.dtype(dtype)
+        self.is_host = device is None if dest is None else not isinstance(dest, torch.Tensor)
+        self.row_bytes = int(np.prod(self.shape[1:], dtype=np.int64)) * abs(ebytes(self.dtype))
+        self.back = None
+
+    def made(self):
+        if self.dest is None:
+            self.dest = np.empty(self.shape, self.dtype) if self.is_host else torch.empty(self.shape, dtype=self.dtype, device=self.device)
+        return self.dest
+
+    def address(self, z0):
+        """device destination: where its row z0 begins"""
+        return self.made().data_ptr() + z0 * self.row_bytes
+
+    def put(self, z0, z1, host):
+        """host destination: rows [z0, z1), on the host as the bytes ``host``, are written.  The whole of a new array is that array."""
+        arr = host.numpy().view(self.dtype).reshape((z1 - z0,) + self.shape[1:])
+        if self.dest is None and (z0, z1) == (0, self.shape[0]):
+            self.dest = arr
+        else:
+            self.made()[z0:z1] = arr
+        return self.dest
+
+    def write(self, z0, z1, dev_bytes):
+        """host destination: rows [z0, z1) lie at the head of the device bytes ``dev_bytes``.  They come down through a pinned buffer
+        as large as the first, the largest, slab: the one place where the label tools synchronise for a download"""
+        self.made()
+        nbytes = (z1 - z0) * self.row_bytes
+        if self.back is None:
+            self.back = torch.empty(max(1, nbytes), dtype=torch.uint8).pin_memory()
+        self.back[:nbytes].copy_(dev_bytes[:nbytes], non_blocking=True)
+        torch.cuda.current_stream(dev_bytes.device).synchronize()
+        self.put(z0, z1, self.back[:nbytes])
 
 
 # ----------------------------------------------------------------------------

@@ -29,9 +29,11 @@ keeps their device drivers (``_morph_device``, ``_fill_device``, ``_split_device
 re-exports the public names.
 
 Inputs are those of ``metrics.label_overlap``: device tensors (read in place), numpy arrays and chunked stores
-(``zstore.DirArray``, zarr arrays) streamed in leading-axis slabs through pinned staging buffers.  An edit returns the kind of
-object it was given: a device tensor for a device tensor, a new numpy array for a numpy array (the caller's array is only written
-with ``inplace=True``), and for a store the store given as ``out=``, written slab by slab.
+(``zstore.DirArray``, zarr arrays) streamed in leading-axis slabs by ``_labelstream.stream_slabs``, which keeps a staged slab
+intact until the work queued on it has run: no tool here synchronises for it.  Results go to a ``_labelstream.Sink``, whose
+destination ``_edit_target`` / ``_components_target`` choose: kernels write a device tensor directly, host rows come down through
+the sink's pinned buffer.  An edit returns the kind of object it was given: a device tensor for a device tensor, a new numpy array
+for a numpy array (the caller's own only with ``inplace=True``), and for a store the store given as ``out=``, written slab by slab.
 
 skimage is not available where this package is built and tested: what ``regionprops_table`` and ``clear_border`` compute is
 restated from their documented behaviour (area = voxel count; bbox = minimum and exclusive maximum per axis; clear_border =
@@ -61,7 +63,7 @@ from . import _abi, _labelplan as P
 from ._labelplan import (FILL_MAX_HOLE_SIZE, FILL_MAX_LEVEL_VOXELS, MORPH_MAX_RADIUS, MORPH_OPS, SPLIT_MAX_BOXES, SPLIT_MAX_DIAGONAL2,  # noqa: F401
                          SPLIT_MAX_DISTANCE, SPLIT_MAX_ENTRIES, _MORPH_GROWS, _morph_args, _morph_tiles, _morph_turns, _split_batches, dims3,
                          morph_footprint_offsets, morph_footprint_rows, morph_schedule, split_marker_ids, split_spacing)
-from ._labelstream import GrowableTable, RawSource, ebytes, hp, initial_capacity, need_device, pick_device, slab_plan, source, stream_slabs
+from ._labelstream import GrowableTable, RawSource, Sink, ebytes, hp, initial_capacity, need_device, pick_device, slab_plan, source, stream_slabs
 
 __all__ = ['LabelTable', 'label_table', 'table_from_arrays', 'LabelMeasures', 'measure_labels', 'measures_from_arrays', 'small_labels', 'boundary_labels', 'count_labels', 'class_label_lists',
            'next_available_labels', 'next_available_label', 'label_bbox', 'delete_labels', 'merge_labels',
@@ -335,15 +337,12 @@ def _measures_of_source(src, shape, spacing, per_slice, border_faces, device, sl
     # the staging slot that the stream refills while this slab is counted, so its last slice is kept in a buffer of its own
     host_halo = src.is_host and not per_slice
     halo = torch.empty(max(1, src.row_bytes), dtype=torch.uint8, device=device) if host_halo else None
-    stream = torch.cuda.current_stream(device)
     for _, z0, z1, (address,) in stream_slabs([src], slab, device):
         below = None if per_slice or z0 == 0 else (halo.data_ptr() if host_halo else address - src.row_bytes)
         table.add(address, src.ebytes, z0, z1 - z0, H, W, rows, below, int(per_slice), int(bool(border_faces)))
         if host_halo and z1 < rows:
-            # `add` has synchronised before this copy is queued: wait for it too, or the refill of this slot could overtake it
             _abi.check(table.lib.emp_copy_d2d(_abi.ptr(halo), address + (z1 - z0 - 1) * src.row_bytes, src.row_bytes, _abi.stream_ptr(device)),
                        'emp_copy_d2d')
-            stream.synchronize()
     keys, cnt, box, sums, faces = (t.cpu().numpy() for t in table.finalize(extra=[(6, torch.int32), (9, torch.int64), (3, torch.int64)]))
     box = box.astype(np.int64)
     box[:, 3:] += 1      # exclusive upper ends
@@ -515,9 +514,9 @@ def _check_values(vals, dtype, what):
 
 
 def _edit_target(labels, out, inplace, shape, dtype, what):
-    """The output rules of an edit: every check of (labels, out, inplace), and where the result goes.  A device tensor gives a
-    device tensor and a numpy array a numpy array, the caller's own with ``inplace=True`` and a new one (None is returned)
-    without; a chunked store of ``shape`` and ``dtype`` is written into ``out=``, or into itself with ``inplace=True``."""
+    """The output rules of an edit: every check of (labels, out, inplace), and the ``Sink`` the result goes to.  A device tensor
+    gives a device tensor and a numpy array a numpy array, the caller's own with ``inplace=True`` and a new one without; a chunked
+    store of ``shape`` and ``dtype`` is written into ``out=``, or into itself with ``inplace=True``."""
     if isinstance(labels, torch.Tensor):
         if not labels.is_cuda:
             raise TypeError(f'{what}: a torch tensor must be on the device (pass host data as a numpy array)')
@@ -525,53 +524,35 @@ def _edit_target(labels, out, inplace, shape, dtype, what):
             raise TypeError(f'{what}: out= is for chunked stores; a device tensor is returned as a device tensor')
         if inplace and not labels.is_contiguous():
             raise ValueError(f'{what}: inplace=True needs a contiguous tensor')
-        return labels if inplace else None
+        return Sink(labels if inplace else None, shape, dtype, labels.device)
     if _is_numpy(labels):
         if out is not None:
             raise TypeError(f'{what}: out= is for chunked stores; a numpy array is returned as a new array (or edited with inplace=True)')
-        return labels if inplace else None
+        return Sink(labels if inplace else None, shape, dtype)
     if out is None:
         if not inplace:
             raise TypeError(f'{what}: a chunked store is written into out= (or into itself with inplace=True)')
-        return labels
+        return Sink(labels, shape, dtype)
     if tuple(out.shape) != tuple(shape) or np.dtype(out.dtype) != np.dtype(dtype):
         raise ValueError(f'{what}: out= must have the shape and dtype of the labels')
-    return out
+    return Sink(out, shape, dtype)
 
 
-def _write_back(target, z0, z1, host, dtype, shape):
-    """rows [z0, z1) of a finished result of ``shape``, downloaded as the bytes ``host``, go to the target ``_edit_target`` chose;
-    without one they are the new array"""
-    arr = host.numpy().view(dtype).reshape((z1 - z0,) + tuple(shape[1:]))
-    if target is None:
-        return arr
-    target[z0:z1] = arr
-    return target
-
-
-def _apply(labels, keys, vals, per_slice, device, out, inplace, slab, what):
-    """out[i] = map[key(i)] if present else labels[i]; keys are labels, or slice << 32 | label with per_slice"""
+def _apply(labels, keys, vals, per_slice, device, out, inplace, slab, what, *, key_labels=None):
+    """out[i] = map[key(i)] if present else labels[i]; the key of i is labels[i] -- or ``key_labels[i]``, an array of the labels'
+    shape from any kind of source --, or slice << 32 | that with per_slice.  A host slab is edited where it was staged"""
     src = source(labels, device)
-    target = _edit_target(labels, out, inplace, src.shape, src.dtype, what)
+    sink = _edit_target(labels, out, inplace, src.shape, src.dtype, what)
     rows, H, W = _geometry(src.shape, per_slice, what)
     _check_values(vals, src.dtype, what)
     m = _Map(keys, vals, device)
-    if not src.is_host:
-        res = src.t if inplace else torch.empty_like(src.t)
-        m.apply(src.t.data_ptr(), src.ebytes, src.t.data_ptr(), src.ebytes, res.data_ptr(), 0, rows, H, W, per_slice, device)
-        return res
-    if target is None:
-        target = np.empty_like(labels)
-    stream = torch.cuda.current_stream(device)
-    slab, _ = slab_plan(rows, src.row_bytes, slab)      # planned here for the size of the download buffer
-    back = torch.empty(max(1, slab * src.row_bytes), dtype=torch.uint8).pin_memory()
-    for k, z0, z1, (addr,) in stream_slabs([src], slab, device):
-        m.apply(addr, src.ebytes, addr, src.ebytes, addr, z0, z1 - z0, H, W, per_slice, device)
-        nbytes = (z1 - z0) * src.row_bytes
-        back[:nbytes].copy_(src.dev[k & 1][:nbytes], non_blocking=True)
-        stream.synchronize()      # the slab is on the host; its device buffer is free for the upload after next
-        _write_back(target, z0, z1, back[:nbytes], src.dtype, src.shape)
-    return target
+    sources = [src] if key_labels is None else [source(key_labels, device), src]
+    for k, z0, z1, addrs in stream_slabs(sources, slab, device):
+        m.apply(addrs[0], sources[0].ebytes, addrs[-1], src.ebytes, addrs[-1] if sink.is_host else sink.address(z0), z0, z1 - z0, H, W,
+                per_slice, device)
+        if sink.is_host:
+            sink.write(z0, z1, src.slab_bytes(k, z0, z1))
+    return sink.made()
 
 
 def _map_keys(ids, per_slice):
@@ -670,23 +651,23 @@ def remove_boundary_labels(labels, whole_labels=False, per_slice=False, device=N
                              f'{shape}; use whole_labels=True (removes whole labels by their boxes, slab by slab) or streamed=True '
                              '(the same components, slab by slab)')
         # what the call cannot do is said before any work: nothing is written, on the device or to the caller's array, by then
-        target = _edit_target(labels, out, inplace, shape, labels.dtype, what)
+        sink = _edit_target(labels, out, inplace, shape, labels.dtype, what)
         edit_own = bool(inplace) and isinstance(labels, torch.Tensor)      # the result replaces the caller's tensor
-        return _whole_array(labels, target, device, False, lambda t, eb: _clear_border(t, eb, shape, per_slice, edit_own, device))
+        return _whole_array(labels, sink, device, False, lambda t, eb: _clear_border(t, eb, shape, per_slice, edit_own, device))
 
 
-def _whole_array(labels, target, device, clone, run):
+def _whole_array(labels, sink, device, clone, run):
     """The way of a whole array to the device and back, for the tools that need all of it there at once.  ``labels``: a device
-    tensor or host data that passed ``_edit_target``, which chose ``target``.  ``run(t, eb)`` gets it as one contiguous device
+    tensor or host data that passed ``_edit_target``, which chose ``sink``.  ``run(t, eb)`` gets it as one contiguous device
     buffer -- the tensor itself, a clone of it with ``clone``, or host data uploaded as bytes (torch has no arithmetic on uint16 /
     uint32) -- and returns (the device buffer that holds the result, anything else) -> (the result as the kind that was given: that
-    buffer for a device tensor, else downloaded into the target, anything else)."""
+    buffer for a device tensor, else downloaded in one piece into the sink, anything else)."""
     if isinstance(labels, torch.Tensor):      # a tensor that passed the check is on the device
         t = labels if labels.is_contiguous() else labels.contiguous()
         return run(t.clone() if clone else t, ebytes(t.dtype))
     host = np.ascontiguousarray(labels if _is_numpy(labels) else labels[...])
     res, rest = run(torch.from_numpy(host.view(np.uint8).reshape(-1)).to(device), ebytes(host.dtype))
-    return _write_back(target, 0, host.shape[0], res.cpu(), host.dtype, host.shape), rest
+    return sink.put(0, host.shape[0], res.cpu()), rest
 
 
 def _clear_border(t, eb, shape, per_slice, edit_own, device):
@@ -712,9 +693,10 @@ def _clear_border(t, eb, shape, per_slice, edit_own, device):
     # components are numbered per image: their key is slice << 32 | id there
     ctable = _table_of_source(RawSource(comps, -4, tuple(comps.shape)), tuple(comps.shape), images, device, None, None)
     cids = boundary_labels(ctable)
-    m = _Map(_map_keys(cids, images), np.zeros(len(cids), np.int64), device)
-    res = t if edit_own else torch.empty_like(t)
-    m.apply(comps.data_ptr(), -4, t.data_ptr(), eb, res.data_ptr(), 0, comps.shape[0], cH, cW, images, device)
+    # the edit runs in the components' geometry, the images of a stack or the one volume, on the buffer's elements
+    res = _apply(_elements(t, eb).reshape(comps.shape), _map_keys(cids, images), np.zeros(len(cids), np.int64), images, device, None,
+                 edit_own, None, 'remove_boundary_labels', key_labels=comps)
+    res = t if edit_own else res.reshape(-1).view(torch.uint8).view(t.dtype).reshape(t.shape)
     after = _table_of_source(RawSource(res, eb, shape), shape, per_slice, device, None, None)
     return res, _vanished(before, after)
 
@@ -740,10 +722,10 @@ COMPONENTS_CAPACITY = 1 << 16      # first size of the union-find over the slabs
 
 
 def _components_target(src, out, device, what):
-    """Where the components go, every check of ``out`` included: ('device', tensor or None) or ('host', array / store or None).
-    None: a new device tensor for a device source, a new numpy array otherwise."""
+    """Where the components go, every check of ``out`` included: the ``Sink`` of a device tensor, or of an array / store on the
+    host.  None: a new device tensor for a device source, a new numpy array otherwise."""
     if out is None:
-        return ('host' if src.is_host else 'device'), None
+        return Sink(None, src.shape, np.int32) if src.is_host else Sink(None, src.shape, torch.int32, device)
     if isinstance(out, torch.Tensor):
         if not out.is_cuda:
             raise TypeError(f'{what}: a torch tensor given as out= must be on the device (pass host memory as a numpy array)')
@@ -753,37 +735,27 @@ def _components_target(src, out, device, what):
             raise ValueError(f'{what}: out= must be int32 and have the shape of the labels')
         if not out.is_contiguous():
             raise ValueError(f'{what}: out= needs a contiguous tensor')
-        return 'device', out
+        return Sink(out, src.shape, torch.int32)
     if not (hasattr(out, 'shape') and hasattr(out, 'dtype') and hasattr(out, '__setitem__')):
         raise TypeError(f'{what}: out= is an int32 device tensor, numpy array or chunked store')
     if tuple(out.shape) != src.shape or np.dtype(out.dtype) != np.dtype(np.int32):
         raise ValueError(f'{what}: out= must be int32 and have the shape of the labels')
-    return 'host', out
-
-
-def _slab_bytes(src, k, z0, z1):
-    """slab k = rows [z0, z1) of a source as the device bytes the stream handed out"""
-    if src.is_host:
-        return src.dev[k & 1][:(z1 - z0) * src.row_bytes]
-    return src.t.reshape(-1).view(torch.uint8)[z0 * src.row_bytes:z1 * src.row_bytes]
+    return Sink(out, src.shape, np.int32)
 
 
 def _components_of_source(src, out, slab, device, capacity, table, stats, what):
     rows, H, W = P.components_geometry(src.shape, what)
     HW = H * W
     slab = P.components_slab(rows, HW, slab, slab_plan(rows, src.row_bytes if src.is_host else None, None)[0], what)
-    kind, target = _components_target(src, out, device, what)
+    sink = _components_target(src, out, device, what)
     if rows * HW == 0:
-        res = target if target is not None else (torch.zeros(src.shape, dtype=torch.int32, device=device) if kind == 'device'
-                                                 else np.zeros(src.shape, np.int32))
-        return res, 0
+        return sink.made(), 0
     # the largest label, off the table as _clear_border reads it; the table's pass also refuses what is no label at all
     if table is None:
         table = _table_of_source(src, src.shape, False, device, slab, None)
     P.components_check_labels(table.labels.max() if len(table.labels) else 0, what)
 
     lib = _abi.load()
-    stream = torch.cuda.current_stream(device)
     ids = torch.empty(slab * HW, dtype=torch.int32, device=device)
     num = torch.empty(1, dtype=torch.int32, device=device)
     work = torch.empty(int(lib.emp_ccl8_work_bytes(1, slab * H, W)), dtype=torch.uint8, device=device)
@@ -791,7 +763,7 @@ def _components_of_source(src, out, slab, device, capacity, table, stats, what):
 
     def ccl(k, z0, z1):
         """the slab's local ids in ``ids`` -> the labels as the kernel read them"""
-        wide = _as_ccl_input(_slab_bytes(src, k, z0, z1), src.ebytes, None)
+        wide = _as_ccl_input(src.slab_bytes(k, z0, z1), src.ebytes, None)
         _abi.check(lib.emp_ccl_range(_abi.ptr(wide), 8 if wide.dtype == torch.int64 else 4, 1, z1 - z0, H, W, 1, CCL_MAX_LABEL + 1,
                                      _abi.ptr(ids), _abi.ptr(num), _abi.ptr(work), _abi.stream_ptr(device)), 'emp_ccl_range')
         st['ccl_runs'] += 1
@@ -821,12 +793,9 @@ def _components_of_source(src, out, slab, device, capacity, table, stats, what):
         bases.append(G)
         G += K
         if z1 < rows:
-            # the last slice, values and ids, for the next seam: `ids` is written again by then, and a host source's staging
-            # slot is refilled while the next slab runs -- wait for the copies, or that refill could overtake them
+            # the last slice, values and ids, for the next seam: `ids` is written again by then, and so is a host source's slot
             n = (z1 - z0) * HW
             prev_vals, prev_ids = wide[n - HW:n].clone(), ids[n - HW:n].clone()
-            if src.is_host:
-                stream.synchronize()
         del wide
     st['slabs'], st['provisional'] = len(bases), G
 
@@ -846,39 +815,24 @@ def _components_of_source(src, out, slab, device, capacity, table, stats, what):
         stats.update(st, count=count)
 
     # pass 2: nothing has been written so far
-    if kind == 'device':
-        if single:
-            res = ids.reshape(src.shape)
-            if target is not None:
-                target.copy_(res)
-            return (res if target is None else target), count
-        res = target if target is not None else torch.empty(src.shape, dtype=torch.int32, device=device)
-        flat = res.reshape(-1)
-    else:
-        res = target if target is not None else np.empty(src.shape, np.int32)
-        back = torch.empty(slab * HW, dtype=torch.int32).pin_memory()
-
-    def download(z0, z1):
-        n = (z1 - z0) * HW
-        back[:n].copy_(ids[:n], non_blocking=True)
-        stream.synchronize()
-        res[z0:z1] = back[:n].numpy().reshape((z1 - z0,) + src.shape[1:])
-
-    if single:
-        download(0, rows)
-        return res, count
+    if single:      # `ids` holds the result
+        if sink.is_host:
+            sink.write(0, rows, ids.view(torch.uint8))
+        elif sink.dest is None:
+            sink.dest = ids.reshape(src.shape)
+        else:
+            sink.dest.copy_(ids.reshape(src.shape))
+        return sink.dest, count
     for k, z0, z1, _ in stream_slabs([src], slab, device):
         ccl(k, z0, z1)      # deterministic, numbered in raster order: the local ids of pass 1
-        n = (z1 - z0) * HW
-        dst = flat[z0 * HW:z1 * HW] if kind == 'device' else ids
-        _abi.check(lib.emp_ccl_lut(_abi.ptr(ids), _abi.ptr(lut), bases[k], G + 1, _abi.ptr(dst), n, _abi.stream_ptr(device)), 'emp_ccl_lut')
-        if kind == 'host':
-            download(z0, z1)
-        elif src.is_host:
-            stream.synchronize()      # the staging slot is refilled when the next slab is asked for
+        dst = ids.data_ptr() if sink.is_host else sink.address(z0)      # a host slab is finished in `ids` and downloaded from there
+        _abi.check(lib.emp_ccl_lut(_abi.ptr(ids), _abi.ptr(lut), bases[k], G + 1, C.c_void_p(dst), (z1 - z0) * HW, _abi.stream_ptr(device)),
+                   'emp_ccl_lut')
+        if sink.is_host:
+            sink.write(z0, z1, ids.view(torch.uint8))
     if stats is not None:
         stats.update(ccl_runs=st['ccl_runs'])
-    return res, count
+    return sink.dest, count
 
 
 @torch.no_grad()
@@ -914,34 +868,15 @@ def _clear_border_streamed(labels, per_slice, device, out, inplace, slab, compon
     if per_slice:
         raise ValueError(f'{what}: streamed=True takes the array as one image or one volume; per_slice is not streamed')
     src = source(labels, device)
-    rows, H, W = P.components_geometry(src.shape, what)
-    target = _edit_target(labels, out, inplace, src.shape, src.dtype, what)
+    P.components_geometry(src.shape, what)
+    _edit_target(labels, out, inplace, src.shape, src.dtype, what)      # what the edit would refuse, before any work
     if components is None:
         components = np.empty(src.shape, np.int32)
     before = _table_of_source(src, src.shape, False, device, slab, None)
     comps, _ = label_components(labels, out=components, slab=slab, device=device, _table=before)
     csrc = source(comps, device)
     cids = boundary_labels(_table_of_source(csrc, csrc.shape, False, device, slab, None))
-    m = _Map(_map_keys(cids, False), np.zeros(len(cids), np.int64), device)
-    stream = torch.cuda.current_stream(device)
-    src, csrc = source(labels, device), source(comps, device)      # fresh staging for the pass over both
-    if not src.is_host:
-        res = src.t if inplace else torch.empty_like(src.t)
-        for _, z0, z1, (caddr, addr) in stream_slabs([csrc, src], slab, device):
-            m.apply(caddr, csrc.ebytes, addr, src.ebytes, res.data_ptr() + z0 * src.row_bytes, z0, z1 - z0, H, W, False, device)
-            if csrc.is_host:
-                stream.synchronize()      # the components' staging slot is refilled when the next slab is asked for
-    else:
-        res = target if target is not None else np.empty(src.shape, src.dtype)
-        host_rows = max(s.row_bytes for s in (src, csrc) if s.is_host)
-        eslab, _ = slab_plan(rows, host_rows, slab)
-        back = torch.empty(max(1, eslab * src.row_bytes), dtype=torch.uint8).pin_memory()
-        for k, z0, z1, (caddr, addr) in stream_slabs([csrc, src], eslab, device):
-            m.apply(caddr, csrc.ebytes, addr, src.ebytes, addr, z0, z1 - z0, H, W, False, device)
-            nbytes = (z1 - z0) * src.row_bytes
-            back[:nbytes].copy_(src.dev[k & 1][:nbytes], non_blocking=True)
-            stream.synchronize()
-            _write_back(res, z0, z1, back[:nbytes], src.dtype, src.shape)
+    res = _apply(labels, _map_keys(cids, False), np.zeros(len(cids), np.int64), False, device, out, inplace, slab, what, key_labels=comps)
     after = _table_of_source(source(res, device), src.shape, False, device, slab, None)
     return res, _vanished(before, after)
 
@@ -1091,7 +1026,7 @@ def _morph_call(labels, what, run, apply3d, plane, axis, device, out, inplace):
     need_device()
     device = pick_device(device, labels)
     with torch.cuda.device(device):
-        target = _edit_target(labels, out, inplace, shape, labels.dtype, what)
+        sink = _edit_target(labels, out, inplace, shape, labels.dtype, what)
 
         def whole(t, eb):
             if len(shape) == 3 and not ball:
@@ -1102,7 +1037,7 @@ def _morph_call(labels, what, run, apply3d, plane, axis, device, out, inplace):
             else:
                 run(t, eb, shape, ball, device)
             return t, None
-        return _whole_array(labels, target, device, not inplace, whole)[0]
+        return _whole_array(labels, sink, device, not inplace, whole)[0]
 
 
 @torch.no_grad()
@@ -1245,7 +1180,8 @@ def _split_device(t, eb, shape, points, ids, min_distance, points_as_markers, st
             t.copy_(before)
         raise
     if stages is not None:
-        torch.cuda.synchronize(device)
+        if events:
+            events[-1][2].synchronize()      # the last event of the stream: every pair before it has been reached
         for name, a, b in events:
             stages[name] = stages.get(name, 0.0) + a.elapsed_time(b)
     return report, stats

@@ -274,6 +274,123 @@ def test_merge_labels_default_target_and_dropped_zeros():
         L.merge_labels(_dev(img), [0, 0])
 
 
+@pytest.mark.parametrize('dtype', [np.uint8, np.uint16, np.int64])
+def test_edit_destinations_with_an_uneven_last_slab(dtype, tmp_path):
+    """every destination of an edit -- a new and the caller's own device tensor, a new and the caller's own numpy array, a store
+    as out= and a store edited in place -- with slabs of 3 rows: 7 rows end in a slab of one, 6 rows in a whole one"""
+    from empanada_napari_amd import labels as L, zstore
+    for rows in (7, 6):
+        vol = LC.runs(rows * 5 * 6, 17 + rows, dtype, run=4, top=40).reshape(rows, 5, 6)
+        ids = np.unique(vol)[1::2]
+        want = np.where(np.isin(vol, ids), 0, vol)
+        d = _dev(vol)
+        out = L.delete_labels(d, ids, slab=3)
+        assert out is not d and out.dtype == d.dtype and np.array_equal(_host(out), want) and np.array_equal(_host(d), vol)
+        assert L.delete_labels(d, ids, slab=3, inplace=True) is d and np.array_equal(_host(d), want)
+        own = vol.copy()
+        out = L.delete_labels(own, ids, slab=3)
+        assert out is not own and out.dtype == vol.dtype and np.array_equal(out, want) and np.array_equal(own, vol)
+        assert L.delete_labels(own, ids, slab=3, inplace=True) is own and np.array_equal(own, want)
+        za = zstore.DirArray.create(str(tmp_path / f'in{rows}'), vol.shape, dtype, (2, 5, 6))
+        za[...] = vol
+        zo = zstore.DirArray.create(str(tmp_path / f'out{rows}'), vol.shape, dtype, (4, 5, 6))
+        assert L.delete_labels(za, ids, slab=3, out=zo) is zo and np.array_equal(np.asarray(zo[...]), want)
+        assert np.array_equal(np.asarray(za[...]), vol)
+        assert L.delete_labels(za, ids, slab=3, inplace=True) is za
+        assert np.array_equal(np.asarray(zstore.DirArray(str(tmp_path / f'in{rows}'))[...]), want)
+
+
+@pytest.mark.parametrize('keys_on, data_on', [('device', 'device'), ('device', 'host'), ('host', 'device'), ('host', 'host')])
+def test_apply_with_a_key_source(keys_on, data_on, tmp_path):
+    """the edit keyed by a second array, as the streamed clear-border runs it: int32 keys, uint8 data, each on the device or on the
+    host, slabs of 4 of 6 rows, into every destination the data's kind has"""
+    import torch
+    from empanada_napari_amd import labels as L, zstore
+    shape = (6, 5, 7)
+    keys = LC.runs(6 * 5 * 7, 5, np.int32, run=3, top=60).reshape(shape)
+    data = LC.runs(6 * 5 * 7, 6, np.uint8, run=5, top=200).reshape(shape)
+    ids = np.unique(keys)[1::3]
+    want = np.where(np.isin(keys, ids), 0, data)
+    assert 0 < (want != data).sum() < data.size
+    device = torch.device('cuda', 0)
+
+    def store(name, arr):
+        za = zstore.DirArray.create(str(tmp_path / name), shape, arr.dtype, (4, 5, 7))
+        za[...] = arr
+        return za
+
+    def run(k, d, out, inplace):
+        with torch.cuda.device(0):
+            return L._apply(d, L._map_keys(ids, False), np.zeros(len(ids), np.int64), False, device, out, inplace, 4, 'test', key_labels=k)
+    for i, k in enumerate([_dev(keys)] if keys_on == 'device' else [keys, store('keys', keys)]):
+        if data_on == 'device':
+            d = _dev(data)
+            out = run(k, d, None, False)
+            assert out is not d and out.dtype == torch.uint8 and np.array_equal(_host(out), want) and np.array_equal(_host(d), data)
+            assert run(k, d, None, True) is d and np.array_equal(_host(d), want)
+        else:
+            own = data.copy()
+            out = run(k, own, None, False)
+            assert isinstance(out, np.ndarray) and out is not own and np.array_equal(out, want) and np.array_equal(own, data)
+            assert run(k, own, None, True) is own and np.array_equal(own, want)
+            zo = zstore.DirArray.create(str(tmp_path / f'out{i}'), shape, np.uint8, (2, 5, 7))
+            assert run(k, store(f'data{i}', data), zo, False) is zo and np.array_equal(np.asarray(zo[...]), want)
+        if keys_on == 'host':
+            assert np.array_equal(np.asarray(k[...]), keys)      # the keys are only read
+
+
+# ----------------------------------------------------------------------------
+# the slab stream
+# ----------------------------------------------------------------------------
+_SPIN = {}
+
+
+def _delay(ms=3.0):
+    """a few milliseconds of work on the current stream: torch's spin kernel, its cycles per millisecond measured once; without
+    it large elementwise passes over a scratch tensor"""
+    import torch
+    if not hasattr(torch.cuda, '_sleep'):
+        scratch = _SPIN.setdefault('scratch', torch.zeros(1 << 26, device='cuda'))
+        for _ in range(8):
+            scratch.add_(1.0)
+        return
+    if 'cycles_per_ms' not in _SPIN:
+        torch.cuda._sleep(1000)      # loads the kernel
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        torch.cuda._sleep(1_000_000)
+        e1.record()
+        e1.synchronize()
+        _SPIN['cycles_per_ms'] = 1_000_000 / max(e0.elapsed_time(e1), 1e-3)
+    torch.cuda._sleep(int(ms * _SPIN['cycles_per_ms']))
+
+
+@pytest.mark.parametrize('dtypes', [(np.uint16,), (np.uint16, np.int32)])
+def test_stream_keeps_a_slab_until_the_consumer_is_done(dtypes):
+    """A consumer that never synchronises the host: per one-row slab it queues a delay and then a device copy of the slab into its
+    place in a result.  The stream refills a staging slot two slabs later: were that not ordered behind the consumer's queue, the
+    copy would read a later slab's rows (inside the same buffers: wrong data, never a fault).  One host source, and two of
+    different row sizes, as label_overlap and the streamed clear-border have them"""
+    import torch
+    from empanada_napari_amd import _abi, _labelstream as S
+    shape = (12, 4, 8)
+    device = torch.device('cuda', 0)
+    arrays = [(np.arange(12 * 4 * 8) * (3 + i) + 1 + i).astype(dt).reshape(shape) for i, dt in enumerate(dtypes)]
+    lib = _abi.load()
+    with torch.cuda.device(0):
+        sources = [S.HostSource(a, device) for a in arrays]
+        results = [torch.zeros(a.nbytes, dtype=torch.uint8, device=device) for a in arrays]
+        for _, z0, z1, addresses in S.stream_slabs(sources, 1, device):
+            assert z1 == z0 + 1
+            for s, res, address in zip(sources, results, addresses):
+                _delay()
+                _abi.check(lib.emp_copy_d2d(res.data_ptr() + z0 * s.row_bytes, address, s.row_bytes, _abi.stream_ptr(device)), 'emp_copy_d2d')
+        got = [res.cpu().numpy().view(a.dtype).reshape(shape) for res, a in zip(results, arrays)]
+    for g, a in zip(got, arrays):
+        wrong = np.flatnonzero((g != a).any(axis=(1, 2)))
+        assert np.array_equal(g, a), f'rows {wrong.tolist()} hold another slab'
+
+
 # ----------------------------------------------------------------------------
 # boundary labels
 # ----------------------------------------------------------------------------
