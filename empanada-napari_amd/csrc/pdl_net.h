@@ -181,6 +181,11 @@ struct emp_pdl {
   std::map<std::string, W32> w32;
   std::map<std::string, std::pair<float*, size_t>> pool32;      // name -> (device buffer, floats)
   std::map<std::string, std::array<int, 4>> geom32;             // zero-tailed RegNet maps: the geometry a buffer was last cleared for
+  // every buffer the LAST forward of the fp32 / fp16x3 graph made, in the order made (emp_pdl_map32; run32 clears it).  kind says how
+  // N, H, W, C, ld are to be read: "map" NHWC rows of ld floats (fmt 1: hl32 rows, ld in channels); the others as include/empanada_hip.h lists them
+  struct Map32 { std::string name, kind; float* p = nullptr; int64_t N = 0, H = 0, W = 0, C = 0, ld = 0; int fmt = 0; };
+  std::vector<Map32> maps32;
+  std::map<std::string, size_t> maps32_at;      // name -> its place in maps32
 
   // device parameters
   std::map<std::string, DevConv> convs;

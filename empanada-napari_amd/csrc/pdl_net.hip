@@ -1596,4 +1596,14 @@ int emp_pdl_tap_raw(emp_pdl_t* net, const char* name, void** d_ptr, int64_t* byt
   return guarded("emp_pdl_tap_raw", [&] { return tap_raw(net, name, d_ptr, bytes); });
 }
 
+int emp_pdl_num_maps32(const emp_pdl_t* net) { return net ? (int)net->maps32.size() : 0; }
+int emp_pdl_map32(const emp_pdl_t* net, int i, const char** name, const char** kind, void** d_ptr, int64_t shape5[5], int* fmt) {
+  EMP_REQUIRE(net && name && kind && d_ptr && shape5 && fmt, "map32: null argument");
+  EMP_REQUIRE(i >= 0 && i < (int)net->maps32.size(), "map32: index %d out of range (%d buffers in the last forward)", i, (int)net->maps32.size());
+  const emp_pdl::Map32& m = net->maps32[i];
+  *name = m.name.c_str(); *kind = m.kind.c_str(); *d_ptr = m.p; *fmt = m.fmt;
+  shape5[0] = m.N; shape5[1] = m.H; shape5[2] = m.W; shape5[3] = m.C; shape5[4] = m.ld;
+  return EMP_OK;
+}
+
 }  // extern "C"

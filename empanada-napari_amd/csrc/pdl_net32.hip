@@ -31,6 +31,18 @@ int buf32(emp_pdl* n, const std::string& key, size_t floats, float** out) {
   return EMP_OK;
 }
 
+// the forward's record of a buffer it made (emp_pdl::maps32): a name made twice in one forward keeps its place, with the later geometry
+void note32(emp_pdl* n, const std::string& name, const char* kind, float* p, int64_t N, int64_t H, int64_t W, int64_t C, int64_t ld, int fmt = 0) {
+  auto at = n->maps32_at.find(name);
+  if (at == n->maps32_at.end()) {
+    n->maps32_at.emplace(name, n->maps32.size());
+    n->maps32.push_back({name, kind, p, N, H, W, C, ld, fmt});
+    return;
+  }
+  emp_pdl::Map32& m = n->maps32[at->second];
+  m.kind = kind; m.p = p; m.N = N; m.H = H; m.W = W; m.C = C; m.ld = ld; m.fmt = fmt;
+}
+
 int t32(emp_pdl* n, const std::string& key, int N, int H, int W, int C, T32* t) {
   t->N = N; t->H = H; t->W = W; t->C = C; t->ld = C;
   return buf32(n, key, (size_t)N * H * W * C, &t->p);
@@ -405,6 +417,7 @@ struct Fwd32 : Forward {
     int rc = t32(n, k, N, H_, W_, C_, &t);
     t.fmt = fmt;
     T[k] = t;
+    if (!rc) note32(n, k, "map", t.p, N, H_, W_, C_, t.ld, fmt);
     return rc;
   }
   int mkp(const std::string& k, int H_, int W_, int C_);
@@ -438,6 +451,7 @@ int Fwd32::mkp(const std::string& k, int H_, int W_, int C_) {
     n->geom32[k] = geo;
   }
   T[k] = t;
+  note32(n, k, "map", t.p, N, H_, W_, C_, t.ld);
   return EMP_OK;
 }
 
@@ -635,6 +649,7 @@ int Fwd32::deeplab_decoders() {
   const T32 p5 = A(pyr[4]);
   float* pooled;
   RC(buf32(n, "pooled", (size_t)N * p5.C, &pooled));
+  note32(n, "pooled", "pooled", pooled, N, 1, 1, p5.C, p5.C);
   if (p5.fmt) RC(launch_avgpool_hl32(reinterpret_cast<const half_t*>(p5.p), N, p5.H * p5.W, p5.C, p5.ld, pooled, s));
   else RC(launch_avgpool_f32(p5.p, N, p5.H * p5.W, p5.C, p5.ld, pooled, s));
   // plane region: the ASPP branches of both decoders merged, from the hl32 p5 into hl32 concat buffers
@@ -678,6 +693,8 @@ int Fwd32::deeplab_decoders() {
     float *poolfeat, *bias_n;
     RC(buf32(n, p + ".poolfeat", (size_t)N * n->aspp_ch, &poolfeat));
     RC(buf32(n, p + ".bias_n", (size_t)N * n->aspp_ch, &bias_n));
+    note32(n, p + ".poolfeat", "poolfeat", poolfeat, N, 1, 1, n->aspp_ch, n->aspp_ch);
+    note32(n, p + ".bias_n", "bias_n", bias_n, N, 1, 1, n->aspp_ch, n->aspp_ch);
     RC(launch_gemv(pooled, N, p5.C, n->f32w.at(p + ".pool.w"), nullptr, n->aspp_ch, 1, poolfeat, s));
     RC(launch_gemv(poolfeat, N, n->aspp_ch, n->f32w.at(p + ".projpool.w"), nullptr, n->aspp_ch, 0, bias_n, s));
     if (!merged && !small) {
@@ -727,6 +744,7 @@ int Fwd32::heads() {
     if (k == 1 && !interp) dst = o_ctr;
     if (k == 2 && !interp) dst = o_off;
     head_out[k] = dst;
+    note32(n, p + ".out", "out", dst, N, hq, wq, hc, hc);      // (where the forward wrote the head: the caller's tensor without interpolate_ins)
     // fp16x3 mode, round 6: depthwise + pointwise + ReLU + the head's 1x1 in one launch (sepconv_x3.hip, head_c <= 2); else the depthwise half
     bool fused = false;
     RC(sep(p + ".head.0.0.sepconv", xin, 5, ACT_RELU, p + ".dw", nullptr, n->f32w.at(p + ".head.1.w"), n->f32w.at(p + ".head.1.b"), hc, dst, &fused));
@@ -740,6 +758,7 @@ int Fwd32::heads() {
       const int tiles = conv16x3_cout_tiles(n->dec_ch);
       float* part;
       RC(buf32(n, p + ".part", (size_t)tiles * N * hq * wq * hc, &part));
+      note32(n, p + ".part", "part", part, N, hq, wq, hc, tiles);
       RC(c32(n, p + ".head.0.0.sepconv.1", A(p + ".dw"), 0, A(p + ".dw"), 0, s,
           {.act = ACT_RELU, .head_w = n->f32w.at(p + ".head.1.w"), .head_part = part, .head_c = hc}));
       RC(launch_head_finish_f32(part, tiles, N, hq * wq, hc, n->f32w.at(p + ".head.1.b"), dst, s));
@@ -771,19 +790,26 @@ int Fwd32::pointrend() {
   for (int st = 0; st < RS; ++st) plane_max *= 4;
   float* fkeys;
   RC(buf32(n, "pr.keys", (size_t)N * plane_max, &fkeys));
+  note32(n, "pr.keys", "pr.keys", fkeys, N, 1, plane_max, 1, 1);
   float* ftopk;
   const size_t topk_bytes = topk_work_bytes(N, plane_max);
   RC(buf32(n, "pr.topk", (topk_bytes + 3) / 4, &ftopk));
+  note32(n, "pr.topk", "pr.topk", ftopk, 1, 1, (int64_t)((topk_bytes + 3) / 4), 1, 1);
   float* fidx;
   RC(buf32(n, "pr.idx", (size_t)N * P, &fidx));
+  note32(n, "pr.idx", "pr.idx", fidx, N, 1, P, 1, 1);
   T32 X[2];
   for (int j = 0; j < 2; ++j) {
     X[j].N = 1; X[j].H = 1; X[j].W = N * P; X[j].C = ldp; X[j].ld = ldp;
     RC(buf32(n, j ? "pr.x1" : "pr.x0", (size_t)N * P * ldp, &X[j].p));
+    note32(n, j ? "pr.x1" : "pr.x0", "pr.x", X[j].p, 1, 1, (int64_t)N * P, ldp, ldp);
   }
   for (int st = 0; st < RS; ++st) {
     float* nxt = o_sem;
-    if (st + 1 < RS) RC(buf32(n, "pr.sem" + std::to_string(st), (size_t)N * n->ncls * hh * ww * 4, &nxt));
+    if (st + 1 < RS) {
+      RC(buf32(n, "pr.sem" + std::to_string(st), (size_t)N * n->ncls * hh * ww * 4, &nxt));
+      note32(n, "pr.sem" + std::to_string(st), "pr.sem", nxt, N, hh * 2, ww * 2, n->ncls, n->ncls);
+    }
     RC(launch_upsample2x_keys(cur, N, n->ncls, hh, ww, nxt, (uint32_t*)fkeys, s));
     hh *= 2; ww *= 2;
     const int64_t plane = (int64_t)hh * ww;
@@ -817,6 +843,8 @@ int run32(emp_pdl* n, const void* img, int dtype, float sub, float mul, int N, i
   EMP_REQUIRE(RS >= 1 && RS <= 6, "render_steps=%d out of range", RS);
   EMP_REQUIRE(c.arch == 0 || (H % 128 == 0 && W % 128 == 0), "BiFPN forward: H=%d W=%d must be multiples of 128", H, W);
   n->flops = 0.0;
+  n->maps32.clear();
+  n->maps32_at.clear();
   // (an encoder at output stride 32 -- the BiFPN networks -- has a quarter of those tiles in layer4: BiFPN-PR with the region on / off
   //  492 / 513 tiles/s at batch 8, 594 / 581 at 16, 651 / 631 at 32: its threshold is twice the stride-16 one)
   const bool hlr = n->precision == 2 && n->x3_planes_ready && c.encoder == 0 &&

@@ -190,6 +190,8 @@ class HipPanopticDeepLab:
                                                    int(render_steps), int(bool(interpolate_ins)), _abi.ptr(sem),
                                                    _abi.ptr(ctr), _abi.ptr(off), _abi.stream_ptr(self.device)),
                    'emp_pdl_forward')
+        if self.precision != 'fp16':
+            self._last_out = (sem, ctr, off)      # maps32() may point into them (kind 'out'): alive until the next forward
         return {'sem_logits': sem, 'ctr_hmp': ctr, 'offsets': off}
 
     def tap(self, name):
@@ -210,6 +212,60 @@ class HipPanopticDeepLab:
         assert t.numel() * 4 <= nb.value, (name, shape, nb.value)
         _abi.check(self.lib.emp_copy_d2d(_abi.ptr(t), p, t.numel() * 4, _abi.stream_ptr(self.device)), 'emp_copy_d2d')
         return t
+
+    def maps32(self):
+        """Every buffer the LAST forward of the fp32 / fp16x3 graph made, in the order made (``emp_pdl_map32``): an ordered dict
+        name -> dict(name, kind, ptr, N, H, W, C, ld, fmt); ``fmt`` 0 fp32, 1 hl32.  The kinds: include/empanada_hip.h."""
+        from collections import OrderedDict
+        out = OrderedDict()
+        for i in range(self.lib.emp_pdl_num_maps32(self._h)):
+            name, kind, p, fmt = C.c_char_p(), C.c_char_p(), C.c_void_p(), C.c_int()
+            shp = (C.c_int64 * 5)()
+            _abi.check(self.lib.emp_pdl_map32(self._h, i, C.byref(name), C.byref(kind), C.byref(p), shp, C.byref(fmt)), 'emp_pdl_map32')
+            N, H, W, Cc, ld = [int(v) for v in shp]
+            out[name.value.decode()] = dict(name=name.value.decode(), kind=kind.value.decode(), ptr=p.value, N=N, H=H, W=W, C=Cc, ld=ld,
+                                            fmt=fmt.value)
+        return out
+
+    def _read32(self, ptr, count, dtype=torch.float32):
+        t = torch.empty(count, dtype=dtype, device=self.device)
+        _abi.check(self.lib.emp_copy_d2d(_abi.ptr(t), C.c_void_p(ptr), t.numel() * t.element_size(), _abi.stream_ptr(self.device)),
+                   'emp_copy_d2d')
+        return t
+
+    def map32(self, rec, parts=False):
+        """A record of ``maps32()`` as a float64 CPU tensor: kind 'map' -> (N, C, H, W), the C written channels; the planes of
+        'out' / 'pr.sem' -> (N, C, H, W); 'pooled' / 'poolfeat' / 'bias_n' -> (N, C); 'part' -> (tiles, N, H * W, C); 'pr.x' ->
+        (rows, C); 'pr.keys' -> (N, W) int64 of the uint32 keys; 'pr.idx' -> (N, W) int64.  An hl32 map goes through
+        ``emp_hl32_to_f32``.  parts=True (maps only): -> (value, tail, halves) with tail the padding channels [C, ld) as
+        (N, ld - C, H, W) and halves the raw (hi, lo) fp16 pair of an hl32 map as (N, ld, H, W) each, None for an fp32 one."""
+        k, N, H, W, Cc, ld = rec['kind'], rec['N'], rec['H'], rec['W'], rec['C'], rec['ld']
+        if k == 'map':
+            rows = N * H * W
+            halves = None
+            if rec['fmt']:
+                raw = self._read32(rec['ptr'], rows * ld * 2, torch.float16).view(rows, ld // 32, 2, 32)
+                halves = tuple(raw[:, :, j].reshape(N, H, W, ld).permute(0, 3, 1, 2).cpu() for j in (0, 1))
+                t = torch.empty((rows, ld), dtype=torch.float32, device=self.device)
+                _abi.check(self.lib.emp_hl32_to_f32(C.c_void_p(rec['ptr']), _abi.ptr(t), rows, ld, ld, ld, _abi.stream_ptr(self.device)),
+                           'emp_hl32_to_f32')
+            else:
+                t = self._read32(rec['ptr'], rows * ld).view(rows, ld)
+            full = t.view(N, H, W, ld).permute(0, 3, 1, 2).double().cpu()
+            return (full[:, :Cc], full[:, Cc:], halves) if parts else full[:, :Cc]
+        assert not parts, 'parts=True is for maps'
+        if k in ('out', 'pr.sem'):
+            return self._read32(rec['ptr'], N * Cc * H * W).view(N, Cc, H, W).double().cpu()
+        if k in ('pooled', 'poolfeat', 'bias_n'):
+            return self._read32(rec['ptr'], N * Cc).view(N, Cc).double().cpu()
+        if k == 'part':
+            return self._read32(rec['ptr'], ld * N * H * W * Cc).view(ld, N, H * W, Cc).double().cpu()
+        if k == 'pr.x':
+            return self._read32(rec['ptr'], W * Cc).view(W, Cc).double().cpu()
+        if k in ('pr.keys', 'pr.idx'):
+            v = self._read32(rec['ptr'], N * W, torch.int32).view(N, W).cpu().to(torch.int64)
+            return v & 0xffffffff if k == 'pr.keys' else v
+        raise ValueError(f"map32: no tensor view of kind {k!r}")
 
     def tap_names(self):
         n = self.lib.emp_pdl_num_taps(self._h)

@@ -177,6 +177,22 @@ EMP_API int emp_pdl_num_taps(const emp_pdl_t* net);
  * PointRend subdivision starts from, (N,C,H/4,W/4); "ins_center.out", "ins_xy.out" when interpolate_ins): device
  * pointer + size in bytes */
 EMP_API int emp_pdl_tap_raw(emp_pdl_t* net, const char* name, void** d_ptr, int64_t* bytes);
+/* Parity/debug only, fp32 and fp16x3 modes: the buffers the LAST forward made, in the order it made them (the intermediate
+ * maps of QuantizablePanopticDeepLabPR.forward / QuantizablePanopticBiFPNPR.forward, quantization/panoptic_deeplab.py:194-250,
+ * panoptic_bifpn.py:147-161, which the reference never names; no reference counterpart).  emp_pdl_tap_raw serves a buffer by
+ * name whichever forward left it; this list holds what the last one wrote, with its geometry.  Entry i -> name, kind, device
+ * pointer, shape5 = {N, H, W, C, ld} and fmt (0 fp32, 1 hl32: csrc/conv16x3p.hip's hi / lo rows, ld in channels).  kind:
+ *   "map"                          NHWC rows of ld floats, C of them written; channels [C, ld) are padding that must read zero
+ *   "pooled" "poolfeat" "bias_n"   N rows of C floats
+ *   "out"                          a head's planes, NCHW (N, C, H, W) -- the pointer the forward WROTE: the caller's tensor for
+ *                                  ins_center / ins_xy without interpolate_ins
+ *   "part"                         the fused head's partial sums (ld cout tiles, N, H * W, C)
+ *   "pr.keys" (N, W) uint32, "pr.topk" W floats of scratch, "pr.idx" (N, W) int32, "pr.x" W rows of C floats: what the buffers
+ *             can hold -- a step whose plane or k is smaller packs its keys as (N, plane), its indices as (N, k), its rows N * k
+ *   "pr.sem"  NCHW (N, C, H, W) logits of an inner subdivision step
+ * The strings live until the next forward or emp_pdl_destroy.  emp_pdl_num_taps / emp_pdl_tap are unchanged. */
+EMP_API int emp_pdl_num_maps32(const emp_pdl_t* net);
+EMP_API int emp_pdl_map32(const emp_pdl_t* net, int i, const char** name, const char** kind, void** d_ptr, int64_t shape5[5], int* fmt);
 /* device-to-device copy on `stream` (lets a host language without a HIP binding read a tap) */
 EMP_API int emp_copy_d2d(void* d_dst, const void* d_src, size_t bytes, void* stream);
 EMP_API const char* emp_pdl_tap_name(const emp_pdl_t* net, int i);

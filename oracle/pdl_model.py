@@ -575,6 +575,18 @@ def _tf_sepconv(P, xin, pre, pad, precise, wsplit=False):
     return _tf_conv(P, dw, f'{pre}.sepconv.1', split=precise and wsplit and P[f'{pre}.sepconv.1'][0].shape[0] == 128)
 
 
+def resnet_blocks(stage4_stride):
+    """The ResNet-50 topology both teacher-forced walks share (resnet.py:217-229): for every bottleneck
+    (name, stride of its conv2 and shortcut, dilation, first of its layer, last of its layer); layer4 is dilated, not strided, at
+    output stride 16 (resnet.py:173-175)"""
+    for li, nblocks in enumerate(RESNET50_LAYERS, start=1):
+        stride, dil = (1 if li == 1 else 2), 1
+        if li == 4 and stage4_stride == 16:
+            stride, dil = 1, 2
+        for b in range(nblocks):
+            yield f'encoder.layer{li}.{b}', (stride if b == 0 else 1), dil, b == 0, b + 1 == nblocks
+
+
 def _tf_encoder(P, cfg, x, tap):
     """ResNet-50 part of the teacher-forced check (both network families); returns the pyramid's tap names.  A block's
     projection shortcut is part of its last launch (conv3 and the shortcut as one GEMM over the concatenated K: one rounding
@@ -589,26 +601,20 @@ def _tf_encoder(P, cfg, x, tap):
     yield 'p1', F.max_pool2d(F.relu(F.conv2d(x, w, b, 2, 3)), 3, 2, 1), True
     xname = 'p1'
     pyr = ['p1']
-    for li, nblocks in enumerate(RESNET50_LAYERS, start=1):
-        stride = 1 if li == 1 else 2
-        dil = 1
-        if li == 4 and cfg.get('stage4_stride', 32) == 16:
-            stride, dil = 1, 2
-        for bidx in range(nblocks):
-            pre = f'encoder.layer{li}.{bidx}'
-            s = stride if bidx == 0 else 1
-            xin = tap(xname)
-            yield pre + '.c1', F.relu(conv(xin, pre + '.conv1')), True
-            yield pre + '.c2', F.relu(conv(tap(pre + '.c1'), pre + '.conv2', s, dil, dil)), True
-            idn = xin
-            if bidx == 0 and fuse_ds:
-                idn = conv(xin, pre + '.downsample.0', s)
-            elif bidx == 0:
-                yield pre + '.ds', conv(xin, pre + '.downsample.0', s), True
-                idn = tap(pre + '.ds')
-            yield pre, F.relu(conv(tap(pre + '.c2'), pre + '.conv3') + idn), True
-            xname = pre
-        pyr.append(xname)
+    for pre, s, dil, first, last in resnet_blocks(cfg.get('stage4_stride', 32)):
+        xin = tap(xname)
+        yield pre + '.c1', F.relu(conv(xin, pre + '.conv1')), True
+        yield pre + '.c2', F.relu(conv(tap(pre + '.c1'), pre + '.conv2', s, dil, dil)), True
+        idn = xin
+        if first and fuse_ds:
+            idn = conv(xin, pre + '.downsample.0', s)
+        elif first:
+            yield pre + '.ds', conv(xin, pre + '.downsample.0', s), True
+            idn = tap(pre + '.ds')
+        yield pre, F.relu(conv(tap(pre + '.c2'), pre + '.conv3') + idn), True
+        xname = pre
+        if last:
+            pyr.append(xname)
     return pyr
 
 
@@ -714,3 +720,580 @@ def teacher_forced_layers_bifpn(P, cfg, x, tap):
     semx = tap('semantic_decoder.out')
     insx = tap('instance_decoder.out') if cfg['ins_decoder'] else semx
     yield from _tf_heads(P, semx, insx, tap, bool(cfg['ins_decoder']), ws, True)
+
+
+# ----------------------------------------------------------------------------
+# teacher-forced walk of the fp32 / fp16x3 graph (csrc/pdl_net32.hip run32)
+# ----------------------------------------------------------------------------
+def _up(c, m):
+    return (c + m - 1) // m * m
+
+
+def _g32_case(kernel, N, H, W, Cin, Cout, k=1, stride=1, pad=0, dil=1, act=1, res='', bias_n=False, out_fmt=0, **kw):
+    """the case dict tests/x3_range_case.py's ``reference`` and tests/layers_case.py's ``conv32_ref_bound`` take (``_c`` there)"""
+    d = dict(id='graph32', kernel=kernel, N=N, H=H, W=W, Cin=Cin, Cout=Cout, k=k, stride=stride, pad=pad, dil=dil, act=act, res=res,
+             bias_n=bias_n, out_fmt=out_fmt, wmode=0, Cin2=0, head_c=0, groups=1, cin_g=0, ksplit=False)
+    d.update(kw)
+    return d
+
+
+def _nhwc32(t, cpad=None):
+    """(N,C,H,W) tensor -> (N,H,W,C [zero-padded to cpad]) float32 numpy: the map as the kernel reads it (its values are fp32)"""
+    import numpy as np
+    a = t.permute(0, 2, 3, 1).contiguous().numpy().astype(np.float32)
+    if cpad is not None and cpad > a.shape[-1]:
+        a = np.concatenate([a, np.zeros(a.shape[:-1] + (cpad - a.shape[-1],), np.float32)], -1)
+    return a
+
+
+def _taps32(w, cpad=None):
+    """OIHW / OIW fp32 -> (O, kh*kw, I [zero-padded to cpad]) fp32: ``pack32``'s order"""
+    import numpy as np
+    w = np.asarray(w, np.float32)
+    if w.ndim == 3:
+        w = w[..., None]
+    O, I = w.shape[:2]
+    t = w.reshape(O, I, -1).transpose(0, 2, 1)
+    if cpad is not None and cpad > I:
+        t = np.concatenate([t, np.zeros((O, t.shape[1], cpad - I), np.float32)], -1)
+    return np.ascontiguousarray(t)
+
+
+def _act(y, act):
+    return F.relu(y) if act == 1 else _silu(y) if act == 2 else y
+
+
+def _pair(t):
+    """fp32 -> the value of its fp16 hi + lo pair (an hl32 map's content), in t's dtype"""
+    t32 = t.to(torch.float32)
+    hi = t32.to(torch.float16).to(torch.float32)
+    return (hi + (t32 - hi).to(torch.float16).to(torch.float32)).to(t.dtype)
+
+
+def g32_conv(x, w, b, dtype, family, stride=1, pad=0, dil=1, act=1, res=None, res_fmt=0, bias_n=None, x2=None, w2=None, stride2=1,
+             in_fmt=0, out_fmt=0, head=None, ps=False):
+    """One ``c32`` launch on the map x (N,C,H,W; the engine's own) -> (value (N,Cout,Ho,Wo) in ``dtype`` before any output
+    rounding, description).  w: OIHW fp32 as ``finalize32`` holds it (never fp16-rounded), b fp32.  x2 / w2: the K-concatenated
+    second source of ``conv3+ds`` (sampled with stride2).  head = (hw (hc, Cout), hb): the head's 1x1 in the epilogue.
+    ps: k2 s2 transposed convolution, w = (Cin, Cout, 2, 2) -> value (N, Cout, 2H, 2W)."""
+    import numpy as np
+    N, C, H, W = x.shape
+    if ps:
+        co = w.shape[1]
+        wq = np.asarray(w, np.float32).transpose(2, 3, 1, 0).reshape(4 * co, C, 1, 1)      # cout block q = dy * 2 + dx (pack32_convT)
+        bq = np.tile(np.asarray(b, np.float32), 4)
+        y, d = g32_conv(x, wq, bq, dtype, family, act=act, in_fmt=in_fmt, out_fmt=out_fmt)
+        y = y.view(N, 2, 2, co, H, W).permute(0, 3, 4, 1, 5, 2).reshape(N, co, 2 * H, 2 * W)
+        d['ps_cout'] = co
+        return y, d
+    w = np.asarray(w, np.float32)
+    if w.ndim == 3:
+        w = w[..., None]
+    Cout, Cin, k = w.shape[0], w.shape[1], w.shape[2]
+    c16 = _up(Cin, 16)
+    assert C >= Cin, (C, Cin)
+    xt = x[:, :Cin].to(dtype)
+    y = F.conv2d(xt, torch.from_numpy(w).to(dtype), None, stride, pad, dil)
+    p = dict(x=_nhwc32(x[:, :Cin], c16), w=_taps32(w, c16), b=np.asarray(b, np.float32))
+    case = _g32_case('hl32' if in_fmt else 'ex', N, H, W, c16, Cout, k, stride, pad, dil, act, out_fmt=out_fmt)
+    if x2 is not None:
+        w2 = np.asarray(w2, np.float32).reshape(Cout, -1)
+        c2 = _up(w2.shape[1], 16)
+        xs = x2[:, :, ::stride2, ::stride2]
+        y = y + F.conv2d(xs.to(dtype), torch.from_numpy(w2).to(dtype)[:, :, None, None])
+        p['x2'], p['w2'], case['Cin2'] = _nhwc32(xs, c2), _taps32(w2[:, :, None, None], c2)[:, 0], c2
+    y = y + torch.from_numpy(p['b']).to(dtype)[None, :, None, None]
+    if bias_n is not None:
+        y = y + bias_n.to(dtype)[:, :, None, None]
+        p['bn'], case['bias_n'] = bias_n.numpy().astype(np.float32), True
+    if res is not None:
+        y = y + res.to(dtype)
+        p['r'], case['res'] = _nhwc32(res), 'hl32' if res_fmt else 'f32'
+    y = _act(y, act)
+    if head is not None:
+        hw, hb = np.asarray(head[0], np.float32).reshape(-1, Cout), np.asarray(head[1], np.float32)
+        y = F.conv2d(_pair(y) if out_fmt else y, torch.from_numpy(hw).to(dtype)[:, :, None, None], torch.from_numpy(hb).to(dtype))
+        p['hw'], p['hb'], case['head_c'] = hw, hb, hw.shape[0]
+    return y, dict(kind='conv', family=family, case=case, p=p, in_fmt=in_fmt, out_fmt=out_fmt)
+
+
+def g32_depthwise(x, wdw, dtype, cpad=None):
+    """``launch_dwconv_f32``: depthwise k x k, pad k // 2, taps (C,1,k,k) fp32 [zero-padded to cpad channels] on all of x's channels"""
+    import numpy as np
+    wdw = np.asarray(wdw, np.float32)
+    C, k = x.shape[1], wdw.shape[2]
+    wt = np.zeros((C, 1, k, k), np.float32)
+    wt[:wdw.shape[0]] = wdw
+    y = F.conv2d(x.to(dtype), torch.from_numpy(wt).to(dtype), None, 1, k // 2, 1, C)
+    return y, dict(kind='dw', x=_nhwc32(x), taps=np.ascontiguousarray(wt.reshape(C, k * k).T), k=k)
+
+
+def g32_sep(x, wdw, wpw, b, dtype, act=1, head=None):
+    """the fused separable block (sepconv_x3.hip) on ALL of x's channels (the concat buffer's pad included: zero taps, zero
+    weights): depthwise k x k -> pointwise + bias -> act [-> head 1x1]"""
+    import numpy as np
+    N, C, H, W = x.shape
+    wdw, wpw = np.asarray(wdw, np.float32), np.asarray(wpw, np.float32).reshape(len(b), -1)
+    k, Cout = wdw.shape[2], wpw.shape[0]
+    wt = np.zeros((C, 1, k, k), np.float32)
+    wt[:wdw.shape[0]] = wdw
+    pw = np.zeros((Cout, C), np.float32)
+    pw[:, :wpw.shape[1]] = wpw
+    d = F.conv2d(x.to(dtype), torch.from_numpy(wt).to(dtype), None, 1, k // 2, 1, C)
+    y = _act(F.conv2d(d, torch.from_numpy(pw).to(dtype)[:, :, None, None], torch.from_numpy(np.asarray(b, np.float32)).to(dtype)), act)
+    p = dict(x=_nhwc32(x), dw=np.ascontiguousarray(wt.reshape(C, k * k).T), pw=pw, b=np.asarray(b, np.float32))
+    case = _g32_case('sep', N, H, W, C, Cout, k, act=act)
+    if head is not None:
+        hw, hb = np.asarray(head[0], np.float32).reshape(-1, Cout), np.asarray(head[1], np.float32)
+        y = F.conv2d(y, torch.from_numpy(hw).to(dtype)[:, :, None, None], torch.from_numpy(hb).to(dtype))
+        p['hw'], p['hb'], case['head_c'] = hw, hb, hw.shape[0]
+    return y, dict(kind='sep', family='x3', case=case, p=p, in_fmt=0, out_fmt=0)
+
+
+class Graph32Walk:
+    """The forward of ``run32`` (csrc/pdl_net32.hip) map by map ON THE ENGINE'S OWN INPUTS, for both precisions of that graph.
+
+    ``has(name)`` / ``fmt(name)``: whether the forward made the buffer ``name`` and its format (0 fp32, 1 hl32) -- what
+    ``HipPanopticDeepLab.maps32()`` lists; the schedule's decisions (fused stem, ``conv3+ds``, the plane region, fused separable
+    blocks, the three head routes) are read off that list, not off the environment.  ``get(name)``: the engine's buffer as
+    ``map32`` returns it (a map: (N,C,H,W) float64, an hl32 map as hi + lo).  ``walk()`` yields
+    ``(name, value, description)``: value is the expectation in ``dtype`` (float64; float32 computes a CPU stand-in of the
+    engine) of the channels ``description['channels']`` (all of them when absent) of buffer ``name`` BEFORE an hl32 output's
+    rounding, from operands as ``finalize32`` packs them (fp32 weights and biases, the summed bias of ``conv3+ds``);
+    the description names the launch -- kind, and what its bound is built from, in the layouts of tests/x3_range_case.py and
+    tests/layers_case.py.  The caller must have stored the value (stand-in) before it asks for the next one.
+    Outputs of the forward are asked from ``get`` under 'sem_logits', 'ctr_hmp', 'offsets'."""
+
+    def __init__(self, P, cfg, image, has, fmt, get, precision, render_steps=2, interpolate_ins=False, dtype=torch.float64):
+        self.P, self.cfg, self.image, self.has, self.fmt, self.get = P, cfg, image, has, fmt, get
+        self.x3 = precision == 'fp16x3'
+        self.family = 'x3' if self.x3 else 'f32'
+        self.RS, self.interp, self.dtype = render_steps, interpolate_ins, dtype
+        self.N, self.H, self.W = image['x'].shape[0], image['H'], image['W']
+
+    # ---- helpers ----
+    def conv(self, name, src, out, **kw):
+        w, b = self.P[name]
+        kw.setdefault('in_fmt', self.fmt(src))
+        kw.setdefault('out_fmt', self.fmt(out))
+        return g32_conv(self.get(src), w, b, self.dtype, self.family, **kw)
+
+    def sepblock(self, pre, src, dwname, outname, act, head=None):
+        """``Fwd32::sep``: fused where the forward made no ``dwname`` buffer"""
+        wdw, (wpw, b) = self.P[pre + '.sepconv.0'][0], self.P[pre + '.sepconv.1']
+        if not self.has(dwname):
+            y, d = g32_sep(self.get(src), wdw, wpw, b, self.dtype, act, head)
+            yield outname, y, d
+            return
+        y, d = g32_depthwise(self.get(src), wdw, self.dtype)
+        yield dwname, y, d
+        if head is None:
+            xin = self.get(dwname)      # every channel of the buffer: the pointwise weights are packed for its width
+            y, d = g32_conv(xin, self._padw(wpw, xin.shape[1]), b, self.dtype, self.family, act=act)
+            yield outname, y, d
+
+    @staticmethod
+    def _padw(w, C):
+        import numpy as np
+        w = np.asarray(w, np.float32).reshape(w.shape[0], -1)
+        out = np.zeros((w.shape[0], C, 1, 1), np.float32)
+        out[:, :w.shape[1], 0, 0] = w
+        return out
+
+    # ---- the graph ----
+    def walk(self):
+        if str(self.cfg.get('encoder', 'resnet50')).startswith('regnet'):
+            pyr = yield from self.regnet()
+        else:
+            pyr = yield from self.resnet()
+        if 'BiFPN' in self.cfg.get('arch', ''):
+            dec_out = yield from self.bifpn(pyr)
+        else:
+            dec_out = yield from self.deeplab(pyr)
+        yield from self.heads(dec_out)
+        yield from self.pointrend(dec_out[0])
+
+    def regnet(self):
+        """regnet.py:160-166.  Every map sits in rows of round_up(C, 16) + 16 floats whose tail is zero: a consumer reads its input
+        channels padded to 16 (from a group's first channel in the grouped 3x3) and meets zeros there."""
+        import numpy as np
+        P, lay = self.P, self.cfg['regnet']
+        w, b = P['encoder.stem.cbr.0']
+        sd = dict(image=self.image, H=self.H, W=self.W, taps=np.ascontiguousarray(np.asarray(w, np.float32).reshape(w.shape[0], -1).T),
+                  b=np.asarray(b, np.float32), k=3)
+        yield 'stem', self.stem_value(w, b, 3, 1), dict(kind='stem', **sd)
+        xname, pyr = 'stem', ['stem']
+        strides = lay.get('strides', [2, 2, 2, 2])
+        for si, (dep, g) in enumerate(zip(lay['depths'], lay['groups']), start=1):
+            for bi in range(1, dep + 1):
+                pre = f'encoder.stage{si}.block{bi}'
+                s = strides[si - 1] if bi == 1 else 1
+                yield (pre + '.a',) + self.conv(pre + '.bottleneck.a.0', xname, pre + '.a')
+                yb, db = self.grouped(pre + '.bottleneck.b.0', self.get(pre + '.a'), g, s)
+                if lay['use_se']:
+                    # x * sigmoid(W2 relu(W1 x)) per pixel (blocks.py:35-50), the gate applied IN PLACE: the ungated map is gone when
+                    # the forward ends, so se1 is forced through it (kind 'conv_prop': its own bound plus the grouped launch's
+                    # through |W1|) and the gated map is the grouped launch's expectation times the engine's own gate ('conv_gated')
+                    w1, b1 = P[pre + '.bottleneck.se.se.0']
+                    xb = yb.to(torch.float32).to(self.dtype)
+                    y1, d1 = g32_conv(xb, w1, b1, self.dtype, self.family)
+                    yield pre + '.se1', y1, dict(kind='conv_prop', inner=d1, upstream=db, w=np.asarray(w1, np.float32).reshape(w1.shape[0], -1))
+                    yield (pre + '.se2',) + self.conv(pre + '.bottleneck.se.se.2', pre + '.se1', pre + '.se2', act=0)
+                    gate = self.get(pre + '.se2')
+                    yield pre + '.b', yb * torch.sigmoid(gate.to(self.dtype)), dict(kind='conv_gated', inner=db, gate=gate.numpy().astype(np.float32))
+                else:
+                    yield pre + '.b', yb, db
+                idn = xname
+                if f'{pre}.downsample.conv.0' in P:
+                    yield (pre + '.ds',) + self.conv(pre + '.downsample.conv.0', xname, pre + '.ds', stride=s, act=0)
+                    idn = pre + '.ds'
+                yield (pre,) + self.conv(pre + '.bottleneck.c.0', pre + '.b', pre, res=self.get(idn))
+                xname = pre
+            pyr.append(xname)
+        return pyr
+
+    def grouped(self, name, x, g, stride):
+        """the grouped 3x3 of a RegNet block: per group Cin = the group's width padded to 16 (the extra channels are the next
+        group's, or the row's zero tail, under zero weights)"""
+        import numpy as np
+        w, b = self.P[name]
+        w = np.asarray(w, np.float32)
+        N, C, H, W = x.shape
+        wg = w.shape[1]
+        c16 = _up(wg, 16)
+        y = _act(F.conv2d(x.to(self.dtype), _t(w).to(self.dtype), _t(np.asarray(b, np.float32)).to(self.dtype), stride, 1, 1, g), 1)
+        case = _g32_case('nhwc', N, H, W, c16, w.shape[0] // g, 3, stride, 1, 1, 1, groups=g, cin_g=wg)
+        p = dict(x=_nhwc32(x, (g - 1) * wg + c16), w=_taps32(w, c16), b=np.asarray(b, np.float32))
+        return y, dict(kind='conv', family=self.family, case=case, p=p, in_fmt=0, out_fmt=0)
+
+    def fuse_coefs(self, name):
+        """``set_fusew`` in its own fp32 arithmetic: relu(w) / (sum + eps)"""
+        import numpy as np
+        w = np.maximum(np.asarray(self.P[name][0], np.float32), np.float32(0))
+        s = np.float32(0)
+        for v in w:
+            s = np.float32(s + v)
+        return [np.float32(v / np.float32(s + np.float32(1e-4))) for v in w]
+
+    def bifpn(self, pyr):
+        """bifpn.py:185-236 as ``Fwd32::bifpn_decoders`` names it"""
+        import numpy as np
+        P, cfg, dt = self.P, self.cfg, self.dtype
+        pyr = list(pyr)
+        for li in (3, 4):      # the plane region's P4 / P5 as fp32 copies for the 128-channel nodes
+            if self.has(pyr[li] + '.f32'):
+                yield pyr[li] + '.f32', self.get(pyr[li]).to(dt), dict(kind='exact')
+                pyr[li] = pyr[li] + '.f32'
+        yield ('p2f',) + self.conv('p2_resample.conv.0', pyr[1], 'p2f', act=0)
+        e4 = np.float32(1e-4)
+        outs = []
+        for d in ['semantic'] + (['instance'] if cfg['ins_decoder'] else []):
+            fp = f'{d}_fpn'
+            yield (fp + '.p6pre',) + self.conv(fp + '.p6_resample.conv.0', pyr[4], fp + '.p6pre', act=0)
+            yield fp + '.in.P6', F.max_pool2d(self.get(fp + '.p6pre').to(dt), 3, 2, 1), dict(kind='exact')
+            yield fp + '.in.P7', F.max_pool2d(self.get(fp + '.in.P6').to(dt), 3, 2, 1), dict(kind='exact')
+            feat = [pyr[2], pyr[3], pyr[4], fp + '.in.P6', fp + '.in.P7']
+            for li in range(cfg['fpn_layers']):
+                pre, L = f'{fp}.bifpns.{li}', f'{fp}.l{li}'
+                new = [None] * 5
+                for up in (0, 1):
+                    dp = pre + ('.bottom_up_fpn' if up else '.top_down_fpn')
+                    w = self.fuse_coefs(dp + '.weights')
+                    prev = L + '.P3.td' if up else feat[4]
+                    if up:
+                        new[0] = prev
+                    for i in range(4):
+                        lv = i + 1 if up else 3 - i
+                        q = f'{L}.P{3 + lv}'
+                        out = q + ('.bu' if up else '.td')
+                        inn = feat[lv]
+                        rk = f'{dp}.resamplings.{i}.conv.0'
+                        if rk in P:
+                            dst = q + ('.rbu' if up else '.rtd')
+                            yield (dst,) + self.conv(rk, feat[lv], dst, act=0)
+                            inn = dst
+                        if up and i < 3:
+                            den = np.float32(np.float32(np.float32(w[i] + w[i + 1]) + w[i + 2]) + e4)
+                            coef, cname = [np.float32(w[i] / den), np.float32(w[i + 1] / den), np.float32(w[i + 2] / den)], q + '.td'
+                        else:
+                            den = np.float32(np.float32(w[i] + w[i + 1]) + e4)
+                            coef, cname = [np.float32(w[i] / den), np.float32(w[i + 1] / den), np.float32(0)], None
+                        a, bm = self.get(prev), self.get(inn)
+                        cm = self.get(cname) if cname else None
+                        ra = F.max_pool2d(a.to(dt), 3, 2, 1) if up else a.to(dt).repeat_interleave(2, 2).repeat_interleave(2, 3)
+                        v = float(coef[0]) * ra + float(coef[1]) * bm.to(dt)
+                        if cm is not None:
+                            v = v + float(coef[2]) * cm.to(dt)
+                        fz = q + ('.bun.fz' if up else '.tdn.fz')
+                        yield fz, v, dict(kind='fuse', a=_nhwc32(a), b=_nhwc32(bm), c=None if cm is None else _nhwc32(cm),
+                                          coef=np.array(coef, np.float32), mode=up)
+                        yield from self.sepblock(dp + '.after_combines.0.0', fz, q + ('.bun.dw' if up else '.tdn.dw'), out, 2)
+                        prev = out
+                        if up:
+                            new[lv] = prev
+                feat = new
+            dp = f'{d}_decoder'
+            skips = [feat[3], feat[2], feat[1], feat[0], 'p2f']
+            xx = feat[4]
+            Fd = P[f'{dp}.upsamplings.0.0'][0].shape[1]
+            for i in range(5):
+                w, b = P[f'{dp}.upsamplings.{i}.0']
+                cn = f'{dp}.cat{i}'
+                y, dsc = g32_conv(self.get(xx), w, b, dt, self.family, act=1, ps=True)
+                dsc['channels'] = (0, Fd)
+                yield cn, y, dsc
+                yield cn, self.get(skips[i]).to(dt), dict(kind='exact', channels=(Fd, 2 * Fd))
+                xx = cn
+            yield from self.sepblock(f'{dp}.fusion.0', xx, dp + '.dw', dp + '.out', 1)
+            outs.append(dp + '.out')
+        return outs if len(outs) == 2 else [outs[0], outs[0]]
+
+    def stem_value(self, w, b, k, pad):
+        im = self.image
+        x = torch.zeros((self.N, 1, self.H, self.W), dtype=self.dtype)
+        x[:, 0, :im['x'].shape[1], :im['x'].shape[2]] = im['x'].to(self.dtype)      # normalised, THEN zero-padded
+        return F.relu(F.conv2d(x, _t(w).to(self.dtype), _t(b).to(self.dtype), 2, pad))
+
+    def resnet(self):
+        import numpy as np
+        P, cfg = self.P, self.cfg
+        w, b = P['encoder.conv1']
+        sd = dict(image=self.image, H=self.H, W=self.W, taps=np.ascontiguousarray(np.asarray(w, np.float32).reshape(w.shape[0], -1).T),
+                  b=np.asarray(b, np.float32), k=7)
+        st = self.stem_value(w, b, 7, 3)
+        if self.has('stem'):
+            yield 'stem', st, dict(kind='stem', **sd)
+            yield 'p1', F.max_pool2d(self.get('stem').to(self.dtype), 3, 2, 1), dict(kind='exact')
+        else:
+            yield 'p1', F.max_pool2d(st, 3, 2, 1), dict(kind='stem_pool', **sd)
+        xname, pyr = 'p1', ['p1']
+        s4 = 32 if 'BiFPN' in cfg.get('arch', '') else cfg.get('stage4_stride', 32)      # (the BiFPN models build their encoder at stride 32)
+        for pre, s, dil, first, last in resnet_blocks(s4):
+            yield (pre + '.c1',) + self.conv(pre + '.conv1', xname, pre + '.c1')
+            yield (pre + '.c2',) + self.conv(pre + '.conv2', pre + '.c1', pre + '.c2', stride=s, pad=dil, dil=dil)
+            if first and not self.has(pre + '.ds'):
+                # conv3 and the shortcut as one convolution over the concatenated K, the two folded biases summed in fp32
+                (w3, b3), (wd, bd) = P[pre + '.conv3'], P[pre + '.downsample.0']
+                yield (pre,) + g32_conv(self.get(pre + '.c2'), w3, np.asarray(b3, np.float32) + np.asarray(bd, np.float32), self.dtype,
+                                       self.family, x2=self.get(xname), w2=wd, stride2=s, in_fmt=self.fmt(pre + '.c2'),
+                                       out_fmt=self.fmt(pre))
+            else:
+                idn = xname
+                if first:
+                    yield (pre + '.ds',) + self.conv(pre + '.downsample.0', xname, pre + '.ds', stride=s, act=0)
+                    idn = pre + '.ds'
+                yield (pre,) + self.conv(pre + '.conv3', pre + '.c2', pre, res=self.get(idn), res_fmt=self.fmt(idn))
+            xname = pre
+            if last:
+                pyr.append(xname)
+        return pyr
+
+    def deeplab(self, pyr):
+        import numpy as np
+        P, cfg, dt = self.P, self.cfg, self.dtype
+        p5n = pyr[4]
+        p5 = self.get(p5n)
+        N, C5, h5, w5 = p5.shape
+        yield 'pooled', p5.to(dt).mean((2, 3)), dict(kind='avgpool', x=_nhwc32(p5).reshape(N, h5 * w5, C5), hl32=bool(self.fmt(p5n)))
+        src = p5n
+        if self.has('p5.hl32'):      # below the plane region's threshold: the merged K-split branches read an hl32 copy of p5
+            yield 'p5.hl32', _pair(p5.to(dt)), dict(kind='exact')
+            src = 'p5.hl32'
+        decs = ['semantic_decoder'] + (['instance_decoder'] if cfg['ins_decoder'] else [])
+        A = P['semantic_decoder.aspp.convs.0.0'][0].shape[0]
+        dec_ch = P['semantic_decoder.fuse.0.0.sepconv.1'][0].shape[0]
+        rates = cfg['atrous_rates']
+        # the branches of both decoders first (merged launches), as run32 orders them when it merges; the order of the yields
+        # only matters to a stand-in, which stores every value before the next is computed
+        outs = []
+        for d in decs:
+            a = f'{d}.aspp'
+            wp, bp = P[f'{a}.convs.4.aspp_pooling.1']
+            assert not np.any(np.asarray(bp)), 'the pooling branch has no bias in the reference (aspp.py:45-48): the engine holds none'
+            pooled = self.get('pooled')
+            wp2 = np.asarray(wp, np.float32).reshape(A, -1)
+            yield f'{d}.poolfeat', F.relu(pooled.to(dt) @ torch.from_numpy(wp2).to(dt).T), dict(
+                kind='gemv', x=pooled.numpy().astype(np.float32), w=wp2, b=None, relu=True)
+            wj, bj = P[f'{a}.project.0']
+            wj = np.asarray(wj, np.float32).reshape(A, 5 * A)
+            pf = self.get(f'{d}.poolfeat')
+            tail = np.ascontiguousarray(wj[:, 4 * A:])
+            yield f'{d}.bias_n', pf.to(dt) @ torch.from_numpy(tail).to(dt).T, dict(
+                kind='gemv', x=pf.numpy().astype(np.float32), w=tail, b=None, relu=False)
+            for i in range(4):
+                r = rates[i - 1] if i else 1
+                y, dsc = self.conv(f'{a}.convs.{i}.0', src, f'{a}.cat', pad=r if i else 0, dil=r)
+                dsc['channels'] = (i * A, (i + 1) * A)
+                yield f'{a}.cat', y, dsc
+            y, dsc = g32_conv(self.get(f'{a}.cat'), np.ascontiguousarray(wj[:, :4 * A])[:, :, None, None], bj, dt, self.family,
+                              bias_n=self.get(f'{d}.bias_n'), in_fmt=self.fmt(f'{a}.cat'), out_fmt=self.fmt(a))
+            yield a, y, dsc
+            xx, xch = a, A
+            for i, stage in enumerate(cfg['low_level_stages']):
+                q = f'{d}.stage{i}'
+                lown = pyr[stage]
+                low = self.get(lown)
+                lp = P[f'{d}.project.{i}.0'][0].shape[0]
+                cpad = _up(xch + lp, 32 if self.x3 else 16)
+                xa = self.get(xx)[:, :xch]
+                hh, ww = low.shape[2:]
+                if tuple(xa.shape[2:]) == (hh, ww):
+                    yield q + '.cat', xa.to(dt), dict(kind='exact', channels=(0, xch))
+                else:
+                    yield q + '.cat', F.interpolate(xa.to(dt), size=(hh, ww), mode='bilinear', align_corners=True), dict(
+                        kind='bilinear', x=_nhwc32(xa), H=hh, W=ww, channels=(0, xch))
+                y, dsc = self.conv(f'{d}.project.{i}.0', lown, q + '.cat')
+                dsc['channels'] = (xch, xch + lp)
+                yield q + '.cat', y, dsc
+                if cpad > xch + lp:
+                    yield q + '.cat', torch.zeros((N, cpad - xch - lp, hh, ww), dtype=dt), dict(kind='zero', channels=(xch + lp, cpad))
+                yield from self.sepblock(f'{d}.fuse.{i}.0', q + '.cat', q + '.dw', q + '.out', 1)
+                xx, xch = q + '.out', dec_ch
+            outs.append(xx)
+        return outs if len(outs) == 2 else [outs[0], outs[0]]
+
+    def heads(self, dec_out):
+        import numpy as np
+        P, dt = self.P, self.dtype
+        for k, p in enumerate(('semantic_head', 'ins_center', 'ins_xy')):
+            xin = dec_out[0 if k == 0 else 1]
+            hw, hb = P[p + '.head.1']
+            hw = np.asarray(hw, np.float32).reshape(hw.shape[0], -1)
+            pre = p + '.head.0.0'
+            if not self.has(p + '.dw'):
+                yield from self.sepblock(pre, xin, p + '.dw', p + '.out', 1, head=(hw, hb))
+                continue
+            yield from self.sepblock(pre, xin, p + '.dw', None, 1, head=(hw, hb))
+            wpw, b = P[pre + '.sepconv.1']
+            dwmap = self.get(p + '.dw')
+            if self.has(p + '.part'):
+                # the head's 1x1 in the pointwise conv's epilogue: per cout tile the partial sums, then their sum in ascending order
+                dec = wpw.shape[0]
+                tiles, tw = ((dec + 127) // 128, 128) if dec > 64 else (1, dec)      # conv16x3_cout_tiles: tiles of 128 couts
+                N, _, hq, wq = dwmap.shape
+                vals, descs = [], []
+                for t in range(tiles):
+                    sl = slice(t * tw, min(dec, (t + 1) * tw))
+                    y, dsc = g32_conv(dwmap, np.asarray(wpw, np.float32)[sl], np.asarray(b, np.float32)[sl], dt, self.family,
+                                      head=(hw[:, sl], np.zeros(hw.shape[0], np.float32)))
+                    vals.append(y.permute(0, 2, 3, 1).reshape(N, hq * wq, -1))
+                    descs.append(dsc)
+                yield p + '.part', torch.stack(vals), dict(kind='tiles', tiles=descs)
+                part = self.get(p + '.part')                                # (tiles, N, H * W, hc)
+                assert part.shape[0] == tiles, (part.shape, tiles)
+                yield p + '.out', (part.to(dt).sum(0) + _t(np.asarray(hb, np.float32)).to(dt)).view(N, hq, wq, -1).permute(0, 3, 1, 2), dict(
+                    kind='head_finish', part=part.numpy().astype(np.float32).reshape(tiles, N * hq * wq, -1), b=np.asarray(hb, np.float32))
+            else:
+                y, dsc = g32_conv(dwmap, wpw, b, dt, self.family)
+                yield p + '.pw', y, dsc
+                pw = self.get(p + '.pw')
+                N, Cc, hq, wq = pw.shape
+                rows = pw.permute(0, 2, 3, 1).reshape(-1, Cc)
+                yield p + '.out', (rows.to(dt) @ _t(hw).to(dt).T + _t(np.asarray(hb, np.float32)).to(dt)).view(N, hq, wq, -1).permute(0, 3, 1, 2), dict(
+                    kind='head1x1', rows=rows.numpy().astype(np.float32), w=hw, b=np.asarray(hb, np.float32))
+        if self.interp:
+            for p, out in (('ins_center', 'ctr_hmp'), ('ins_xy', 'offsets')):
+                v = self.get(p + '.out')
+                yield out, F.interpolate(v.to(dt), scale_factor=4.0, mode='bilinear', align_corners=True), dict(
+                    kind='bilinear', x=_nhwc32(v), H=4 * v.shape[2], W=4 * v.shape[3])
+
+    def point_chain(self, semx, coarse, idx, hh, ww, layers):
+        """the point rows of the cells idx (N, k) of an hh x ww grid through sampling and the first `layers` fc layers, in
+        float64 from fp32 operands at every stage -> (rows (N * k, ldp), the stages' descriptions)"""
+        import numpy as np
+        P, dt = self.P, self.dtype
+        N, k = idx.shape
+        ncls, Cf = coarse.shape[1], semx.shape[1]
+        ldp = _up(Cf + ncls, 16)
+        coords = torch.zeros(N, k, 2, dtype=torch.float)
+        coords[:, :, 0] = 0.5 * (1.0 / float(ww)) + (1.0 / float(ww)) * (idx % ww).float()
+        coords[:, :, 1] = 0.5 * (1.0 / float(hh)) + (1.0 / float(hh)) * torch.div(idx, ww, rounding_mode='floor').float()
+        fine = point_sample(semx.to(dt), coords.to(dt)).permute(0, 2, 1).reshape(N * k, Cf)
+        cs = point_sample(coarse.to(dt), coords.to(dt)).permute(0, 2, 1).reshape(N * k, ncls)
+        xr = torch.cat([fine, cs, torch.zeros(N * k, ldp - Cf - ncls, dtype=dt)], 1)
+        stages = [dict(kind='sample', feat=_nhwc32(semx), C=Cf, coarse=coarse.numpy().astype(np.float32), idx=idx.numpy().astype(np.int32),
+                       H2=hh, W2=ww, ld=ldp, channels=(0, ldp))]
+        for f in range(layers):
+            w, b = P[f'semantic_pr.point_head.fc_layers.{f}.0']
+            wf = np.zeros((w.shape[0], ldp, 1, 1), np.float32)
+            wf[:, :w.shape[1], 0, 0] = np.asarray(w, np.float32).reshape(w.shape[0], -1)
+            xr = xr.to(torch.float32).to(dt)      # (each stage is described at fp32 operands)
+            y, dsc = g32_conv(xr.T.reshape(1, ldp, 1, N * k), wf, b, dt, self.family)
+            dsc.update(rows=N * k, w=wf[:, :, 0, 0])
+            stages.append(dsc)
+            xr = torch.cat([y.view(Cf, N * k).T, xr[:, Cf:]], 1)
+        return xr, stages
+
+    def pointrend(self, semx_name):
+        """point_rend.py:241-269 (eval).  Every step's buffers are overwritten by the next, so only the LAST step can be forced on
+        the engine's own rows and indices: the selection (every selected key <= every unselected one), the coarse columns of both
+        row buffers, the last fc layer from the row buffer that holds its input, the predictor at the cells of ``pr.idx`` and
+        the plain 2x up-sampling everywhere else.  An earlier step leaves ``pr.sem<k>`` alone: it is the up-sampling of its
+        input except at no more than k cells (description kind 'upsample_but'), and those hold the point head's logits of
+        their cell within the bound composed over all its layers -- three times through |w|, so a loose one.  The tight check
+        of a step is the walk in which it is the last one (render_steps 1 for step 0)."""
+        import numpy as np
+        P, cfg, dt = self.P, self.cfg, self.dtype
+        coarse = self.get('semantic_head.out')
+        semx = self.get(semx_name)
+        N, ncls, hq, wq = coarse.shape
+        Cf = semx.shape[1]
+        ldp = _up(Cf + ncls, 16)
+        npts, num_fc = cfg['subdivision_num_points'], cfg['num_fc']
+        cur, hh, ww = 'semantic_head.out', hq, wq
+        for st in range(self.RS):
+            last = st + 1 == self.RS
+            target = 'sem_logits' if last else f'pr.sem{st}'
+            src = self.get(cur)
+            up = F.interpolate(src.to(dt), scale_factor=2.0, mode='bilinear', align_corners=False)
+            hh, ww = 2 * hh, 2 * ww
+            plane = hh * ww
+            k = min(plane, npts)
+            if not last:
+                # the indices of an inner step are gone when the forward ends: every cell is either the plain up-sampling or the point
+                # head's logits AT THAT CELL (sampling, every fc layer, predictor, forced from the engine's feature map and coarse
+                # logits: kind 'chain' and the predictor's bound; loose after three layers), and at most k cells are the latter
+                allidx = torch.arange(plane).unsqueeze(0).expand(N, -1)
+                xr, stages = self.point_chain(semx, coarse, allidx, hh, ww, num_fc)
+                wpr, bpr = P['semantic_pr.point_head.predictor']
+                wpad = np.zeros((ncls, ldp), np.float32)
+                wpad[:, :wpr.shape[1]] = np.asarray(wpr, np.float32).reshape(ncls, -1)
+                yield target, up, dict(kind='upsample_but', x=src.numpy().astype(np.float32), k=k, plane=plane, stages=stages, w=wpad,
+                                       b=np.asarray(bpr, np.float32))
+                cur = target
+                continue
+            # (both buffers are packed for the step: k indices and `plane` keys per image, whatever the buffers could hold)
+            idx = self.get('pr.idx').reshape(-1)[:N * k].view(N, k)
+            keys = self.get('pr.keys').reshape(-1)[:N * plane].view(N, plane)
+            yield 'pr.idx', idx, dict(kind='selection', keys=keys.numpy(), k=k, plane=plane, out=target)
+            # rows [Cf features | ncls coarse | 0]: the coarse columns and the pad survive every fc layer in both buffers
+            fin, other = ('pr.x1', 'pr.x0') if num_fc % 2 else ('pr.x0', 'pr.x1')      # fc f reads X[f % 2] and writes X[(f + 1) % 2]
+            sample = dict(kind='sample', feat=_nhwc32(semx), C=Cf, coarse=coarse.numpy().astype(np.float32), idx=idx.numpy().astype(np.int32),
+                          H2=hh, W2=ww, ld=ldp)
+            coords = torch.zeros(N, k, 2, dtype=torch.float)
+            coords[:, :, 0] = 0.5 * (1.0 / float(ww)) + (1.0 / float(ww)) * (idx % ww).float()
+            coords[:, :, 1] = 0.5 * (1.0 / float(hh)) + (1.0 / float(hh)) * torch.div(idx, ww, rounding_mode='floor').float()
+            cs = point_sample(coarse.to(dt), coords.to(dt)).permute(0, 2, 1).reshape(N * k, ncls)
+            for buf in (other, fin):
+                yield buf, torch.cat([cs, torch.zeros(N * k, ldp - Cf - ncls, dtype=dt)], 1), dict(sample, channels=(Cf, ldp), rows=N * k)
+            if num_fc >= 2:
+                # the feature columns of the buffer the last fc layer reads: the sampled rows are overwritten by then, so they are
+                # forced from the engine's feature map and indices through sampling and the first num_fc - 1 layers (kind 'chain':
+                # each stage's own bound plus the bound so far through |w|)
+                xr, stages = self.point_chain(semx, coarse, idx, hh, ww, num_fc - 1)
+                yield other, xr[:, :Cf], dict(kind='chain', stages=stages, channels=(0, Cf), rows=N * k)
+                w, b = P[f'semantic_pr.point_head.fc_layers.{num_fc - 1}.0']
+                rows = self.get(other)[:N * k]
+                wq_ = np.zeros((w.shape[0], ldp, 1, 1), np.float32)
+                wq_[:, :w.shape[1], 0, 0] = np.asarray(w, np.float32).reshape(w.shape[0], -1)
+                y, dsc = g32_conv(rows.T.reshape(1, ldp, 1, N * k), wq_, b, dt, self.family)
+                dsc.update(channels=(0, Cf), rows=N * k)
+                yield fin, y.view(Cf, N * k).T, dsc
+            wpr, bpr = P['semantic_pr.point_head.predictor']
+            wpr = np.asarray(wpr, np.float32).reshape(ncls, -1)
+            wpad = np.zeros((ncls, ldp), np.float32)
+            wpad[:, :wpr.shape[1]] = wpr
+            rows = self.get(fin)[:N * k]
+            logits = rows.to(dt) @ _t(wpad).to(dt).T + _t(np.asarray(bpr, np.float32)).to(dt)
+            yield target, up, dict(kind='refined', x=src.numpy().astype(np.float32), idx=idx.numpy(), logits=logits.view(N, k, ncls),
+                                   rows=rows.numpy().astype(np.float32), w=wpad, b=np.asarray(bpr, np.float32))

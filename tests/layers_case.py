@@ -55,8 +55,22 @@ U = 2^-24 is the unit round-off of fp32 (one rounding of a value v costs at most
   result is an fp32 subnormal that may be flushed.  exp(-90) = 0 and exp(-30) < U make the gate exactly x; exp(90) = inf makes it
   exactly 0: asserted as equalities.
 * depthwise fp32 (dw_e32): one fmaf chain of K*K taps from 0: K*K U sum |w||x|.
+* the fp32 mode's convolution (conv32_ref_bound; csrc/ref32.hip conv32_kernel).  Both operands are fp32 and enter the exact fp32
+  matrix pipe as they are: no operand error.  v_mfma_f32_32x32x2_f32 is an fmaf chain per output: K = KH KW Cin16 steps (the
+  padding's products are exact zeros), every step rounding a partial sum bounded by S = |x| . |w|, so on any path a term passes
+  at most K roundings:  worst = K U S.  Taken independent in sign, K roundings each of a partial sum whose size is the root sum
+  square of the terms:  rss = U sqrt(K) sqrt(x^2 . w^2).  The epilogue is x3_range_case's, the same code: bias, per-image bias
+  and residual one addition each, U (S + |b| + |b_n| + |r| + error so far) each; ReLU keeps the bound; SiLU is
+  t / (1 + __expf(-t)): 1.1 times the error before it plus (13 + |t|) U |silu(t)| + 2^-126.  A head's partial sums in ascending
+  order and its bias (head_finish_bound): tiles + 1 additions, (tiles + 1) U (sum |part| + |b|).
+  A correct kernel never exceeds `worst`; test_graph32_case_host.py holds a float32 evaluation of the same sums, in ascending
+  and in a shuffled order, to 3 of `rss` (x3_range_case.RSS_HOST) and the GPU tests accept min(worst, 6 rss) (RSS_GPU) --
+  the factors of the fp16x3 bounds, not refitted.
+  (head1x1 on the fp32 graph is pointrend_case.predictor_ref's bound: a K-term fp32 dot product in any order and the bias add.)
 """
 import numpy as np
+
+import x3_range_case as x3
 
 U = 2.0 ** -24
 UH = 2.0 ** -11
@@ -424,3 +438,68 @@ def dw_ref_bound(x, w, K):
                 out += xp[:, ky:ky + H, kx:kx + W] * ww[ky * K + kx]
         return out
     return conv(x64, w64), K * K * U * conv(np.abs(x64), np.abs(w64))
+
+
+# ----------------------------------------------------------------------------
+# the fp32 mode's convolution (conv32_kernel) and the fused head's finish
+# ----------------------------------------------------------------------------
+def conv32_ref_bound(c, p):
+    """A case dict and operands in x3_range_case's layouts (x3_range_case._c / build: x (N,H,W,C), w (Cout, k*k, Cin) tap-major,
+    b, bn, r; groups as there) -> dict(ref, worst, rss), (M, Cout) float64: the module docstring's bound of conv32_kernel"""
+    refs, worsts, rsss, Ss = [], [], [], []
+    for X, Wm, _, _ in x3.gemm_blocks(c, p):
+        K = X.shape[1]
+        S = np.abs(X) @ np.abs(Wm).T
+        refs.append(X @ Wm.T)
+        worsts.append(K * U * S)
+        rsss.append(U * np.sqrt(K) * np.sqrt((X * X) @ (Wm * Wm).T))
+        Ss.append(S)
+    t = np.concatenate(refs, 1) + np.asarray(p['b'], np.float64)[None]
+    worst, rss, A = np.concatenate(worsts, 1), np.concatenate(rsss, 1), np.concatenate(Ss, 1) + np.abs(p['b'])[None]
+    n_ep = 1
+    for name, on in (('bn', c['bias_n']), ('r', bool(c['res']))):
+        if on:
+            v = x3._rows(c, p, name)
+            t, A, n_ep = t + v, A + np.abs(v), n_ep + 1
+    ep = n_ep * U * (A + worst)
+    worst, rss = worst + ep, rss + ep
+    if c['act'] == 1:
+        out = np.maximum(t, 0.0)
+    elif c['act'] == 2:
+        with np.errstate(over='ignore'):
+            out = x3._silu(t)
+        ea = (13.0 + np.abs(t)) * U * np.abs(out) + TINY32 + np.where(t < -87.0, np.abs(out), 0.0)
+        worst, rss = x3.SILU_LIP * worst + ea, x3.SILU_LIP * rss + ea
+    else:
+        out = t
+    return dict(ref=out, worst=worst, rss=rss)
+
+
+def conv32_emulate(c, p, order=None, rows=None, cols=None):
+    """the same sums in float32, one rounding per term in the K order `order` (a permutation of K; None: ascending, the
+    kernel's), then the fp32 epilogue -> float32, (M, Cout) or its sub-matrix rows x cols (index arrays).  fp32 x fp32 is exact
+    in float64, so the float64 product rounded once with the running sum is an fmaf.  One group only."""
+    (X, Wm, _, _), = x3.gemm_blocks(c, p)
+    rows = np.arange(X.shape[0]) if rows is None else np.asarray(rows)
+    cols = np.arange(Wm.shape[0]) if cols is None else np.asarray(cols)
+    X, Wm = X[rows], Wm[cols]
+    acc = np.zeros((len(rows), len(cols)), np.float32)
+    for k in (range(X.shape[1]) if order is None else order):
+        acc = (acc.astype(np.float64) + X[:, k:k + 1] * Wm[None, :, k]).astype(np.float32)
+    t = acc + np.asarray(p['b'], np.float32)[None, cols]
+    if c['bias_n']:
+        t = t + x3._rows(c, p, 'bn').astype(np.float32)[np.ix_(rows, cols)]
+    if c['res']:
+        t = t + x3._rows(c, p, 'r').astype(np.float32)[np.ix_(rows, cols)]
+    if c['act'] == 1:
+        t = np.maximum(t, np.float32(0.0))
+    elif c['act'] == 2:
+        with np.errstate(over='ignore'):
+            t = (t / (np.float32(1.0) + np.exp(-t))).astype(np.float32)
+    return t.astype(np.float32)
+
+
+def head_finish_ref_bound(part, b):
+    """part (tiles, M, C) as the kernel reads it, b (C) -> (reference (M, C), bound): tiles additions from the bias"""
+    part, b = np.asarray(part, np.float64), np.asarray(b, np.float64)
+    return part.sum(0) + b[None], (part.shape[0] + 1) * U * (np.abs(part).sum(0) + np.abs(b)[None])
