@@ -11,7 +11,10 @@ here, as functions over plain arrays and a ``LabelTable`` (anything with its ``l
   and the ids the reference's loop hands out turn by turn (``split_ids``);
 * connected components slab by slab (``labels.label_components``): how an array is cut (``components_geometry``,
   ``components_slab`` with the cap of the default slab) and what is refused, with the texts (``components_check_labels``,
-  ``components_check_count``).
+  ``components_check_count``);
+* Shape Labels (``labels.shape_labels``): the half-directions of the intercept columns (``shape_directions``), the Crofton weights
+  of a spacing (``crofton_weights``; scipy's spherical Voronoi cells, imported when it is called) and the surface or perimeter
+  they give (``crofton_size``).
 
 This module imports numpy only, so all of it is tested without a device (tests/test_labelplan_host.py)."""
 import numpy as np
@@ -409,3 +412,64 @@ def split_ids(turns, report, launches, cur_max, start_label, eb):
             cur_max = max_label + n
             report[i] = max_label + np.arange(1, n + 1, dtype=np.int64)
     return report, all_bases
+
+
+# ----------------------------------------------------------------------------
+# Shape Labels: the directions, the Crofton weights and what follows from the intercept counts
+# ----------------------------------------------------------------------------
+def shape_directions(ndim):
+    """(13, 3) or (4, 2): the half-directions of the 26- / 8-neighbourhood, the offsets in {-1, 0, 1}^ndim whose first non-zero
+    component is +1, in ascending lexicographic order -- the columns of ``LabelShapes.intercepts``"""
+    import itertools
+    return np.array([d for d in itertools.product((-1, 0, 1), repeat=ndim) if any(d) and next(v for v in d if v) > 0], dtype=np.int64)
+
+
+SHAPE_IMAGE_COLUMNS = (0, 7, 8, 9)      # an image (R, W) goes through the kernel as the volume (R, 1, W): its directions there
+SHAPE_AXIS_COLUMNS = {3: (8, 2, 0), 2: (2, 0)}      # the columns of the axis directions: measure_labels' faces
+
+
+def shape_spacing(spacing, ndim, per_slice):
+    """the voxel size per column: ``ndim`` positive values, default 1; a stack's (z, y, x) gives its images' (y, x)"""
+    if spacing is None:
+        return (1.0,) * ndim
+    try:
+        sp = tuple(float(v) for v in np.asarray(spacing, dtype=np.float64).reshape(-1))
+    except (TypeError, ValueError):
+        sp = ()
+    if per_slice and len(sp) == 3:
+        sp = sp[1:]
+    if len(sp) != ndim or not all(np.isfinite(v) and v > 0 for v in sp):
+        raise ValueError(f'shape_labels: spacing needs {ndim} positive values, got {spacing}')
+    return sp
+
+
+def crofton_weights(spacing=None, ndim=3):
+    """(13,) or (4,): per half-direction d_k the share c_k of the unit sphere (circle) that is nearer to +-d_k * spacing than to any
+    other direction; they sum to 1.  3-D: the areas of the spherical Voronoi cells of the 26 unit vectors (scipy), +- summed;
+    2-D: a direction's cell reaches half way to its two neighbours on the circle."""
+    sp = np.asarray(shape_spacing(spacing, ndim, False), dtype=np.float64)
+    d = shape_directions(ndim) * sp
+    u = d / np.linalg.norm(d, axis=1, keepdims=True)
+    if ndim == 2:
+        ang = np.arctan2(u[:, 0], u[:, 1])      # the four half-directions lie in [0, pi); the other four are opposite
+        order = np.argsort(ang)
+        a = ang[order]
+        gaps = np.diff(np.concatenate([a, [a[0] + np.pi]]))      # to the next direction; the last one's next is the first's opposite
+        c = np.empty(4)
+        c[order] = (gaps + np.roll(gaps, 1)) / (2.0 * np.pi)
+        return c
+    from scipy.spatial import SphericalVoronoi
+    areas = SphericalVoronoi(np.concatenate([u, -u])).calculate_areas()
+    return (areas[:13] + areas[13:]) / (4.0 * np.pi)
+
+
+def crofton_size(intercepts, spacing):
+    """The Cauchy-Crofton surface (13 columns) or perimeter (4 columns) of every row of intercept counts: chords per direction
+    (half the intercepts) times the area (length) per lattice line of that direction, v / |d_k * spacing|, averaged over the
+    sphere (circle) with ``crofton_weights``, times 4 (times pi)."""
+    intercepts = np.asarray(intercepts)
+    ndim = 3 if intercepts.shape[1] == 13 else 2
+    sp = np.asarray(spacing, dtype=np.float64)
+    per_line = float(np.prod(sp)) / np.linalg.norm(shape_directions(ndim) * sp, axis=1)
+    terms = intercepts * (crofton_weights(sp, ndim) * per_line)
+    return (2.0 if ndim == 3 else np.pi / 2.0) * terms.sum(axis=1)

@@ -47,6 +47,10 @@ The one deliberate difference: on an image without labels the reference's ``filt
 first and second moments of its voxel coordinates and its exposed voxel faces per axis, all integers; ``LabelMeasures`` derives
 centroids, volumes, face surfaces, covariances and principal axes from them as pure numpy.
 
+``shape_labels`` (csrc/shape.hip) counts, per label, the intercepts along the 13 half-directions of the 26-neighbourhood and the
+Euler number under full and under face connectivity, again all integers; ``LabelShapes`` derives the Cauchy-Crofton surface (or
+perimeter), the sphericity that goes with it and the Euler numbers as pure numpy, with the weights of ``crofton_weights``.
+
 ``label_components`` (csrc/components.hip) splits a label array of any size into its connected components, slab by slab: per slab
 ``emp_ccl_range``, across the seams a union-find over the slabs' component ids, then one numbering in raster order.
 ``remove_boundary_labels(streamed=True)`` is the reference mode on top of it, for arrays the one-call CCL cannot take.
@@ -62,10 +66,10 @@ import torch
 from . import _abi, _labelplan as P
 from ._labelplan import (FILL_MAX_HOLE_SIZE, FILL_MAX_LEVEL_VOXELS, MORPH_MAX_RADIUS, MORPH_OPS, SPLIT_MAX_BOXES, SPLIT_MAX_DIAGONAL2,  # noqa: F401
                          SPLIT_MAX_DISTANCE, SPLIT_MAX_ENTRIES, _MORPH_GROWS, _morph_args, _morph_tiles, _morph_turns, _split_batches, dims3,
-                         morph_footprint_offsets, morph_footprint_rows, morph_schedule, split_marker_ids, split_spacing)
+                         crofton_weights, morph_footprint_offsets, morph_footprint_rows, morph_schedule, shape_directions, split_marker_ids, split_spacing)
 from ._labelstream import GrowableTable, RawSource, Sink, ebytes, hp, initial_capacity, need_device, pick_device, slab_plan, source, stream_slabs
 
-__all__ = ['LabelTable', 'label_table', 'table_from_arrays', 'LabelMeasures', 'measure_labels', 'measures_from_arrays', 'small_labels', 'boundary_labels', 'count_labels', 'class_label_lists',
+__all__ = ['LabelTable', 'label_table', 'table_from_arrays', 'LabelMeasures', 'measure_labels', 'measures_from_arrays', 'LabelShapes', 'shape_labels', 'shapes_from_arrays', 'crofton_weights', 'shape_directions', 'small_labels', 'boundary_labels', 'count_labels', 'class_label_lists',
            'next_available_labels', 'next_available_label', 'label_bbox', 'delete_labels', 'merge_labels',
            'filter_out_small_label_areas', 'remove_boundary_labels', 'label_components', 'morph_labels', 'fill_label_holes', 'morph_schedule',
            'morph_footprint_rows', 'morph_footprint_offsets', 'split_labels', 'split_spacing', 'split_marker_ids']
@@ -368,6 +372,163 @@ def measure_labels(labels, spacing=None, per_slice=False, border_faces=True, dev
     with torch.cuda.device(device):
         src = source(labels, device)
         return _measures_of_source(src, src.shape, spacing, bool(per_slice), border_faces, device, slab, capacity)
+
+
+# ----------------------------------------------------------------------------
+# device: the shapes
+# ----------------------------------------------------------------------------
+@dataclass
+class LabelShapes:
+    """What ``shape_labels`` counts, per label that occurs (background 0 left out), and what follows from it.
+
+    The raw columns are integers and exact.  ``labels`` ascending, ``areas`` the voxel counts; ``intercepts`` (k, 13), or (k, 4)
+    for an image and, per slice, for the images of a stack: column j belongs to the half-direction ``directions[j]`` (the offsets
+    in {-1, 0, 1}^ndim whose first non-zero component is +1, in lexicographic order) and holds, with M the voxels of the label,
+    #{p in M : p + d not in M} + #{p in M : p - d not in M}; the axis columns are ``measure_labels``' ``faces``.  ``euler`` (k, 2):
+    the Euler number under full connectivity (26 / 8: of the union of the closed voxel cubes) and under face connectivity (6 / 4:
+    voxels - face pairs + quads - octets).  Per slice ``slices`` holds the leading-axis index and rows are sorted by slice, then
+    label.  ``spacing``: the voxel size per axis; ``doublings``: how often the device table had to grow.
+
+    Everything derived is pure numpy on these columns.  ``surface_area`` and ``perimeter`` are the Cauchy-Crofton estimates: the
+    intercepts of a direction are twice the chords of the object along its lattice lines, every line stands for the area
+    (length) v / |d * spacing| perpendicular to it, and the directions are averaged with ``crofton_weights``.  This is the estimator
+    of ``skimage.measure.perimeter_crofton(directions=4)`` for an image and the same estimator with 13 directions for a volume,
+    ``euler`` is ``skimage.measure.euler_number`` with connectivity ndim and 1: both restated from their documentation, not pinned
+    against them (skimage is not available here).  Pinned are the integers, against a numpy statement and ``measure_labels``."""
+    labels: np.ndarray
+    areas: np.ndarray
+    intercepts: np.ndarray
+    euler: np.ndarray
+    slices: object = None
+    shape: tuple = ()
+    spacing: tuple = ()
+    doublings: int = 0
+
+    @property
+    def per_slice(self):
+        return self.slices is not None
+
+    @property
+    def ndim(self):
+        return 3 if self.intercepts.shape[1] == 13 else 2
+
+    @property
+    def directions(self):
+        return P.shape_directions(self.ndim)
+
+    @property
+    def volume(self):
+        """voxel count times the voxel's volume (its area for ndim 2)"""
+        return self.areas * float(np.prod(self.spacing))
+
+    @property
+    def surface_area(self):
+        """2 sum_k c_k intercepts[k] v / |d_k * spacing|: within a few per cent of a smooth surface (a digitised ball of radius 8:
+        -1.3 %), where the voxel-face surface of ``LabelMeasures`` is up to 1.5 times too large"""
+        if self.ndim != 3:
+            raise ValueError('surface_area: for volumes; an image has a perimeter')
+        return P.crofton_size(self.intercepts, self.spacing)
+
+    @property
+    def perimeter(self):
+        """(pi / 2) sum_k c_k intercepts[k] a / |d_k * spacing|"""
+        if self.ndim != 2:
+            raise ValueError('perimeter: for images; a volume has a surface_area')
+        return P.crofton_size(self.intercepts, self.spacing)
+
+    @property
+    def sphericity(self):
+        """pi^(1/3) (6 V)^(2/3) / S with the Crofton surface: close to 1 for a digitised ball"""
+        with np.errstate(divide='ignore', invalid='ignore'):
+            return np.cbrt(np.pi) * np.cbrt(6.0 * self.volume) ** 2 / self.surface_area
+
+    @property
+    def circularity(self):
+        """4 pi A / P^2 with the Crofton perimeter"""
+        with np.errstate(divide='ignore', invalid='ignore'):
+            return 4.0 * np.pi * self.volume / self.perimeter ** 2
+
+    def euler_number(self, connectivity=None):
+        """objects - tunnels + cavities per label (in an image: objects - holes).  ``connectivity``: None or ndim for full
+        connectivity (26 / 8), 1 for face connectivity (6 / 4)"""
+        if connectivity not in (None, 1, self.ndim):
+            raise ValueError(f'euler_number: connectivity 1 or {self.ndim}, got {connectivity}')
+        return self.euler[:, 1 if connectivity == 1 else 0]
+
+    def to_table(self):
+        """dict of columns"""
+        out = {'slice': self.slices} if self.per_slice else {}
+        out.update({'label': self.labels, 'area': self.areas, 'volume': self.volume})
+        if self.ndim == 3:
+            out.update({'surface_area': self.surface_area, 'sphericity': self.sphericity})
+        else:
+            out.update({'perimeter': self.perimeter, 'circularity': self.circularity})
+        out.update({'euler_number': self.euler[:, 0], 'euler_number_faces': self.euler[:, 1]})
+        out.update({f'intercepts-{j}': self.intercepts[:, j] for j in range(self.intercepts.shape[1])})
+        return out
+
+    def to_csv(self, path):
+        import csv
+        table = self.to_table()
+        with open(path, 'w', newline='') as f:
+            w = csv.writer(f)
+            w.writerow(table)
+            w.writerows(zip(*(col.tolist() for col in table.values())))
+
+
+def shapes_from_arrays(labels, areas, intercepts, euler, shape, spacing=None, slices=None, doublings=0):
+    """LabelShapes from host arrays (rows in any order, each key once)."""
+    shape = tuple(int(s) for s in shape)
+    if len(shape) not in (2, 3) or (slices is not None and len(shape) != 3):
+        raise ValueError(f'shapes_from_arrays: 2-D or 3-D label arrays (per slice: 3-D), got shape {shape}')
+    nd = 2 if slices is not None else len(shape)
+    cols = [np.asarray(labels, dtype=np.int64).reshape(-1), np.asarray(areas, dtype=np.int64).reshape(-1),
+            np.asarray(intercepts, dtype=np.int64).reshape(-1, 13 if nd == 3 else 4), np.asarray(euler, dtype=np.int64).reshape(-1, 2)]
+    if len({len(c) for c in cols}) != 1:
+        raise ValueError('shapes_from_arrays: the columns differ in length')
+    if slices is not None:
+        slices = np.asarray(slices, dtype=np.int64).reshape(-1)
+        order = np.lexsort((cols[0], slices))
+        slices = slices[order]
+    else:
+        order = np.argsort(cols[0], kind='stable')
+    return LabelShapes(*(c[order] for c in cols), slices, shape, P.shape_spacing(spacing, nd, slices is not None), int(doublings))
+
+
+def _shapes_of_source(src, shape, spacing, per_slice, border_faces, device, slab, capacity):
+    rows, H, W = _geometry(shape, per_slice, 'shape_labels')
+    nd = 2 if per_slice else len(shape)
+    spacing = P.shape_spacing(spacing, nd, per_slice)      # refused before anything is allocated
+    table = GrowableTable('emp_label_shape', 'shape_labels', capacity or min(initial_capacity(rows * H * W), MEASURE_MAX_CAPACITY), device)
+    # the slice below a slab's first one, as in _measures_of_source: in front of a device slab, kept in a buffer for a host one
+    host_halo = src.is_host and not per_slice
+    halo = torch.empty(max(1, src.row_bytes), dtype=torch.uint8, device=device) if host_halo else None
+    for _, z0, z1, (address,) in stream_slabs([src], slab, device):
+        below = None if per_slice or z0 == 0 else (halo.data_ptr() if host_halo else address - src.row_bytes)
+        table.add(address, src.ebytes, z0, z1 - z0, H, W, rows, below, int(per_slice), int(bool(border_faces)))
+        if host_halo and z1 < rows:
+            _abi.check(table.lib.emp_copy_d2d(_abi.ptr(halo), address + (z1 - z0 - 1) * src.row_bytes, src.row_bytes, _abi.stream_ptr(device)),
+                       'emp_copy_d2d')
+    keys, cnt, icpt, euler = (t.cpu().numpy() for t in table.finalize(extra=[(13, torch.int64), (2, torch.int64)]))
+    if per_slice:      # the images' four directions are the kernel's first four
+        return LabelShapes(keys & 0xffffffff, cnt, icpt[:, :4], euler, keys >> 32, tuple(shape), spacing, table.doublings)
+    if len(shape) == 2:      # kernel (z, y, x) = image (y, 0, x)
+        return LabelShapes(keys, cnt, icpt[:, list(P.SHAPE_IMAGE_COLUMNS)], euler, None, tuple(shape), spacing, table.doublings)
+    return LabelShapes(keys, cnt, icpt, euler, None, tuple(shape), spacing, table.doublings)
+
+
+@torch.no_grad()
+def shape_labels(labels, spacing=None, per_slice=False, border_faces=True, device=None, slab=None, capacity=None):
+    """The ``LabelShapes`` of a 2-D or 3-D label array (csrc/shape.hip): sources, dtypes, value domain, ``per_slice``, ``slab`` and
+    ``capacity`` as ``measure_labels``; label 0 is background.  ``spacing``: the voxel size per axis (default 1).
+    ``border_faces``: a neighbour outside the array counts as not of the label (default); False leaves out every pair with one
+    end outside the array.  The Euler numbers always take the outside as background.  The raw columns are exact, do not depend
+    on ``slab`` and are bit-reproducible."""
+    need_device()
+    device = pick_device(device, labels)
+    with torch.cuda.device(device):
+        src = source(labels, device)
+        return _shapes_of_source(src, src.shape, spacing, bool(per_slice), border_faces, device, slab, capacity)
 
 
 # ----------------------------------------------------------------------------

@@ -980,6 +980,52 @@ EMP_API int emp_label_measure_finalize(void* d_table, int64_t capacity, uint64_t
                                  uint64_t* d_sums, uint64_t* d_faces, int64_t max_out, int64_t* h_num, void* stream);
 
 /* ------------------------------------------------------------------------
+ * 7c. Shape Labels (csrc/shape.hip): per label that occurs, background 0
+ *    excepted, the integers behind a smooth surface and a hole count: the
+ *    intercept counts along the 13 half-directions of the 26-neighbourhood
+ *    (Cauchy-Crofton: surface = 2 sum_k c_k I_k v / |d_k|, with the weights
+ *    c_k the host derives from the spacing; in an image the perimeter from
+ *    the first four) and the Euler number under full and under face
+ *    connectivity.  What skimage's perimeter_crofton and euler_number
+ *    compute is restated from their documentation and is NOT pinned against
+ *    them (skimage is not available where this library is built); pinned
+ *    are the integers against a numpy statement and the axis intercepts
+ *    against section 7b's faces.
+ *
+ *    The table has the life cycle and the overflow contract of sections 6,
+ *    7 and 7b.  A slot is 136 bytes.  All sums are exact; the Euler sums are
+ *    signed and kept modulo 2^64.
+ * ---------------------------------------------------------------------- */
+/* 0 if the capacity is not a power of two in [64, 2^32] */
+EMP_API size_t emp_label_shape_work_bytes(int64_t capacity);
+EMP_API int emp_label_shape_reset(void* d_table, int64_t capacity, void* stream);
+/* Adds the slab d_labels (depth, H, W), slices [z0, z0 + depth) of a volume of total_depth slices, to the table: arguments, keys,
+ * value domain, d_halo and errors are those of emp_label_measure_accumulate (there is no moment guard; total_depth < 2^31 and
+ * H, W < 2^30).  Per key, with M the voxels of the label:
+ *   count          the voxels
+ *   I[k], k < 13   the half-directions d_k are the (dz, dy, dx) in {-1, 0, 1}^3 \ {0} whose first non-zero component is +1, in
+ *                  ascending lexicographic order: (0,0,1), (0,1,-1), (0,1,0), (0,1,1), (1,-1,-1), .., (1,1,1).
+ *                  I[k] = #{p in M : p + d_k not in M} + #{p in M : p - d_k not in M}.  border_faces != 0: a neighbour outside
+ *                  the array is not in M; 0: a pair with one end outside the array is not counted.  I[8], I[2], I[0] are the F
+ *                  of section 7b.  per_slice 1: only k < 4 (the directions of an image) are counted, the rest stay 0.
+ *   chi[0]         the Euler number of the union of the closed voxel cubes of M (full connectivity: 26, in an image 8):
+ *                  vertices - edges + faces - voxels of the cubical complex, on the array padded with background
+ *   chi[1]         the Euler number under face connectivity (6 / 4): voxels - face pairs inside M + 2 x 2 quads inside M -
+ *                  2 x 2 x 2 octets inside M.  per_slice 1: both are the image's, nothing crosses slices.
+ * An image (R, W) is passed as the volume (R, 1, W): its four directions are k = 0, 7, 8, 9, and both Euler numbers are the
+ * image's.  The vertices on the faces z = total_depth, y = H, x = W of the array are counted by the voxels at the last index,
+ * for z by the slab that holds the last slice.  Synchronises the stream.  *h_overflow = 1 as in section 7b. */
+EMP_API int emp_label_shape_accumulate(const void* d_labels, int in_bytes, int64_t z0, int depth, int H, int W, int64_t total_depth,
+                                 const void* d_halo, int per_slice, int border_faces, void* d_table, int64_t capacity, void* stream,
+                                 int* h_overflow);
+/* Re-inserts the counted cells of d_from into the reset, larger table d_to.  Synchronises.  *h_overflow = 1: d_to is too small too. */
+EMP_API int emp_label_shape_grow(const void* d_from, int64_t from_capacity, void* d_to, int64_t to_capacity, void* stream, int* h_overflow);
+/* *h_num = the number of keys, of which min(*h_num, max_out) are written, in no particular order: d_keys[i], d_counts[i],
+ * d_intercepts[13 i ..] = I, d_euler[2 i ..] = chi.  Synchronises.  The table stays valid and can be fed further. */
+EMP_API int emp_label_shape_finalize(void* d_table, int64_t capacity, uint64_t* d_keys, uint64_t* d_counts, uint64_t* d_intercepts,
+                                 int64_t* d_euler, int64_t max_out, int64_t* h_num, void* stream);
+
+/* ------------------------------------------------------------------------
  * 8. Morph Labels (csrc/morph.hip): binary dilation, erosion, closing and
  *    opening of single labels with a disk / ball of radius 1..7, every label
  *    inside its own padded box -- the plugin's Morph Labels
