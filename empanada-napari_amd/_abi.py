@@ -202,6 +202,11 @@ PROTOTYPES = {
     'emp_label_shape_accumulate': (c_int, [vp, c_int, c_i64, c_int, c_int, c_int, c_i64, vp, c_int, c_int, vp, c_i64, vp, C.POINTER(c_int)]),
     'emp_label_shape_grow': (c_int, [vp, c_i64, vp, c_i64, vp, C.POINTER(c_int)]),
     'emp_label_shape_finalize': (c_int, [vp, c_i64, vp, vp, vp, vp, c_i64, C.POINTER(c_i64), vp]),
+    'emp_label_contacts_work_bytes': (sz, [c_i64]),
+    'emp_label_contacts_reset': (c_int, [vp, c_i64, vp]),
+    'emp_label_contacts_accumulate': (c_int, [vp, c_int, c_i64, c_int, c_int, c_int, c_i64, vp, c_int, vp, c_i64, vp, C.POINTER(c_int)]),
+    'emp_label_contacts_grow': (c_int, [vp, c_i64, vp, c_i64, vp, C.POINTER(c_int)]),
+    'emp_label_contacts_finalize': (c_int, [vp, c_i64, vp, vp, vp, c_i64, C.POINTER(c_i64), vp]),
     'emp_morph_tile_shape': (c_int, [c_int, c_int, c_int, C.POINTER(c_int), C.POINTER(c_int), C.POINTER(c_int)]),
     'emp_morph_labels': (c_int, [vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp, c_i64, vp, vp, c_int, vp, c_i64, vp,
                                  C.POINTER(c_int)]),

@@ -473,3 +473,68 @@ def crofton_size(intercepts, spacing):
     per_line = float(np.prod(sp)) / np.linalg.norm(shape_directions(ndim) * sp, axis=1)
     terms = intercepts * (crofton_weights(sp, ndim) * per_line)
     return (2.0 if ndim == 3 else np.pi / 2.0) * terms.sum(axis=1)
+
+
+# ----------------------------------------------------------------------------
+# Contact Labels: what follows from the pair counts per half-direction
+# ----------------------------------------------------------------------------
+def contact_spacing(spacing, ndim):
+    """``shape_spacing`` with the tool's own name in the error"""
+    try:
+        return shape_spacing(spacing, ndim, False)
+    except ValueError:
+        raise ValueError(f'label_contacts: spacing needs {ndim} positive values, got {spacing}') from None
+
+
+def contact_face_sizes(spacing):
+    """per axis the physical size of a voxel face perpendicular to it (an image: of a pixel edge): the product of the other spacings"""
+    sp = np.asarray(spacing, dtype=np.float64)
+    return float(np.prod(sp)) / sp
+
+
+def contact_sizes(pairs, spacing):
+    """The Cauchy-Crofton area (13 columns) or length (4 columns) of the surface every row's pairs cross: a pair along d_k is one
+    crossing of a lattice line of that direction, which is one intercept of either label, so this is ``crofton_size`` of the pair
+    counts: 2 sum_k c_k N_k v / |d_k * spacing| (an image: pi / 2 in place of 2)"""
+    pairs = np.asarray(pairs)
+    if len(pairs) == 0:
+        return np.zeros(0, np.float64)
+    return crofton_size(pairs, spacing)
+
+
+def contact_fold_classes(a, b, pairs, label_divisor):
+    """the table over (a // divisor, b // divisor), lower class first: (ca, cb, pairs) sorted by (ca, cb), the columns summed.  Pairs
+    of two instances of one class are kept as (c, c); the background stays class 0"""
+    div = int(label_divisor)
+    if div < 1:
+        raise ValueError(f'by_class: label_divisor must be positive, got {label_divisor}')
+    ca, cb = np.asarray(a, np.int64) // div, np.asarray(b, np.int64) // div
+    lo, hi = np.minimum(ca, cb), np.maximum(ca, cb)
+    both = np.stack([lo, hi], axis=1)
+    keys, inv = np.unique(both, axis=0, return_inverse=True)
+    out = np.zeros((len(keys), np.asarray(pairs).shape[1]), np.int64)
+    np.add.at(out, inv.reshape(-1), np.asarray(pairs, np.int64))
+    return keys[:, 0].copy(), keys[:, 1].copy(), out
+
+
+def contact_groups(a, b, keep):
+    """The groups of labels that the kept rows join, by union-find on the host: a list of ascending int64 id arrays, each of two ids
+    or more, in ascending order of their smallest id"""
+    a, b = np.asarray(a, np.int64)[keep], np.asarray(b, np.int64)[keep]
+    ids, inv = np.unique(np.concatenate([a, b]), return_inverse=True)
+    parent = list(range(len(ids)))
+
+    def find(i):
+        while parent[i] != i:
+            parent[i] = parent[parent[i]]
+            i = parent[i]
+        return i
+
+    for i, j in zip(inv[:len(a)].tolist(), inv[len(a):].tolist()):
+        ri, rj = find(i), find(j)
+        if ri != rj:
+            parent[max(ri, rj)] = min(ri, rj)      # the root is the smallest id: ids is sorted
+    groups = {}
+    for i in range(len(ids)):
+        groups.setdefault(find(i), []).append(int(ids[i]))
+    return [np.array(g, np.int64) for _, g in sorted(groups.items()) if len(g) > 1]

@@ -26,9 +26,10 @@ PER_FILE = {
     # the loop over a lane's 16 one-byte voxels is longer than the size up to which `#pragma unroll` is obeyed in full; unrolled in
     # part it indexes the lane's windows at run time, which puts them into scratch memory
     'shape.hip': ['-mllvm', '-pragma-unroll-threshold=131072'],
+    'contacts.hip': ['-mllvm', '-pragma-unroll-threshold=131072'],      # the same windows, the same loop
 }
 SOURCES = ['abi.hip', 'conv_igemm.hip', 'layers.hip', 'pointrend.hip', 'postprocess.hip', 'pdl_net.hip', 'pdl_net32.hip', 'sparse.hip',
-           'sepconv.hip', 'sepconv_precise.hip', 'conv_igemm256.hip', 'conv_igemm_s64.hip', 'conv3x3c64.hip', 'stem.hip', 'matcher.hip', 'ref32.hip', 'conv16x3.hip', 'conv_igemm_grouped.hip', 'conv16x3p.hip', 'sepconv_x3.hip', 'overlap.hip', 'labels.hip', 'measure.hip', 'shape.hip', 'morph.hip', 'split.hip', 'components.hip']
+           'sepconv.hip', 'sepconv_precise.hip', 'conv_igemm256.hip', 'conv_igemm_s64.hip', 'conv3x3c64.hip', 'stem.hip', 'matcher.hip', 'ref32.hip', 'conv16x3.hip', 'conv_igemm_grouped.hip', 'conv16x3p.hip', 'sepconv_x3.hip', 'overlap.hip', 'labels.hip', 'measure.hip', 'shape.hip', 'contacts.hip', 'morph.hip', 'split.hip', 'components.hip']
 # sources that #include another source: rebuilt when that one changes
 INCLUDES = {'conv_igemm_grouped.hip': ['conv_igemm.hip']}
 

@@ -51,6 +51,11 @@ centroids, volumes, face surfaces, covariances and principal axes from them as p
 Euler number under full and under face connectivity, again all integers; ``LabelShapes`` derives the Cauchy-Crofton surface (or
 perimeter), the sphericity that goes with it and the Euler numbers as pure numpy, with the weights of ``crofton_weights``.
 
+``label_contacts`` (csrc/contacts.hip) counts, per unordered pair of different labels that occur next to each other, the voxel pairs
+that join them along the same 13 half-directions; ``LabelContacts`` derives shared faces, the Cauchy-Crofton contact area, the
+adjacency matrix, the share of each label's surface and the groups a threshold on them joins (``merge_groups``, whose groups
+``merge_labels`` takes) as pure numpy.
+
 ``label_components`` (csrc/components.hip) splits a label array of any size into its connected components, slab by slab: per slab
 ``emp_ccl_range``, across the seams a union-find over the slabs' component ids, then one numbering in raster order.
 ``remove_boundary_labels(streamed=True)`` is the reference mode on top of it, for arrays the one-call CCL cannot take.
@@ -69,7 +74,7 @@ from ._labelplan import (FILL_MAX_HOLE_SIZE, FILL_MAX_LEVEL_VOXELS, MORPH_MAX_RA
                          crofton_weights, morph_footprint_offsets, morph_footprint_rows, morph_schedule, shape_directions, split_marker_ids, split_spacing)
 from ._labelstream import GrowableTable, RawSource, Sink, ebytes, hp, initial_capacity, need_device, pick_device, slab_plan, source, stream_slabs
 
-__all__ = ['LabelTable', 'label_table', 'table_from_arrays', 'LabelMeasures', 'measure_labels', 'measures_from_arrays', 'LabelShapes', 'shape_labels', 'shapes_from_arrays', 'crofton_weights', 'shape_directions', 'small_labels', 'boundary_labels', 'count_labels', 'class_label_lists',
+__all__ = ['LabelTable', 'label_table', 'table_from_arrays', 'LabelMeasures', 'measure_labels', 'measures_from_arrays', 'LabelShapes', 'shape_labels', 'shapes_from_arrays', 'LabelContacts', 'label_contacts', 'contacts_from_arrays', 'crofton_weights', 'shape_directions', 'small_labels', 'boundary_labels', 'count_labels', 'class_label_lists',
            'next_available_labels', 'next_available_label', 'label_bbox', 'delete_labels', 'merge_labels',
            'filter_out_small_label_areas', 'remove_boundary_labels', 'label_components', 'morph_labels', 'fill_label_holes', 'morph_schedule',
            'morph_footprint_rows', 'morph_footprint_offsets', 'split_labels', 'split_spacing', 'split_marker_ids']
@@ -529,6 +534,213 @@ def shape_labels(labels, spacing=None, per_slice=False, border_faces=True, devic
     with torch.cuda.device(device):
         src = source(labels, device)
         return _shapes_of_source(src, src.shape, spacing, bool(per_slice), border_faces, device, slab, capacity)
+
+
+# ----------------------------------------------------------------------------
+# device: the contacts
+# ----------------------------------------------------------------------------
+@dataclass
+class LabelContacts:
+    """What ``label_contacts`` counts, per unordered pair of different labels that occur next to each other, and what follows from
+    it.  Rows are sorted by (a, b), ``a < b``; with ``background`` a pair with the background is the row (0, b), without it there
+    is none.  ``pairs`` (n, 13), or (n, 4) for an image: column k belongs to the half-direction ``directions[k]`` (those of
+    ``LabelShapes.intercepts``) and holds #{p : p and p + d_k both in the array, {L(p), L(p + d_k)} = {a, b}}.  A pair with an end
+    outside the array is never counted.  These integers are exact and do not depend on ``slab``.  Summed over a label's rows, the
+    background's included, ``pairs`` is ``shape_labels(border_faces=False).intercepts`` of that label.
+
+    Everything derived is pure numpy.  ``contact_area`` (``contact_length`` for an image) is the Cauchy-Crofton estimate
+    ``LabelShapes.surface_area`` uses, on the pairs of the row: the part of either label's surface that the other one covers.
+    There is no counterpart in the reference plugin; the nearest thing is skimage's region adjacency graph (``skimage.graph.RAG``,
+    ``rag_boundary``), and nothing here is pinned against it."""
+    a: np.ndarray
+    b: np.ndarray
+    pairs: np.ndarray
+    shape: tuple = ()
+    spacing: tuple = ()
+    background: bool = False
+    doublings: int = 0
+
+    @property
+    def ndim(self):
+        return 3 if self.pairs.shape[1] == 13 else 2
+
+    @property
+    def directions(self):
+        return P.shape_directions(self.ndim)
+
+    @property
+    def counts(self):
+        """the voxel pairs of every row, all directions"""
+        return self.pairs.sum(axis=1)
+
+    @property
+    def faces(self):
+        """(n, ndim): the pairs along the axes, in z, y, x order: the voxel faces the two labels share"""
+        return self.pairs[:, list(P.SHAPE_AXIS_COLUMNS[self.ndim])]
+
+    @property
+    def face_area(self):
+        """the shared voxel faces times their physical size: up to sqrt(3) times the smooth area on a slanted interface"""
+        if self.ndim != 3:
+            raise ValueError('face_area: for volumes; an image has a face_length')
+        return self.faces @ P.contact_face_sizes(self.spacing)
+
+    @property
+    def face_length(self):
+        if self.ndim != 2:
+            raise ValueError('face_length: for images; a volume has a face_area')
+        return self.faces @ P.contact_face_sizes(self.spacing)
+
+    @property
+    def contact_area(self):
+        """2 sum_k c_k pairs[k] v / |d_k * spacing|"""
+        if self.ndim != 3:
+            raise ValueError('contact_area: for volumes; an image has a contact_length')
+        return P.contact_sizes(self.pairs, self.spacing)
+
+    @property
+    def contact_length(self):
+        """(pi / 2) sum_k c_k pairs[k] a / |d_k * spacing|"""
+        if self.ndim != 2:
+            raise ValueError('contact_length: for images; a volume has a contact_area')
+        return P.contact_sizes(self.pairs, self.spacing)
+
+    def _size(self):
+        return P.contact_sizes(self.pairs, self.spacing)
+
+    @property
+    def labels(self):
+        """the sorted distinct ids of all rows"""
+        return np.unique(np.concatenate([self.a, self.b]))
+
+    def neighbors(self, label, connectivity=None):
+        """the ids in contact with ``label``, ascending.  ``connectivity``: None or ndim keeps every pair, 1 only pairs that share a
+        voxel face"""
+        if connectivity not in (None, 1, self.ndim):
+            raise ValueError(f'neighbors: connectivity 1 or {self.ndim}, got {connectivity}')
+        keep = np.ones(len(self.a), bool) if connectivity != 1 else self.faces.any(axis=1)
+        return np.unique(np.concatenate([self.b[keep & (self.a == label)], self.a[keep & (self.b == label)]]))
+
+    def degree(self):
+        """per id of ``labels`` the number of its partners"""
+        ids = self.labels
+        other = self.a != self.b
+        return np.bincount(np.searchsorted(ids, np.concatenate([self.a, self.b[other]])), minlength=len(ids)).astype(np.int64)
+
+    def _weight(self, weight):
+        if weight in ('contact_area', 'contact_length'):
+            return self._size()
+        if weight in ('face_area', 'face_length'):
+            return self.faces @ P.contact_face_sizes(self.spacing)
+        if weight == 'counts':
+            return self.counts.astype(np.float64)
+        raise ValueError(f'adjacency: weight contact_area, face_area or counts, got {weight}')
+
+    def adjacency(self, weight='contact_area'):
+        """the symmetric ``scipy.sparse.csr_matrix`` over ``labels``: entry (i, j) is the weight of the row {labels[i], labels[j]}"""
+        from scipy.sparse import coo_matrix
+        ids = self.labels
+        i, j, w = np.searchsorted(ids, self.a), np.searchsorted(ids, self.b), self._weight(weight)
+        off = i != j
+        return coo_matrix((np.concatenate([w, w[off]]), (np.concatenate([i, j[off]]), np.concatenate([j, i[off]]))), shape=(len(ids),) * 2).tocsr()
+
+    def fractions(self):
+        """(n, 2): the contact's share of the whole Crofton surface that a and b have inside the array.  The whole surface of a
+        label is the sum over all its rows, the background's included: it needs ``background=True``"""
+        if not self.background:
+            raise ValueError('fractions: the share of a surface needs the pairs with the background: label_contacts(..., background=True)')
+        ids, size = self.labels, self._size()
+        i, j = np.searchsorted(ids, self.a), np.searchsorted(ids, self.b)
+        whole = np.bincount(i, size, len(ids)) + np.bincount(j[i != j], size[i != j], len(ids))
+        return np.stack([size / whole[i], size / whole[j]], axis=1) if len(size) else np.zeros((0, 2))
+
+    def by_class(self, label_divisor):
+        """the same table over the classes (a // label_divisor, b // label_divisor).  Pairs of two instances of one class are kept
+        as the row (c, c); the background stays class 0"""
+        ca, cb, pairs = P.contact_fold_classes(self.a, self.b, self.pairs, label_divisor)
+        return LabelContacts(ca, cb, pairs, self.shape, self.spacing, self.background, self.doublings)
+
+    def merge_groups(self, min_area=0.0, min_fraction=None, label_divisor=None):
+        """The groups of labels joined by contacts of at least ``min_area`` (``contact_area``; an image: ``contact_length``) and, if
+        given, of at least ``min_fraction`` of the surface of one of the two (the larger share; needs ``background=True``).  The
+        background joins nothing.  ``label_divisor``: only labels of one class are joined.  The union-find runs on the host.
+        Returns a list of ascending id arrays in ascending order of their smallest id: each is a valid ``ids=`` of ``merge_labels``."""
+        keep = (self.a != 0) & (self.a != self.b) & (self._size() >= float(min_area))
+        if min_fraction is not None:
+            keep &= self.fractions().max(axis=1) >= float(min_fraction)
+        if label_divisor is not None:
+            keep &= self.a // int(label_divisor) == self.b // int(label_divisor)
+        return P.contact_groups(self.a, self.b, keep)
+
+    def to_table(self):
+        """dict of columns"""
+        out = {'a': self.a, 'b': self.b, 'count': self.counts}
+        size = 'area' if self.ndim == 3 else 'length'
+        out.update({f'contact_{size}': self._size(), f'face_{size}': self.faces @ P.contact_face_sizes(self.spacing)})
+        out.update({f'faces-{ax}': self.faces[:, j] for j, ax in enumerate('zyx'[3 - self.ndim:])})
+        out.update({f'pairs-{j}': self.pairs[:, j] for j in range(self.pairs.shape[1])})
+        return out
+
+    def to_csv(self, path):
+        import csv
+        table = self.to_table()
+        with open(path, 'w', newline='') as f:
+            w = csv.writer(f)
+            w.writerow(table)
+            w.writerows(zip(*(col.tolist() for col in table.values())))
+
+
+def contacts_from_arrays(a, b, pairs, shape, spacing=None, background=False, doublings=0):
+    """LabelContacts from host arrays (rows in any order, each pair once, ``a < b``)."""
+    shape = tuple(int(s) for s in shape)
+    if len(shape) not in (2, 3):
+        raise ValueError(f'contacts_from_arrays: 2-D or 3-D label arrays, got shape {shape}')
+    nd = len(shape)
+    cols = [np.asarray(a, dtype=np.int64).reshape(-1), np.asarray(b, dtype=np.int64).reshape(-1),
+            np.asarray(pairs, dtype=np.int64).reshape(-1, 13 if nd == 3 else 4)]
+    if len({len(c) for c in cols}) != 1:
+        raise ValueError('contacts_from_arrays: the columns differ in length')
+    if not (cols[0] < cols[1]).all() or (cols[0] < 0).any():
+        raise ValueError('contacts_from_arrays: every row needs 0 <= a < b')
+    if not background and (cols[0] == 0).any():
+        raise ValueError('contacts_from_arrays: a row with the background (a = 0) needs background=True')
+    order = np.lexsort((cols[1], cols[0]))
+    return LabelContacts(*(c[order] for c in cols), shape, P.contact_spacing(spacing, nd), bool(background), int(doublings))
+
+
+def _contacts_of_source(src, shape, spacing, background, device, slab, capacity):
+    rows, H, W = _geometry(shape, False, 'label_contacts')
+    spacing = P.contact_spacing(spacing, len(shape))      # refused before anything is allocated
+    table = GrowableTable('emp_label_contacts', 'label_contacts', capacity or min(initial_capacity(rows * H * W), MEASURE_MAX_CAPACITY), device)
+    # the slice below a slab's first one, as in _measures_of_source: in front of a device slab, kept in a buffer for a host one
+    halo = torch.empty(max(1, src.row_bytes), dtype=torch.uint8, device=device) if src.is_host else None
+    for _, z0, z1, (address,) in stream_slabs([src], slab, device):
+        below = None if z0 == 0 else (halo.data_ptr() if src.is_host else address - src.row_bytes)
+        table.add(address, src.ebytes, z0, z1 - z0, H, W, rows, below, int(background))
+        if src.is_host and z1 < rows:
+            _abi.check(table.lib.emp_copy_d2d(_abi.ptr(halo), address + (z1 - z0 - 1) * src.row_bytes, src.row_bytes, _abi.stream_ptr(device)),
+                       'emp_copy_d2d')
+    keys, _, pairs = (t.cpu().numpy() for t in table.finalize(extra=[(13, torch.int64)]))
+    keys = keys.view(np.uint64)      # sorted as unsigned: by (a, b)
+    a, b = (keys >> np.uint64(32)).astype(np.int64), (keys & np.uint64(0xffffffff)).astype(np.int64)
+    if len(shape) == 2:      # kernel (z, y, x) = image (y, 0, x)
+        pairs = pairs[:, list(P.SHAPE_IMAGE_COLUMNS)]
+    return LabelContacts(a, b, pairs, tuple(shape), spacing, background, table.doublings)
+
+
+@torch.no_grad()
+def label_contacts(labels, spacing=None, background=False, device=None, slab=None, capacity=None):
+    """The ``LabelContacts`` of a 2-D or 3-D label array (csrc/contacts.hip): which labels touch, over how many voxel pairs per
+    half-direction.  Sources, dtypes, ``slab`` and ``capacity`` as ``shape_labels``; labels lie in [0, 2^32): a pair takes one
+    64-bit key.  ``spacing``: the voxel size per axis (default 1).  ``background``: also enter the pairs of a label with the
+    background 0, as rows (0, b); ``fractions`` and ``merge_groups(min_fraction=...)`` need them.  A pair with an end outside
+    the array is never counted.  The raw columns are exact, do not depend on ``slab`` and are bit-reproducible.
+    Not built: ``per_slice`` (slice, a and b do not fit one key: call it per image), 4-D arrays, labels at or above 2^32."""
+    need_device()
+    device = pick_device(device, labels)
+    with torch.cuda.device(device):
+        src = source(labels, device)
+        return _contacts_of_source(src, src.shape, spacing, bool(background), device, slab, capacity)
 
 
 # ----------------------------------------------------------------------------

@@ -1026,6 +1026,51 @@ EMP_API int emp_label_shape_finalize(void* d_table, int64_t capacity, uint64_t* 
                                  int64_t* d_euler, int64_t max_out, int64_t* h_num, void* stream);
 
 /* ------------------------------------------------------------------------
+ * 7d. Contact Labels (csrc/contacts.hip): per unordered pair {a, b} of
+ *    different label values that occur next to each other, the number of
+ *    voxel pairs that join them along each of the 13 half-directions d_k of
+ *    section 7c -- the integers behind the area two objects share and behind
+ *    a region adjacency graph.  This section has no counterpart in the
+ *    reference plugin; the nearest thing is skimage's region adjacency graph
+ *    (skimage.graph.RAG, rag_boundary), and it is NOT pinned against skimage
+ *    (not available where this library is built): the tests state the
+ *    definition in numpy, and the sums over a label's partners are pinned
+ *    against section 7c's intercepts and section 7b's faces.
+ *
+ *      N[k] = #{p : p and p + d_k both in the array, {L(p), L(p + d_k)} = {a, b}}
+ *      count = sum_k N[k]; a pair exists exactly if its count is positive
+ *      key = min(a, b) << 32 | max(a, b), labels in [0, 2^32)
+ *
+ *    A pair with an end outside the array is never counted (there is no
+ *    border_faces here).  background 0: a pair with a 0 in it is not
+ *    entered; != 0: it is entered under the key (0, b).  There is no
+ *    per_slice: slice, a and b do not fit a 64-bit key.  Summed over the
+ *    partners b of a label a, 0 included, N[k](a, b) is I[k] of a in section
+ *    7c with border_faces 0.
+ *
+ *    The table has the life cycle and the overflow contract of sections 6,
+ *    7, 7b and 7c.  A slot is 120 bytes.  Every column is exact and does not
+ *    depend on the slabs.
+ * ---------------------------------------------------------------------- */
+/* 0 if the capacity is not a power of two in [64, 2^32] */
+EMP_API size_t emp_label_contacts_work_bytes(int64_t capacity);
+EMP_API int emp_label_contacts_reset(void* d_table, int64_t capacity, void* stream);
+/* Adds the pairs whose later end lies in the slab d_labels (depth, H, W), slices [z0, z0 + depth) of a volume of total_depth
+ * slices, to the table.  in_bytes in {1, 2, 4, 8}, negative = signed; total_depth < 2^31 and H, W < 2^30; a value outside
+ * [0, 2^32) -- an 8-byte value with a high word, a negative signed value -- is EMP_ERR_INVALID ("a label outside ...") and
+ * leaves the table undefined.  d_halo: slice z0 - 1 (H * W elements of the same type) on the device: the pairs across the
+ * slab's lower border are counted by this, the upper, slab and by no other; NULL for z0 == 0.  An image (R, W) is passed as the
+ * volume (R, 1, W): its four directions are k = 0, 7, 8, 9.  Synchronises the stream.  *h_overflow = 1 as in section 7b. */
+EMP_API int emp_label_contacts_accumulate(const void* d_labels, int in_bytes, int64_t z0, int depth, int H, int W, int64_t total_depth,
+                                 const void* d_halo, int background, void* d_table, int64_t capacity, void* stream, int* h_overflow);
+/* Re-inserts the counted cells of d_from into the reset, larger table d_to.  Synchronises.  *h_overflow = 1: d_to is too small too. */
+EMP_API int emp_label_contacts_grow(const void* d_from, int64_t from_capacity, void* d_to, int64_t to_capacity, void* stream, int* h_overflow);
+/* *h_num = the number of pairs, of which min(*h_num, max_out) are written, in no particular order: d_keys[i], d_counts[i],
+ * d_pairs[13 i ..] = N.  Synchronises.  The table stays valid and can be fed further. */
+EMP_API int emp_label_contacts_finalize(void* d_table, int64_t capacity, uint64_t* d_keys, uint64_t* d_counts, uint64_t* d_pairs /* 13 per row */,
+                                 int64_t max_out, int64_t* h_num, void* stream);
+
+/* ------------------------------------------------------------------------
  * 8. Morph Labels (csrc/morph.hip): binary dilation, erosion, closing and
  *    opening of single labels with a disk / ball of radius 1..7, every label
  *    inside its own padded box -- the plugin's Morph Labels
